@@ -7,31 +7,38 @@ BASELINE config 2 = 100 M mocker-shaped framed FlowMessages, 64 k SrcAS/DstAS
 pairs, 3 five-minute windows, 2 ETypes, per GPU (weak scaling: every rank is one
 Kafka partition with its own 100 M records).
 
-    python bench.py --gpus N --steps K --warmup W      (N > 1 without a torchrun environment: starts its own ranks)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                       (N > 1 without a torchrun environment: starts its own ranks)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (see the contract in the task description):
+Rank 0 prints ONE JSON line (see the contract in the task description).  A plain run holds the headline alone: the K steps
+timed in ONE bracket (`value`, `ms_per_step`) after an untimed settle phase that runs steps until two consecutive ones agree
+within 1 % (a fresh box starts at sclk 155 MHz) and the W warm-up steps; `settle`; `config`;
   roofline      wire bytes / hipEvent time of the WHOLE decode+aggregate path of a launch (ingest kernel +
                 second-chance parsers + tuple aggregation; SURVEY.md 8(d): t_kernel = decode + aggregate) vs the
-                8 TB/s HBM peak; the ingest kernel alone is reported beside it as `dominant_kernel`;
+                8 TB/s HBM peak; the ingest kernel alone is reported beside it as `dominant_kernel` (the library's events
+                of the timed launches: no run of its own).
+--dump-outputs DIR writes the flows_5m rows that the warm-up and timed steps added to the timed context (the rows a caller
+gets at window close, less what the settle phase put there) as DIR/flows_5m_<field>.npy.
+--full adds everything else, outside the timed region:
   cpu_baseline  the C oracle on this box's usable CPUs (affinity mask cut by the cgroup quota), thread sweep with
                 per-thread decode times, best run; N=1 only;
   parity        every record of the step verified against the oracle (per-chunk row checksums), outside the
                 timed region, on every rank; N>1: also the rows merged across ranks at window close against the
                 oracle's rollup of all partitions;
   host_fed      the PCIe-inclusive rate through fa_ingest (host buffers) - a secondary figure, never `value`.
-  ms_per_step_all / ms_per_step_median / settle
-                the headline's K steps are timed in ONE bracket (the contract: `value`, `ms_per_step`); before it an untimed
-                settle phase runs steps until two consecutive ones agree within 1 % (a fresh box starts at sclk 155 MHz), and
-                behind it the same K steps run once more, each with its own fence: per-step times and their median.
+  ms_per_step_all / ms_per_step_median
+                behind the timed bracket the same K steps run once more, each with its own fence: per-step times and their median.
+  clocks        sclk / mclk from rocm-smi before and after the steps.
   secondary     (N = 1, default workload) the other BASELINE configurations and the consumer on the SAME driver clock, each with
                 its own parity booleans against the oracle and `ok`: config3_exact / config3_candidates (configs[2], 200 M
                 records), config5 (configs[4] single-GPU shape, 100 M records: ingest fraction AND close time of one run),
                 group8 (8 contexts in one process through fa_group_*), host_consume (the C++ consumer, 8 partition logs of
                 config 2's stream).  --no-secondary skips them; they never change metric / value / config.
-  group_preflight
-                (N > 1) rank 0 creates one small ctx on EVERY visible device and runs the in-process group close (fa_group_*:
-                peer copies AND ncclCommInitAll) on known partitions against the oracle - reported, never fatal.
+  preflight / group_preflight
+                (N > 1) the three window-close exchanges on known data; rank 0 creates one small ctx on EVERY visible device and
+                runs the in-process group close (fa_group_*: peer copies AND ncclCommInitAll) on known partitions against the
+                oracle - reported, never fatal.
 Other workloads (side measurements, their JSON goes to profiles/): --mode zipf --key-sets 7 (config 3 shape),
 --key-sets 9 (config 5 shape), --mode goflow / reversed (67-field producer / order-free parser), --stage decode
 (projection only).
@@ -55,6 +62,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 # sources this process runs (source_hash stamp).
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "r06_traffic.json")
 SOA_BYTES_PER_RECORD = 5 * 8 + 7 * 4 + 3 * 16 + 1  # fa_columns: 15 columns + status byte
+DUMP_LIMIT_BYTES = 60 * 10**6  # --dump-outputs: the arrays' data stays below 64 MB, .npy headers included
 
 
 def pmc_traffic(fa, default_workload):
@@ -91,6 +99,33 @@ def rows_checksum(rows):
         h = mix64(a ^ mix64(b))
         v = rows["bytes"] * np.uint64(3) + rows["packets"] * np.uint64(5) + rows["count"] * np.uint64(7) + np.uint64(1)
         return int((h * v).sum(dtype=np.uint64))
+
+
+def rows_added(before, after):
+    """flows_5m rows (sorted by key, as the library returns them) of what was ingested between two reads of one window:
+    `after`'s sums less `before`'s, mod 2^64.  Every step ingests the same records, so both reads hold the same groups."""
+    if len(before) == 0:
+        return after
+    keys = ("date", "timeslot", "src_as", "dst_as", "etype")
+    if len(before) != len(after) or any(not np.array_equal(before[k], after[k]) for k in keys):
+        raise RuntimeError("the window's groups changed between the steps (%d -> %d rows)" % (len(before), len(after)))
+    out = after.copy()
+    with np.errstate(over="ignore"):
+        for f in ("bytes", "packets", "count"):
+            out[f] = after[f] - before[f]
+    return out
+
+
+def dump_outputs(path, rows):
+    """--dump-outputs: every field of the rows as DIR/flows_5m_<field>.npy in float64 (keys are 32-bit, a group's sums stay
+    far below 2^53: exact).  Rows beyond DUMP_LIMIT_BYTES: a fixed seeded sample, the same rows for the same arguments."""
+    fields = [f for f in rows.dtype.names if not f.startswith("_")]
+    cap = DUMP_LIMIT_BYTES // (8 * len(fields))
+    if len(rows) > cap:
+        rows = rows[np.sort(np.random.default_rng(0).choice(len(rows), cap, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for f in fields:
+        np.save(os.path.join(path, "flows_5m_%s.npy" % f), rows[f].astype(np.float64))
 
 
 def effective_cpus():
@@ -899,7 +934,15 @@ def main():
     ap.add_argument("--secondary-config5-records", type=int, default=100_000_000)
     ap.add_argument("--secondary-host-records", type=int, default=64_000_000)
     ap.add_argument("--settle-max-steps", type=int, default=400, help="untimed settle phase: at most this many steps (it ends when two consecutive steps agree within 1 %%)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: per-step times, parity against the oracle, "
+                    "cpu_baseline, host_fed, secondary, clocks and (world > 1) the preflights; a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the flows_5m rows the warm-up and timed steps added to DIR/flows_5m_<field>.npy "
+                    "(float64, sorted by key; a fixed seeded sample of the rows beyond %d MB)" % (DUMP_LIMIT_BYTES // 10**6))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.stage == "decode":
+        ap.error("--dump-outputs writes flows_5m rows: not with --stage decode")
     if args.group_preflight_only:
         group_preflight_body()
         return
@@ -923,7 +966,7 @@ def main():
     dev = torch.device("cuda", local_rank)
     xdev = dev if backend == "nccl" else torch.device("cpu")  # where the window-close exchange tensors live
     gpre = None
-    if world > 1 and rank == 0 and not args.no_group_preflight:
+    if world > 1 and rank == 0 and args.full and not args.no_group_preflight:
         # the product's OTHER multi-GPU form - one process, a ctx per device, fa_group_* - has never run on more than one device:
         # rank 0 runs it on every visible device in a process of its own BEFORE it joins the process group (the other ranks wait in
         # init_process_group's rendezvous, on the CPU - not inside a collective that spins on their GPUs)
@@ -942,9 +985,9 @@ def main():
     mode = {"mocker": fa.MOCK_MOCKER, "aspairs": fa.MOCK_ASPAIRS, "zipf": fa.MOCK_ZIPF, "goflow": fa.MOCK_GOFLOW,
             "reversed": fa.MOCK_REVERSED, "distinct": fa.MOCK_DISTINCT}[args.mode]
     n_rec = args.records // world if args.strong else args.records
-    clocks = {"start": gpu_clocks(local_rank)} if rank == 0 else None
+    clocks = {"start": gpu_clocks(local_rank)} if rank == 0 and args.full else None
     pre = None
-    if world > 1 and not args.no_preflight:
+    if world > 1 and args.full and not args.no_preflight:
         pre = preflight(fa, torch, dist, rank, world, local_rank, backend, xdev, strict=args.strict_preflight)
     # every rank = one Kafka partition with its own stream (seed 2 = config 2, + rank)
     mp = fa.mock_params(mode=mode, framed=1, seed=2 + rank, n_total=n_rec, span_secs=900, per_sec=400_000,
@@ -1007,6 +1050,8 @@ def main():
             done = int(t.item()) == 0
         if done:
             break
+    # (the settle phase's length varies from run to run: the dumped rows are what the steps after it added)
+    settled_rows = agg.read_window() if args.dump_outputs else None
     for _ in range(args.warmup):
         step()
     fence()
@@ -1017,8 +1062,13 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     st1 = agg.stats()
+    dump_rows = None
+    if args.dump_outputs:
+        dump_rows = rows_added(settled_rows, agg.read_window())
+        if world > 1:
+            dump_rows = fa.dist.merge_rows_host(fa.dist.allgather_struct(dump_rows, fa.dist.ROW5M_DTYPE, device=xdev))
     # the same K steps once more, each with its own fence (sync overhead included: ~20 us of a 2 ms step) - not `value`
-    per_step_ms = [timed_step() for _ in range(args.steps)]
+    per_step_ms = [timed_step() for _ in range(args.steps)] if args.full else []
     extra_steps = len(settle_ms) + len(per_step_ms)
     if clocks is not None:
         clocks["end"] = gpu_clocks(local_rank)
@@ -1037,8 +1087,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3,
-        "ms_per_step_median": float(np.median(per_step_ms)) if per_step_ms else None,
-        "ms_per_step_all": [round(x, 4) for x in per_step_ms],
         "settle": {"steps": len(settle_ms), "first_ms": round(settle_ms[0], 4) if settle_ms else None, "last_ms": round(settle_ms[-1], 4) if settle_ms else None,
                    "rule": "untimed steps until two consecutive ones agree within 1 % (>= 8, <= --settle-max-steps)"},
         "higher_is_better": True,
@@ -1047,6 +1095,9 @@ def main():
         "dtype": "u64",
         "data": "synthetic",
     }
+    if args.full:
+        common["ms_per_step_median"] = float(np.median(per_step_ms))
+        common["ms_per_step_all"] = [round(x, 4) for x in per_step_ms]
 
     if decode_stage:
         launches = st1["decode_launches"] - st0["decode_launches"]
@@ -1178,7 +1229,7 @@ def main():
         out["roofline"]["per_rank_dominant_kernel_ms"] = [float(x[1].item()) for x in allt]
         out["roofline"]["note"] = "achieved / frac are rank 0's; value is the whole job over the slowest rank's wall clock"
 
-    if not args.no_verify and not args.no_assert:
+    if args.full and not args.no_verify and not args.no_assert:
         # parity on the WHOLE step, every rank its own partition: every chunk again through a fresh ctx, its rows against
         # the oracle's rows for the same records (order-independent checksum of (key, sums); u64 sums commute, so equal
         # chunk results = equal step).  N > 1 additionally: the rows the ranks merged at window close (RCCL all-gather +
@@ -1238,13 +1289,13 @@ def main():
         out["parity"] = parity
         assert parity["ok"], "GPU rows differ from the oracle: %r" % (parity,)
 
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         po = _pkg.load_oracle()
         gp = po.gen_params(mode=mode, framed=1, seed=2, n_total=n_rec, span_secs=900, per_sec=400_000, zipf_s_x100=args.zipf_s,
                            zipf_log2_universe=args.zipf_universe_log2)
         out["cpu_baseline"] = cpu_baseline(po, gp, min(args.cpu_sample, n_rec), n_rec, int(len(merged)))
 
-    if rank == 0 and world == 1 and not args.no_host_fed and not args.no_assert:
+    if args.full and rank == 0 and world == 1 and not args.no_host_fed and not args.no_assert:
         # the path a Kafka consumer uses: host buffers -> pinned staging -> H2D -> the same kernels (never `value`)
         nh = min(8_000_000, n_rec)
         hb, ho = fa.mock_generate_host(mp, 0, nh)
@@ -1264,9 +1315,11 @@ def main():
     agg.close()
     del chunks
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and default_workload and not (args.no_secondary or args.no_assert or args.no_verify or args.cpu_sample <= 0):  # (measurement runs of the tools skip them)
+    if args.full and rank == 0 and world == 1 and default_workload and not (args.no_secondary or args.no_assert or args.no_verify or args.cpu_sample <= 0):  # (measurement runs of the tools skip them)
         out["secondary"] = run_secondary(fa, _pkg.load_oracle(), torch, dev, args)
     if rank == 0:
+        if dump_rows is not None:
+            dump_outputs(args.dump_outputs, dump_rows)
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

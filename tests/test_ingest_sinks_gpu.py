@@ -386,7 +386,7 @@ def test_bench_harness_two_ranks_dry_run(gpu_lib):
     """bench.py's N>1 path (per-rank partitions, barrier + max-over-ranks timing, window close merged across ranks,
     merged top-k) on the 1-GPU box: both ranks on device 0, exchange over gloo.  Never a reported configuration."""
     r = _torchrun(2, ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--records", "2000000", "--chunk", "1000000",
-                      "--mode", "zipf", "--key-sets", "3", "--cpu-sample", "0"],
+                      "--mode", "zipf", "--key-sets", "3", "--cpu-sample", "0", "--full"],
                   {"FA_BENCH_BACKEND": "gloo", "FA_BENCH_SHARE_GPU": "1"})
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -404,7 +404,7 @@ def test_bench_launches_its_own_ranks(gpu_lib):
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--records", "3000000",
-                        "--chunk", "1000000"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--chunk", "1000000", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["scaling"] == "weak"
@@ -450,7 +450,7 @@ def test_bench_side_measurements_run(gpu_lib):
     """The side-measurement modes of bench.py produce a line (small sizes; numbers are not judged here)."""
     for extra in (["--stage", "decode"], ["--mode", "goflow"], ["--mode", "reversed"]):
         r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--records", "2000000", "--chunk", "1000000",
-                            "--cpu-sample", "0", "--no-host-fed"] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                            "--cpu-sample", "0", "--no-host-fed", "--full"] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
         assert r.returncode == 0, (extra, r.stdout[-1000:], r.stderr[-3000:])
         out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert out["roofline"]["frac"] > 0, extra
@@ -458,6 +458,30 @@ def test_bench_side_measurements_run(gpu_lib):
             assert out["config"]["records_second_chance_parser"] == 0 and out["parity"]["ok"]
         if extra == ["--mode", "reversed"]:
             assert out["config"]["records_second_chance_parser"] == 2_000_000 and out["parity"]["ok"]
+
+
+def test_bench_plain_run_dumps_the_rows_of_its_steps(gpu_lib, po, tmp_path):
+    """A plain bench.py run carries the headline alone (nothing that --full adds), and --dump-outputs writes the flows_5m rows
+    of its warm-up + timed steps: the oracle's rollup of one step's records x (W + K), whatever the settle phase ran."""
+    n, warmup, steps = 2_000_000, 1, 2
+    r = subprocess.run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", str(warmup), "--records", str(n), "--chunk", "1000000",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == steps and out["warmup"] == warmup and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["unit"] == "FlowMessages/s" and out["higher_is_better"] is True and out["dtype"] == "u64"
+    for k in ("parity", "cpu_baseline", "host_fed", "secondary", "clocks", "ms_per_step_all", "ms_per_step_median"):
+        assert k not in out, k
+    assert out["settle"]["steps"] >= 8
+    gp = po.gen_params(mode=po.GEN_ASPAIRS, framed=1, seed=2, n_total=n, span_secs=900, per_sec=400_000, zipf_s_x100=110, zipf_log2_universe=24)
+    buf, off = po.gen_records(gp, 0, n)
+    ref = po.Rollup(300)
+    assert ref.ingest(buf, off, 1) == 0
+    want = ref.rows()
+    assert out["config"]["groups"] == len(want)
+    for f in ("date", "timeslot", "src_as", "dst_as", "etype", "bytes", "packets", "count"):
+        got = np.load(tmp_path / ("flows_5m_%s.npy" % f))
+        assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint64), want[f] * np.uint64(1 if f not in ("bytes", "packets", "count") else warmup + steps)), f
 
 
 @pytest.mark.parametrize("cap_log2", [10, 12, 13, 14])
