@@ -128,7 +128,10 @@ struct fa_ctx {
     bool cms_atomic = false;  // env FA_CMS=atomic (A/B, tests): every sketch update through memory-side atomics
     bool cms_scatter_ok = false;  // the sketch geometry fits the scatter sink (256 partitions of <= 2^14 counters)
     int sink_mode = 0;  // 0 auto, 1 direct, 2 scatter (env FA_SINK)
-    bool use_wave_tiles = false;  // decision for the batch being launched
+    // decision for the batch being launched: the scatter sink, whose kernel is the wave-tile kernel (15-20 % faster than the
+    // 256-thread workgroup-tile kernel when most records leave as tuples); the workgroup-tile kernel serves the decode path,
+    // the direct sink (small batches) and key sets without the flows_5m rollup
+    bool use_wave_tiles = false;
     bool use_t8 = false;          // ... compact 8-byte tuples (table.cuh) for it
     // tuple format feedback: compact tuples while (almost) every record fits them.  A launch whose misfits (records
     // that only a wide tuple holds - they took the direct path) exceed 1/16 of its records switches the ctx to wide
@@ -142,15 +145,9 @@ struct fa_ctx {
     uint32_t agg_passes_forced = 0;  // env FA_AGG_PASSES (tests, A/B)
     uint32_t agg_passes = 1;      // agg8_kernel passes for the next launch (1, 2, 4, 8): groups per launch / (partitions x passes) <= half the LDS table
     unsigned stage_threads = 8;   // host threads of the staging copy (fa_ingest)
-    bool agg_generic = false;     // env FA_AGG=generic (A/B): compact tuples through the two-word-key aggregation kernel
     uint32_t par = 0;             // parity of the next launch (Counters::exotic_count / retry_count copies)
     uint32_t seg_cap_limit = 0;   // env FA_SEG_CAP (tests only): upper bound on tuples per segment
     uint32_t last_nwg = 0;        // workgroups of the last scatter-sink launch (FA_VERBOSE: reads its segment counts back)
-    // ingest kernel (env FA_TILE=wave|wg, measurement / tests): wave-private tiles + LDS tuple bins is the
-    // production kernel of the scatter sink (never slower than the 256-thread workgroup-tile kernel on the
-    // workloads measured, 15-20 % faster when most records leave as tuples); the workgroup kernel serves the
-    // decode path, the direct sink (small batches) and key sets without the flows_5m rollup.
-    int tile_mode = 0;  // 0 default (wave), 1 wave, 2 workgroup
     uint32_t plog2 = PART_LOG2_MAX, wgpc_cap = 0;  // experiment knobs (env FA_PLOG2, FA_WGPC)
 
     // host-fed path: pinned staging (double buffered) + device input
@@ -374,9 +371,7 @@ extern "C" int fa_create(const fa_config* cfg_in, fa_ctx** out) {
     if (const char* d = getenv("FA_PLOG2")) c->plog2 = std::min<uint32_t>(PART_LOG2_MAX, std::max<uint32_t>(4, (uint32_t)atoi(d)));
     if (const char* d = getenv("FA_WGPC")) c->wgpc_cap = (uint32_t)atoi(d);
     if (const char* d = getenv("FA_SEG_CAP")) c->seg_cap_limit = std::max<uint32_t>(40u, (uint32_t)atoi(d) & ~7u);
-    if (const char* d = getenv("FA_TILE")) c->tile_mode = !strcmp(d, "wave") ? 1 : !strcmp(d, "wg") ? 2 : 0;
     if (const char* d = getenv("FA_SINK")) c->sink_mode = !strcmp(d, "direct") ? 1 : !strcmp(d, "scatter") ? 2 : 0;
-    if (const char* d = getenv("FA_AGG")) c->agg_generic = !strcmp(d, "generic");
     if (const char* d = getenv("FA_CMS")) c->cms_atomic = !strcmp(d, "atomic");
     if (const char* d = getenv("FA_WIDE")) c->wide_mode = !strcmp(d, "atomic") ? 1 : !strcmp(d, "scatter") ? 2 : !strcmp(d, "log") ? 3 : 0;
     if (const char* d = getenv("FA_WIDE_LOG_CHUNKS")) c->wlog_max = (size_t)std::max(0, atoi(d));
@@ -439,8 +434,7 @@ extern "C" int fa_create(const fa_config* cfg_in, fa_ctx** out) {
         }
         // (the side stream of the ingest path - launch_tiles: the flows_5m tuple aggregation runs on it beside the sketch fold - is
         // created here: a stream costs milliseconds, not a thing for the first ingest launch)
-        const bool want_side = cfg.topk_mode == FA_TOPK_CANDIDATES && (getenv("FA_AGG_SIDE") == nullptr || strcmp(getenv("FA_AGG_SIDE"), "0") != 0);
-        if (want_side) {  // (only the candidates mode uses it: every stream of a process competes for its few hardware queues)
+        if (cfg.topk_mode == FA_TOPK_CANDIDATES) {  // (only the candidates mode uses it: every stream of a process competes for its few hardware queues)
             if ((e = hipStreamCreateWithFlags(&c->cand_stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate(side stream)", e);
             for (int i = 0; i < 2; i++)
                 if ((e = hipEventCreateWithFlags(&c->cand_ev[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);

@@ -1,5 +1,5 @@
 // ingest.cuh - the ingest kernels: per-record work (parse -> key -> sink), the LDS tuple bins, the wave-tile
-// kernel (production), the workgroup-tile kernel (decode path / direct sink), probe and deferred kernels.
+// kernel (production), the workgroup-tile kernel (decode path / direct sink), the deferred kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -218,7 +218,7 @@ __device__ __forceinline__ void lane_work(const KArgs& a, LdsTable<LDS_SLOTS>& l
                 else lt_seen = lt_hits = 0;
             }
         }
-        // tuple path: one tuple to this workgroup's private segment of the key's partition
+        // tuple path (the scatter sink: wave-tile kernel only): one tuple to this workgroup's private segment of the key's partition
         uint32_t fill_part = 0xffffffffu;  // wave-tile kernel: the bin this lane has just filled
         bool fits = false;
         uint32_t part = 0;
@@ -274,12 +274,6 @@ __device__ __forceinline__ void lane_work(const KArgs& a, LdsTable<LDS_SLOTS>& l
                         lds_add_u32(&part_cnt[part], 0xffff0000u);  // (not stored: -1 on the back count, which never wraps into stored tuples)
                     }
                 }
-            }
-        } else if (!T8 && pending && fits) {  // workgroup-tile kernel: straight into the segment
-            const uint32_t q = atomicAdd(&part_cnt[part], 1u);
-            if (q < a.capq) {
-                if (!(FA_DBG(a, DBG_NO_TUPLE_STORE))) a.seg[(size_t)part * a.region + (size_t)blockIdx.x * a.capq + q] = tv;
-                pending = false;
             }
         }
         fill_out = fill_part;  // full bins leave in bins_flush(), which the wave-tile kernel runs right after this call
@@ -361,7 +355,7 @@ __device__ __forceinline__ void block_counters_add(uint32_t* lds4, Counters* ctr
 // 64 evenly spaced records are decoded by the 64 lanes of a wave; tb_base = (smallest time bucket seen) - 2, so
 // that the 4-bit relative bucket of the tuple path covers the batch (Kafka partitions are close to time-ordered;
 // records outside [tb_base, tb_base+16) take the direct path).  Wave-uniform result, the same for every wave that
-// asks: the wave-tile kernel evaluates it in its prologue; the workgroup-tile kernel gets it from probe_kernel.
+// asks: the wave-tile kernel evaluates it in its prologue.
 __device__ __forceinline__ uint32_t probe_tb_base(const KArgs& a) {
     const uint32_t ln = __lane_id();
     const uint32_t idx = a.n <= 64 ? ln : (uint32_t)(((uint64_t)ln * (a.n - 1)) / 63u);
@@ -400,10 +394,6 @@ __device__ __forceinline__ uint32_t probe_tb_base(const KArgs& a) {
     for (int o = 32; o > 0; o >>= 1) lo = min(lo, (uint32_t)__shfl_xor((int)lo, o));
     lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
     return lo == 0xffffffffu ? 0u : (lo > 2u ? lo - 2u : 0u);
-}
-__global__ __launch_bounds__(64) void probe_kernel(KArgs a) {
-    const uint32_t tb = probe_tb_base(a);
-    if (threadIdx.x == 0) a.ctr->tb_base = tb;
 }
 
 // ---- the tile kernel ----------------------------------------------------------
@@ -452,16 +442,12 @@ __global__ __launch_bounds__(BLOCK) void tile_kernel(KArgs a) {
     constexpr uint32_t COLS = MODE == MODE_DECODE ? (uint32_t)COL_ALL : cols_for_keysets<KEYSETS>();
     __shared__ __attribute__((aligned(16))) uint32_t tile[TILE_STRIDE / 4];
     __shared__ LdsTable<LDS_SLOTS> lt;
-    __shared__ uint32_t part_cnt[NPART_MAX];  // tuples this workgroup appended per key partition
-    __shared__ LdsMinutes lm;                 // per-minute series pre-aggregation (KS_ALL variant only)
+    __shared__ uint32_t ctr_scratch[NPART_MAX];  // block_counters_add (5 words; the LDS footprint stays the one measured at 6 workgroups per CU)
+    __shared__ LdsMinutes lm;                    // per-minute series pre-aggregation (KS_ALL variant only)
 
     const uint32_t tid = threadIdx.x;
-    if (MODE == MODE_INGEST && (KEYSETS & FA_KEYS_AS_PAIR)) {
-        lds_table_clear(lt);
-        for (int i = tid; i < NPART_MAX; i += BLOCK) part_cnt[i] = 0;
-    }
+    if (MODE == MODE_INGEST && (KEYSETS & FA_KEYS_AS_PAIR)) lds_table_clear(lt);
     if (MODE == MODE_INGEST && (KEYSETS & FA_KEYS_MINUTE_SERIES)) lds_minutes_clear(lm);
-    const uint32_t tb_base = MODE == MODE_INGEST ? a.ctr->tb_base : 0u;
 
     LaneTally tally;
     uint32_t lt_seen = 0, lt_hits = 0, no_fill = 0, pmode = 0;
@@ -509,7 +495,7 @@ __global__ __launch_bounds__(BLOCK) void tile_kernel(KArgs a) {
                 unsigned int j = atomicAdd(&a.ctr->exotic_count[a.par], 1u);
                 a.exotic_idx[j] = cur.r0 + tid;
             }
-            lane_work<MODE, KEYSETS, COLS>(a, lt, lm, part_cnt, tile, mine, o0 - cbase, o1 - cbase, cur.r0 + tid, tb_base, tally, pmode, lt_seen, lt_hits, nullptr, nullptr, no_fill);
+            lane_work<MODE, KEYSETS, COLS>(a, lt, lm, nullptr, tile, mine, o0 - cbase, o1 - cbase, cur.r0 + tid, 0u, tally, pmode, lt_seen, lt_hits, nullptr, nullptr, no_fill);
         } else if (!cur_sane) {  // broken bounds: every record of the tile to the generic path (which checks them one by one)
             if (tid < cur.nrec) {
                 unsigned int j = atomicAdd(&a.ctr->exotic_count[a.par], 1u);
@@ -542,7 +528,7 @@ __global__ __launch_bounds__(BLOCK) void tile_kernel(KArgs a) {
                     }
                     done += 1;
                 } else {
-                    lane_work<MODE, KEYSETS, COLS>(a, lt, lm, part_cnt, tile, mine, p0 - cbase, p1 - cbase, cur.r0 + k, tb_base, tally, pmode, lt_seen, lt_hits, nullptr, nullptr, no_fill);
+                    lane_work<MODE, KEYSETS, COLS>(a, lt, lm, nullptr, tile, mine, p0 - cbase, p1 - cbase, cur.r0 + k, 0u, tally, pmode, lt_seen, lt_hits, nullptr, nullptr, no_fill);
                     done += nfit;
                 }
                 __syncthreads();  // the buffer is restaged by the next pass
@@ -595,14 +581,7 @@ __global__ __launch_bounds__(BLOCK) void tile_kernel(KArgs a) {
                 quad_atomic_update(sp, b, p, c);
             }
         }
-        if ((KEYSETS & FA_KEYS_AS_PAIR) && a.seg) {
-            for (int i = tid; i < (1 << a.plog2); i += BLOCK)
-{
-                a.seg_counts[(size_t)i * a.nwg + blockIdx.x] = min(part_cnt[i], a.capq);
-                a.seg_counts[((size_t)NPART_MAX + i) * a.nwg + blockIdx.x] = 0;
-            }
-        }
-        block_counters_add(part_cnt, a.ctr, tally);  // (part_cnt has been written out: reused as scratch)
+        block_counters_add(ctr_scratch, a.ctr, tally);
     }
 }
 

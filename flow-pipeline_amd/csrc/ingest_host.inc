@@ -1,8 +1,7 @@
 // ingest_host.inc - the ingest path: tuple segments, device-side framing, launches, host staging (included by flowagg.hip: one translation unit, see kernels.cuh for the device side).
 
 // ---- ingest ---------------------------------------------------------------------------
-// Launch order on the ctx stream: tile -> deferred -> [agg]   (wave-tile kernel: it finds the batch's time base
-// itself; the workgroup-tile kernel with the scatter sink still takes it from probe_kernel).
+// Launch order on the ctx stream: tile -> deferred -> [agg]   (the wave-tile kernel finds the batch's time base itself).
 template <int MODE>
 static int launch_tiles(fa_ctx* c, KArgs& a, int grid, fa_ctx::LaunchEvents* ev = nullptr) {
     dim3 b(BLOCK);
@@ -10,21 +9,19 @@ static int launch_tiles(fa_ctx* c, KArgs& a, int grid, fa_ctx::LaunchEvents* ev 
     dim3 ge(std::min(256u, (a.n + BLOCK - 1) / BLOCK));
     a.par = c->par;
     c->par ^= 1u;
-    const bool wave_tiles = MODE == MODE_INGEST && a.seg != nullptr && a.tile_recs <= (uint32_t)WT_RECS && c->use_wave_tiles;
+    const bool wave_tiles = MODE == MODE_INGEST && a.seg != nullptr && c->use_wave_tiles;
     const bool t8 = wave_tiles && c->use_t8;
     // (the second-chance kernel runs in line: on a side stream beside the aggregation it cost MORE - 66 vs 58 us for
     // deferred + aggregation per launch, the cross-stream hand-over being slower than the 4.5 us kernel - and its atomic
     // upserts would race with the region-owned plain stores of agg8_kernel / cms_agg_kernel; the knob is gone)
     hipStream_t dstream = c->stream;
     if (ev) (void)hipEventRecord(ev->e0, c->stream);
-    if (MODE == MODE_INGEST && a.seg && !wave_tiles) hipLaunchKernelGGL(probe_kernel, dim3(1), dim3(64), 0, c->stream, a);
     // most records of the last launches needed the order-free parser: the kernel that learns a field order per wave (ingest.cuh tier 4)
     const bool seq_variant = wave_tiles && c->cfg.key_sets == FA_KEYS_AS_PAIR && c->seq_mode != 2 && (c->seq_mode == 1 || c->stats.batches < c->seq_until);
     if (seq_variant) c->stats.learnt_order_launches += 1;
     // the sketch variants exist once per top-k contract (the contract as a template argument: the exact mode's kernel carries no
     // candidate test, the candidates mode's no probe of the big sets in its tile loop - config 3: 1.15 -> 1.08 ms and 1.115 -> 1.055 ms
-    // per launch, same box); FA_CAND_VARIANTS=0: the one kernel that reads the contract from its arguments (A/B)
-    static const bool cand_variants = getenv("FA_CAND_VARIANTS") == nullptr || strcmp(getenv("FA_CAND_VARIANTS"), "0") != 0;
+    // per launch, same box); without sketch segments: the kernel that reads the contract from its arguments
     if (wave_tiles) c->stats.wave_tile_launches += 1;
     if (t8) c->stats.compact_tuple_launches += 1;
     // the bucket range of the wide tuples this launch leaves in its segments starts empty (Counters::wtb_min, wtb_nmax)
@@ -32,7 +29,7 @@ static int launch_tiles(fa_ctx* c, KArgs& a, int grid, fa_ctx::LaunchEvents* ev 
 #define FA_LAUNCH_W(KS)                                                                         \
     do {                                                                                        \
         if constexpr ((KS & 6u) != 0u && KS != KS_ALL) {  /* a sketch: a kernel per top-k contract */ \
-            if (cand_variants && a.cseg) {                                                      \
+            if (a.cseg) {                                                      \
                 if (c->cand_state) {                                                            \
                     if (t8) hipLaunchKernelGGL((wtile_kernel<KS, true, false, 1>), g, dim3(wtile_block<KS>()), 0, c->stream, a); \
                     else hipLaunchKernelGGL((wtile_kernel<KS, false, false, 1>), g, dim3(wtile_block<KS>()), 0, c->stream, a);   \
@@ -85,10 +82,8 @@ static int launch_tiles(fa_ctx* c, KArgs& a, int grid, fa_ctx::LaunchEvents* ev 
     //   side stream  [flows_5m tuple aggregation: agg8_kernel / agg_kernel]
     // The boundary's two small kernels (52 us of BASELINE config 3's 1.03 ms) and the tails of the two big ones - each one LDS-filling
     // workgroup per CU - overlap: 1.017-1.034 -> 0.966-0.983 ms per launch, same box (profiles/r06_exp_agg_side_stream.jsonl).
-    // FA_AGG_SIDE=0: everything in line on the ctx stream (A/B).
-    static const bool agg_side = getenv("FA_AGG_SIDE") == nullptr || strcmp(getenv("FA_AGG_SIDE"), "0") != 0;
     // (candidates mode only: in the exact mode the two big kernels gain nothing from each other - measured 0 .. +1 % - and stay in line)
-    const bool side = MODE == MODE_INGEST && agg_side && wave_tiles && a.seg && a.cseg && c->cand_stream && c->cand_state;
+    const bool side = MODE == MODE_INGEST && wave_tiles && a.cseg && c->cand_stream && c->cand_state;
     hipStream_t agg_stream = c->stream;
     if (side) {
         HIPCHK(c, hipEventRecord(c->cand_ev[0], c->stream));
@@ -96,40 +91,49 @@ static int launch_tiles(fa_ctx* c, KArgs& a, int grid, fa_ctx::LaunchEvents* ev 
         agg_stream = c->cand_stream;
     }
     if (MODE == MODE_INGEST && a.seg) {
-        const dim3 ga((1u << a.plog2) * AGG_SPLIT);
-        if (t8 && AGG_SPLIT == 1 && !c->agg_generic) hipLaunchKernelGGL(agg8_kernel, ga, dim3(AGG_BLOCK), 0, agg_stream, a);
-        else if (t8) hipLaunchKernelGGL(agg_kernel<true>, ga, dim3(AGG_BLOCK), 0, agg_stream, a);
-        else hipLaunchKernelGGL(agg_kernel<false>, ga, dim3(AGG_BLOCK), 0, agg_stream, a);
+        const dim3 ga(1u << a.plog2);
+        if (t8) hipLaunchKernelGGL(agg8_kernel, ga, dim3(AGG_BLOCK), 0, agg_stream, a);
+        else hipLaunchKernelGGL(agg_kernel, ga, dim3(AGG_BLOCK), 0, agg_stream, a);
     }
-    if (side) HIPCHK(c, hipEventRecord(c->cand_ev[1], c->cand_stream));
-    if (MODE == MODE_INGEST && wave_tiles && a.cseg) {  // fold the sketch tuples (Count-Min scatter sink)
-        const uint32_t set_mask = (c->cfg.key_sets >> 1) & 3u;
-        const uint32_t nlog = CMS_NPART * (set_mask == 3u ? 2u : 1u);
-        hipLaunchKernelGGL(cms_agg_kernel, dim3(std::min<uint32_t>((uint32_t)c->num_cus, nlog)), dim3(AGG_BLOCK), 0, c->stream, a, set_mask, c->cms_par);  // persistent: one per CU
-        c->cms_par ^= 1u;
-    }
-    // candidates mode: the launch boundary - theta of this boundary and the bits the NEXT launch tests its addresses against
-    // (behind every kernel of the launch that adds to a sketch: hot-address flushes, the atomic paths, cms_agg_kernel)
-    if (MODE == MODE_INGEST && c->cand_state) {
-        HIPCHK(c, hipMemsetAsync(c->cand_state, 0, 2 * sizeof(CandState), c->stream));
-        const dim3 gs(CAND_SCAN_BLOCKS, 2), gb(256, 2);
-        hipLaunchKernelGGL(cand_scan_kernel, gs, dim3(256), 0, c->stream, c->ks_src, c->ks_dst, 1u << c->ks_log2, (const unsigned long long*)c->cms_src,
-                           (const unsigned long long*)c->cms_dst, c->cfg.cms_depth, c->cfg.cms_width_log2, c->cfg.cms_seed, c->cand_state, c->cand_chunkmax);
-        hipLaunchKernelGGL(cand_bits_kernel, gb, dim3(256), 0, c->stream, (const KeySlot*)c->ks_src, (const KeySlot*)c->ks_dst, (const unsigned long long*)c->cms_src,
-                           (const unsigned long long*)c->cms_dst, c->cfg.cms_depth, c->cfg.cms_width_log2, c->cfg.topk_track, std::max(c->ks_log2, 8u) - 2u, c->cand_state,
-                           c->cand_bits[0], c->cand_bits[1]);
-    }
-    // fold the (SrcAddr,DstPort,Proto) tuples: one workgroup per table region, plain loads and stores - behind every
-    // dispatch of this launch that updates the wide table with atomics (wagg.cuh)
-    if (MODE == MODE_INGEST && wave_tiles && a.wseg) {
-        if (c->wlog_now) {  // log mode: the tuples stay where they are (the chunk is taken over behind the launch: wlog_record)
-            // (the time base and the tuples' bucket range, three words: Counters::tb_base, wtb_min, wtb_nmax)
-            HIPCHK(c, hipMemcpyAsync(c->wseg_counts + c->wseg_counts_cap, &c->d_ctr->tb_base, 3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-        } else {
-            hipLaunchKernelGGL(wagg_kernel, dim3(1u << a.wplog2), dim3(WAGG_BLOCK), 0, c->stream, a, (const uint32_t*)nullptr, 0u);
+    // Nothing returns between the fork and the join: the ctx stream's part is a lambda, whose early returns (HIPCHK) end that
+    // part only - on every way out of this launch the ctx stream waits for the side stream.
+    const hipError_t side_done = side ? hipEventRecord(c->cand_ev[1], c->cand_stream) : hipSuccess;
+    const int rc = [&]() -> int {
+        if (MODE == MODE_INGEST && wave_tiles && a.cseg) {  // fold the sketch tuples (Count-Min scatter sink)
+            const uint32_t set_mask = (c->cfg.key_sets >> 1) & 3u;
+            const uint32_t nlog = CMS_NPART * (set_mask == 3u ? 2u : 1u);
+            hipLaunchKernelGGL(cms_agg_kernel, dim3(std::min<uint32_t>((uint32_t)c->num_cus, nlog)), dim3(AGG_BLOCK), 0, c->stream, a, set_mask, c->cms_par);  // persistent: one per CU
+            c->cms_par ^= 1u;
         }
+        // candidates mode: the launch boundary - theta of this boundary and the bits the NEXT launch tests its addresses against
+        // (behind every kernel of the launch that adds to a sketch: hot-address flushes, the atomic paths, cms_agg_kernel)
+        if (MODE == MODE_INGEST && c->cand_state) {
+            HIPCHK(c, hipMemsetAsync(c->cand_state, 0, 2 * sizeof(CandState), c->stream));
+            const dim3 gs(CAND_SCAN_BLOCKS, 2), gb(256, 2);
+            hipLaunchKernelGGL(cand_scan_kernel, gs, dim3(256), 0, c->stream, c->ks_src, c->ks_dst, 1u << c->ks_log2, (const unsigned long long*)c->cms_src,
+                               (const unsigned long long*)c->cms_dst, c->cfg.cms_depth, c->cfg.cms_width_log2, c->cfg.cms_seed, c->cand_state, c->cand_chunkmax);
+            hipLaunchKernelGGL(cand_bits_kernel, gb, dim3(256), 0, c->stream, (const KeySlot*)c->ks_src, (const KeySlot*)c->ks_dst, (const unsigned long long*)c->cms_src,
+                               (const unsigned long long*)c->cms_dst, c->cfg.cms_depth, c->cfg.cms_width_log2, c->cfg.topk_track, std::max(c->ks_log2, 8u) - 2u, c->cand_state,
+                               c->cand_bits[0], c->cand_bits[1]);
+        }
+        // fold the (SrcAddr,DstPort,Proto) tuples: one workgroup per table region, plain loads and stores - behind every
+        // dispatch of this launch that updates the wide table with atomics (wagg.cuh)
+        if (MODE == MODE_INGEST && wave_tiles && a.wseg) {
+            if (c->wlog_now) {  // log mode: the tuples stay where they are (the chunk is taken over behind the launch: wlog_record)
+                // (the time base and the tuples' bucket range, three words: Counters::tb_base, wtb_min, wtb_nmax)
+                HIPCHK(c, hipMemcpyAsync(c->wseg_counts + c->wseg_counts_cap, &c->d_ctr->tb_base, 3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+            } else {
+                hipLaunchKernelGGL(wagg_kernel, dim3(1u << a.wplog2), dim3(WAGG_BLOCK), 0, c->stream, a, (const uint32_t*)nullptr, 0u);
+            }
+        }
+        return FA_OK;
+    }();
+    // the join: everything behind this launch sees the aggregated table (on the host if the stream cannot wait for it)
+    if (side && (side_done != hipSuccess || hipStreamWaitEvent(c->stream, c->cand_ev[1], 0) != hipSuccess)) {
+        (void)hipStreamSynchronize(c->cand_stream);
+        if (rc == FA_OK) return fail(c, FA_ERR_HIP, "joining the side stream failed");
     }
-    if (side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->cand_ev[1], 0));  // (everything behind this launch sees the aggregated table)
+    if (rc) return rc;
     if (ev) (void)hipEventRecord(ev->e2, c->stream);
     HIPCHK(c, hipGetLastError());
     return FA_OK;
@@ -505,7 +509,7 @@ static int ingest_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
     }
     // small batches are not worth a second pass: they go straight to the device-wide table
     const bool scatter = (c->cfg.key_sets & FA_KEYS_AS_PAIR) && (c->sink_mode == 2 || (c->sink_mode == 0 && n >= (1u << 15)));
-    c->use_wave_tiles = scatter && c->tile_mode != 2;
+    c->use_wave_tiles = scatter;
     // tuple format of this launch (table.cuh): compact 8-byte tuples on the wave-tile kernel with 256 partitions,
     // unless recent launches showed that this stream's records do not fit them
     c->use_t8 = c->use_wave_tiles && c->plog2 == 8 && c->t8_mode != 2 && (c->t8_mode == 1 || c->stats.batches >= c->t8_wide_until);
@@ -560,7 +564,6 @@ static int ingest_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
         const uint32_t waves = (uint32_t)(big_wg ? WBLOCK_CMS : WBLOCK) / 64u;
         const uint32_t wgs = (wtiles + waves - 1) / waves;
         grid = (int)std::max(1u, std::min<uint32_t>(wgs, (uint32_t)c->num_cus * (uint32_t)(big_wg ? 1 : WT_WG_PER_CU)));
-        if (a.tile_recs > (uint32_t)WT_RECS) c->use_t8 = false;
     }
     if (scatter) {
         rc = ensure_segments(c, n, (uint32_t)grid, c->use_t8, a);

@@ -8,7 +8,7 @@
 //   -> everything else leaves the workgroup as a tuple (compact 8 bytes / wide 16, table.cuh) in the workgroup's PRIVATE
 //      segment of the key's partition, whole store units at a time (LDS bins; positions from LDS counters - no global
 //      atomics: MI355X retires only ~24 G memory-side atomics/s);
-//   (tile_kernel = the 256-thread workgroup-tile form: decode path, direct sink, FA_TILE=wg)
+//   (tile_kernel = the 256-thread workgroup-tile form: decode path, direct sink)
 //   agg8_kernel / agg_kernel: one 1024-thread workgroup per key partition streams the partition's segments back,
 //      aggregates them in an LDS hash table (two packed 64-bit LDS atomics per tuple) and adds each group to the
 //      device-wide table once - agg8_kernel with plain loads and stores: the partition owns the key's table region.

@@ -67,11 +67,7 @@ constexpr int AGG_BLOCK = 1024;    // agg_kernel: 16 waves share one LDS table
 #ifndef FA_AGG_SLOTS
 #define FA_AGG_SLOTS 4096
 #endif
-#ifndef FA_AGG_SPLIT
-#define FA_AGG_SPLIT 1
-#endif
 constexpr int AGG_SLOTS = FA_AGG_SLOTS;  // 32 B of LDS per slot (4096: 128 KiB)
-constexpr int AGG_SPLIT = FA_AGG_SPLIT;  // workgroups per key partition (each with its own LDS table)
 constexpr int AGG_PROBES = 16;
 constexpr uint32_t AGG_MAX_BATCH = 1u << 24;  // wide tuples: count <= 2^24 per slot keeps the packed LDS sums exact (Packets < 2^15: 15 + 24 + 25 bits)
 constexpr uint32_t AGG8_MAX_BATCH = (1u << 25) - 1u;  // compact tuples (Packets < 2^9): 25 bits of count
@@ -935,7 +931,6 @@ __device__ __forceinline__ void wide_sink_wave(const KArgs& a, LdsMinutes& lm, c
                 if (!sp) wspill_park(t, k, r.bytes, r.packets, 1);
             }
         }
-#ifndef FA_NO_WRANGE  // (A/B of the bookkeeping's cost only: reads of log chunks need it)
         if (wpart_cnt) {
             // the bucket range of the tuples this workgroup leaves in the segments (two LDS words behind the region counts): a close
             // compares its range with the chunk's and knows when nothing of a chunk is left - without a scan of the chunk.  A tile's
@@ -961,7 +956,6 @@ __device__ __forceinline__ void wide_sink_wave(const KArgs& a, LdsMinutes& lm, c
                 }
             }
         }
-#endif
         if (__builtin_amdgcn_ballot_w64(sp != nullptr) != 0ull) quad_atomic_update_at<4>((uint64_t)sp, r.bytes, r.packets, 1);
     }
     if (ks_on<KEYSETS>(a, FA_KEYS_PORT_HIST)) {

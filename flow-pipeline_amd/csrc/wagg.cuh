@@ -28,9 +28,6 @@ namespace fa {
 #ifndef FA_WAGG_U
 #define FA_WAGG_U 2
 #endif
-#ifndef FA_WAGG_EARLY
-#define FA_WAGG_EARLY 1
-#endif
 // Two workgroups per CU (512 regions, 66 KiB of LDS each): a chunk's LDS phases (staging, dedup) and its table phase
 // (random 64-byte lines: latency) alternate, and with one workgroup per CU nothing was in flight during the former.
 constexpr int WAGG_BLOCK = FA_WAGG_BLOCK;
@@ -166,10 +163,8 @@ __global__ __launch_bounds__(WAGG_BLOCK) void wagg_kernel(KArgs a, const uint32_
 #pragma unroll
         for (int u = 0; u < WAGG_U; u++) {
             hs[u] = &t.tab[h[u] & t.mask];
-#if FA_WAGG_EARLY
             k01[u] = *reinterpret_cast<const ulonglong2*>(&hs[u]->w[0]);
             k23[u] = *reinterpret_cast<const ulonglong2*>(&hs[u]->w[2]);
-#endif
         }
         if (base + WAGG_CHUNK < total) fetch(base + WAGG_CHUNK);
         __syncthreads();
@@ -210,10 +205,6 @@ __global__ __launch_bounds__(WAGG_BLOCK) void wagg_kernel(KArgs a, const uint32_
 #pragma unroll
         for (int u = 0; u < WAGG_U; u++) {
             const uint32_t e = (uint32_t)u * WAGG_BLOCK + tid;
-#if !FA_WAGG_EARLY
-            k01[u] = *reinterpret_cast<const ulonglong2*>(&hs[u]->w[0]);
-            k23[u] = *reinterpret_cast<const ulonglong2*>(&hs[u]->w[2]);
-#endif
             sb[u] = L.accb[e];
             sp[u] = L.accp[e];
             sc[u] = L.accc[e];

@@ -354,15 +354,11 @@ def test_decode_noncanonical_records(gpu_lib, fa, po):
     assert_decode_equal(got, want, wstatus)
 
 
-@pytest.mark.parametrize("tile", ["wave", "wg", ""])
-def test_tile_kernel_variants_agree_with_oracle(gpu_lib, fa, po, monkeypatch, tile):
-    """Both ingest kernels (wave-private tiles + LDS tuple bins: the default / 256-thread workgroup tiles) over
-    several batches incl. escapes, hot keys and a record size that shrinks the tiles."""
-    if tile:
-        monkeypatch.setenv("FA_TILE", tile)
-    else:
-        monkeypatch.delenv("FA_TILE", raising=False)
-    n = 400000
+# (the id is the one the case had while a parameter could force the ingest kernel: the case keeps its name)
+@pytest.mark.parametrize("n", [400000], ids=[""])
+def test_tile_kernel_variants_agree_with_oracle(gpu_lib, fa, po, n):
+    """The scatter sink's ingest kernel (wave-private tiles + LDS tuple bins) over several batches incl. escapes,
+    hot keys and a record size that shrinks the tiles."""
     gp = po.gen_params(mode=1, framed=1, seed=31, n_total=n, span_secs=1500)
     buf, off = po.gen_records(gp, 0, n)
     recs = _custom_records(fa, po, 40000, 32)
@@ -375,7 +371,7 @@ def test_tile_kernel_variants_agree_with_oracle(gpu_lib, fa, po, monkeypatch, ti
             ref.ingest(b, o, 1)
             agg.sync()
         st = agg.stats()
-        assert st["wave_tile_launches"] == (0 if tile == "wg" else 2)
+        assert st["wave_tile_launches"] == 2
         assert agg.read_window().tobytes() == ref.rows().tobytes()
     ref = po.Rollup(300)
     with fa.FlowAgg(framed=False) as agg:
@@ -498,27 +494,23 @@ def _large_batch_checksum_run(fa, po, mode, n=4_000_000):
         return agg.stats()
 
 
-@pytest.mark.parametrize("mode,tile", [(1, ""), (2, ""), (0, ""), (1, "wg")])
-def test_large_device_batches_checksum_equals_oracle(gpu_lib, fa, po, monkeypatch, mode, tile):
+# (ids: as for test_tile_kernel_variants_agree_with_oracle)
+@pytest.mark.parametrize("mode", [1, 2, 0], ids=["1-", "2-", "0-"])
+def test_large_device_batches_checksum_equals_oracle(gpu_lib, fa, po, mode):
     """Bench-scale batches (full grids, every LDS bin cycling hundreds of times).  Small batches do not exercise
     the cross-wave bin hand-over enough to catch ordering mistakes there."""
-    if tile:
-        monkeypatch.setenv("FA_TILE", tile)
     st = _large_batch_checksum_run(fa, po, mode)
-    assert st["wave_tile_launches"] == (0 if tile == "wg" else 3)
+    assert st["wave_tile_launches"] == 3
 
 
-@pytest.mark.parametrize("tile,cap", [("", 40), ("", 48), ("wg", 40)])
-def test_segment_overflow_fallbacks_stay_exact(gpu_lib, fa, po, monkeypatch, tile, cap):
-    """Segments far too small for the batch (FA_SEG_CAP, a test knob): full bins that find the front part full,
-    single tuples that find the back part full and the workgroup kernel's plain overflow all fall back to the
-    device-wide table - slower, but the rows must not change."""
+@pytest.mark.parametrize("cap", [40, 48], ids=["-40", "-48"])  # (ids: as above)
+def test_segment_overflow_fallbacks_stay_exact(gpu_lib, fa, po, monkeypatch, cap):
+    """Segments far too small for the batch (FA_SEG_CAP, a test knob): full bins that find the front part full
+    and single tuples that find the back part full fall back to the device-wide table - slower, but the rows
+    must not change."""
     monkeypatch.setenv("FA_SEG_CAP", str(cap))
-    if tile:
-        monkeypatch.setenv("FA_TILE", tile)
     st = _large_batch_checksum_run(fa, po, 1)
-    if not tile:  # (the workgroup kernel's 1536 segments per partition hold ~10 tuples each here: rarely above 40)
-        assert st["records_direct"] > (500_000 if cap == 40 else 10_000), st  # the fallbacks really ran (of 12 M records)
+    assert st["records_direct"] > (500_000 if cap == 40 else 10_000), st  # the fallbacks really ran (of 12 M records)
 
 
 def test_config3_shape_sketches_and_topk_at_scale(gpu_lib, fa, po):

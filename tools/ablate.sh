@@ -5,7 +5,7 @@
 #        16 no parse, 32 no tuple stores, 64/128/256 agg kernel: loads only / no flush / no probing path,
 #        512 DMA without nt, 1024 phase timing (workgroup kernel), 2048/4096 nt / system-scope single tuple stores,
 #        8192 no per-lane offset loads, 16384 synthetic aligned tiles, 32768 lanes own nothing, 131072 no frame check
-#        (csrc/sinks.cuh DBG_*); FA_SINK=direct forces the device-wide-table sink, FA_TILE=wg the workgroup-tile kernel
+#        (csrc/sinks.cuh DBG_*); FA_SINK=direct forces the device-wide-table sink (and with it the workgroup-tile kernel)
 REC=${1:-100000000}
 MODE=${2:-aspairs}
 for f in 0 2 4 32 1 17 d0 d2; do
