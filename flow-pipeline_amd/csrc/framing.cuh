@@ -39,6 +39,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wire.cuh"  // (FA_HD: the walk and the position arithmetic below also compile for the host, tests/host_positions.hip)
+
 namespace fa {
 
 constexpr uint32_t FS_BLOCK = 16384;
@@ -55,6 +57,15 @@ constexpr uint32_t FS_STAGE = 1024; // bytes of a block the guess stages in LDS 
 constexpr uint32_t FS_SLACK = 16;   // bytes staged behind a block: the prefix of a frame that starts on its last byte
 constexpr uint32_t FS_REWALK_WGS = 64;   // fs_rewalk_kernel's grid: its lanes share the list
 static_assert(FS_NSUB == 64, "fs_emit_kernel: one lane per sub-block");
+
+// Position arithmetic at the top of the offset range: a stream may end anywhere below 2^32 - 1, so its last block can end above
+// 2^32 - FS_BLOCK, where begin + FS_BLOCK and the stage's slack behind it wrap past 2^32.
+// The end of sub-block j of the block [begin, end) (end - begin <= FS_BLOCK): never past end, written as a difference.
+FA_HD uint32_t fs_sub_end(uint32_t begin, uint32_t j, uint32_t end) {
+    return end - begin > (j + 1u) * FS_SUB ? begin + (j + 1u) * FS_SUB : end;
+}
+// byte lo + i lies inside the stream [0, len) (the sum in 64 bits)
+FA_HD bool fs_in_stream(uint32_t lo, uint32_t i, uint32_t len) { return (uint64_t)lo + i < (uint64_t)len; }
 
 // bytes [lo, lo + n) of the stream, staged in LDS (what lies behind is read as the last staged byte: the callers keep away)
 struct FsLds {
@@ -74,7 +85,7 @@ __device__ __forceinline__ void fs_stage(const uint8_t* buf, uint32_t len, uint3
 #pragma unroll
     for (uint32_t t = 0; t < TRIPS; t++) {
         const uint32_t i = lane * 16u + t * 1024u;
-        r[t] = (i < N && lo + i < len) ? *reinterpret_cast<const uint4*>(buf + lo + i) : make_uint4(0, 0, 0, 0);
+        r[t] = (i < N && fs_in_stream(lo, i, len)) ? *reinterpret_cast<const uint4*>(buf + lo + i) : make_uint4(0, 0, 0, 0);
     }
 #pragma unroll
     for (uint32_t t = 0; t < TRIPS; t++) {
@@ -89,7 +100,7 @@ __device__ __forceinline__ void fs_stage(const uint8_t* buf, uint32_t len, uint3
 // the frame that starts at byte p of buf[0, len): the offset of the next frame, or FS_ERR (prefix longer than 10 bytes, prefix
 // or payload beyond len) - the rules of the host split (flowagg.hip, frame_split_host).  *payload: where its payload begins.
 template <class Bytes>
-__device__ __forceinline__ uint32_t fs_next(const Bytes& buf, uint32_t p, uint32_t len, uint32_t* payload = nullptr) {
+FA_HD uint32_t fs_next(const Bytes& buf, uint32_t p, uint32_t len, uint32_t* payload = nullptr) {
     unsigned long long v = 0;
     uint32_t q = p;
     for (int i = 0;; i++) {
@@ -266,7 +277,7 @@ __global__ __launch_bounds__(256) void fs_guess_kernel_t(const uint8_t* buf, uin
 // ent8[j] = where the first frame of sub-block j starts (offset inside the sub-block; only where bit j of *present is set),
 // stored four sub-blocks at a time.
 template <class Bytes>
-__device__ __forceinline__ void fs_walk_block(const Bytes& bytes, uint32_t len, uint32_t begin, uint32_t end, uint32_t from, uint32_t* cnt, uint8_t* err, uint32_t* exit_out,
+FA_HD void fs_walk_block(const Bytes& bytes, uint32_t len, uint32_t begin, uint32_t end, uint32_t from, uint32_t* cnt, uint8_t* err, uint32_t* exit_out,
                                               uint8_t* ent8, unsigned long long* present) {
     uint32_t* e32 = reinterpret_cast<uint32_t*>(ent8);
     uint32_t p = from, c = 0, sub = 0;  // sub: sub-blocks below it have been passed
@@ -403,7 +414,7 @@ __global__ __launch_bounds__(256) void fs_emit_kernel(const uint8_t* buf, uint32
         fs_stage<FS_BLOCK + FS_SLACK>(buf, len, begin, stage[wave], lane);
         const FsLds bytes{reinterpret_cast<const uint8_t*>(stage[wave]), begin, FS_BLOCK + FS_SLACK};
         const bool mine = (mask >> lane) & 1ull;
-        const uint32_t sub_end = min(begin + (lane + 1) * FS_SUB, end);
+        const uint32_t sub_end = fs_sub_end(begin, lane, end);
         const uint32_t p0 = begin + lane * FS_SUB + ent8[(size_t)b * FS_NSUB + lane];
         uint32_t c = 0;
         if (mine)

@@ -374,14 +374,16 @@ __device__ __forceinline__ uint32_t probe_tb_base(const KArgs& a) {
         if (ok) {
             // what proto.Marshal emits (mocker.go:97): [Type 08 xx] then TimeReceived 10 <varint> - one or two
             // cache-resident windows instead of a walk over the whole record; anything else: the general parser
+            // (pos <= end throughout, and the tests are written as differences: at the top of the offset range pos + 2 or
+            // pos + 1 + vl would wrap past 2^32)
             uint64_t w = window64(src, pos);
-            if ((w & 0x80ffu) == 0x0008u) {
+            if ((w & 0x80ffu) == 0x0008u && end - pos >= 2u) {
                 pos += 2;
                 w = window64(src, pos);
             }
             uint32_t vl;
             uint64_t val;
-            if ((w & 0xffu) == 0x10u && varint6(w >> 8, vl, val) && pos + 1 + vl <= end) {
+            if ((w & 0xffu) == 0x10u && varint6(w >> 8, vl, val) && vl < end - pos) {
                 lo = time_bucket(a, (uint32_t)val);
             } else {
                 Rec r;

@@ -95,7 +95,10 @@ FA_HD void rec_clear(Rec& r) {
 }
 
 // ---- byte sources ---------------------------------------------------------
+// ABS: the source's positions are offsets into the caller's whole batch (up to 2^32 - 1), where a cursor step can wrap past 2^32
+// (see fa_lands).  LDS positions are below 2^18: their walks keep the plain 32-bit tests.
 struct LdsSrc {
+    static constexpr bool ABS = false;
     const uint32_t* base;  // LDS, dword aligned
     FA_HD uint32_t dw(uint32_t i) const { return base[i]; }
 };
@@ -103,6 +106,7 @@ struct LdsSrc {
 // (tile base folded in once per record) and a window load is "and -4, ds_read2, ds_read" - the add of the tile's base that
 // every field step of LdsSrc pays is gone (one VALU instruction per step: 14 of a mocker-shaped record's ~420, 33 of GoFlow's).
 struct LdsAbsSrc {
+    static constexpr bool ABS = false;
     FA_HD uint32_t dw(uint32_t i) const {
 #if defined(__HIP_DEVICE_COMPILE__)
         typedef const __attribute__((address_space(3))) uint32_t* lds_p;
@@ -113,9 +117,19 @@ struct LdsAbsSrc {
     }
 };
 struct GlobalSrc {
+    static constexpr bool ABS = true;
     const uint32_t* base;  // global, dword aligned
     FA_HD uint32_t dw(uint32_t i) const { return base[i]; }
 };
+
+// A cursor at `from` <= end that steps to `to` = from + step (step < 2^32) lands inside the record: to <= end.  For ABS sources
+// the sum may have wrapped past 2^32 (a record in the last bytes below 2^32, or the walks' "no stop byte" step of 2^29 from a
+// position >= 0xE0000000) and would then move the cursor BACKWARDS: to < from is that wrap.
+template <class Src>
+FA_HD bool fa_lands(uint32_t from, uint32_t to, uint32_t end) {
+    if (Src::ABS) return to >= from && to <= end;
+    return to <= end;
+}
 
 // 8 bytes starting at byte offset pos (little endian), from aligned dwords.
 template <class Src>
@@ -223,7 +237,14 @@ FA_HD bool parse_fast(const Src& s, uint32_t pos, uint32_t end, Rec& r) {
                 }
             }
         }
-        pos = npos + (sz & (0u - isl));
+        const uint32_t nx = npos + (sz & (0u - isl));
+        if (Src::ABS) {  // a step that wraps past 2^32 (< 2^20 + 17 bytes: at most once) lands beyond end: not sure, the walk ends
+            const bool wrap = nx < pos;
+            doubt |= wrap ? 1u : 0u;
+            pos = wrap ? end : nx;
+        } else {
+            pos = nx;
+        }
     }
     return doubt == 0 && pos == end;
 }
@@ -259,8 +280,8 @@ FA_HD void canon_short(const Src& s, Cursor& c, uint32_t end, uint32_t& out) {
     if (FA_ANY(m)) {
         const uint32_t v = fa_alignbyte(c.y, c.x, TL);  // value bytes 0..3
         const uint32_t sb = fa_ffbl(~v & 0x80808080u);
-        const uint32_t pn = c.pos + (sb >> 3) + (TL + 1u);  // sb = 0xffffffff (no stop) -> far beyond end
-        const bool ok = m && pn <= end;
+        const uint32_t pn = c.pos + (sb >> 3) + (TL + 1u);  // sb = 0xffffffff (no stop) -> far beyond end (fa_lands: also where the sum wraps)
+        const bool ok = m && fa_lands<Src>(c.pos, pn, end);
         if (WANT) {
             const uint32_t val = varint28(v, sb);
             out = ok ? val : out;
@@ -281,7 +302,7 @@ FA_HD void canon_long(const Src& s, Cursor& c, uint32_t end, uint64_t& out) {
         const uint32_t s1 = fa_ffbl(~c.y & 0x80808080u) | 32u;  // stays 0xffffffff when there is no stop
         const uint32_t sb = s0 < s1 ? s0 : s1;                  // window bit index of the stop byte's bit 7
         const uint32_t pn = c.pos + (sb >> 3) + 1u;
-        const bool ok = m && pn <= end;
+        const bool ok = m && fa_lands<Src>(c.pos, pn, end);
         if (WANT) {
             const uint32_t lo = fa_alignbyte(c.y, c.x, TL);  // value bytes 0..3
             const uint32_t hi = c.y >> (8u * TL);            // value bytes 4..
@@ -304,7 +325,7 @@ FA_HD void canon_addr(const Src& s, Cursor& c, uint32_t end, uint32_t out[4]) {
     if (FA_ANY(m)) {
         const uint32_t len = (c.x >> 8) & 0xffu;
         const uint32_t pn = c.pos + 2u + len;
-        const bool ok = m && len <= 16u && pn <= end;
+        const bool ok = m && len <= 16u && fa_lands<Src>(c.pos, pn, end);
         if (WANT) {
             uint32_t a16[4];
             load_fixed16(s, c.pos + 2u, len > 16u ? 16u : len, a16);
@@ -349,7 +370,7 @@ FA_HD void canon_skip(const Src& s, Cursor& c, uint32_t end, bool go) {
     body = ((wt == 2u) & (lb < 0x80u)) ? 1u + lb : body;
     body = wt == 0u ? vlen : body;
     const uint32_t pn = c.pos + TL + body;
-    const bool ok = go && pn <= end;
+    const bool ok = go && fa_lands<Src>(c.pos, pn, end);
     c.pos = ok ? pn : c.pos;
     cur_load(s, c);
 }
@@ -480,8 +501,8 @@ FA_HD void tw_short(const Src& s, Cursor& c, uint32_t end, uint32_t& out) {
     const bool m = (c.x & (TL == 1 ? 0xffu : 0xffffu)) == TAG;
     const uint32_t v = fa_alignbyte(c.y, c.x, TL);  // value bytes 0..3
     const uint32_t sb = fa_ffbl(~v & 0x80808080u);
-    const uint32_t pn = c.pos + (sb >> 3) + (TL + 1u);  // sb = 0xffffffff (no stop) -> far beyond end
-    const bool ok = m && pn <= end;
+    const uint32_t pn = c.pos + (sb >> 3) + (TL + 1u);  // sb = 0xffffffff (no stop) -> far beyond end (fa_lands: also where the sum wraps)
+    const bool ok = m && fa_lands<Src>(c.pos, pn, end);
     if (WANT) {
         const uint32_t val = varint28b(v, sb);
         out = ok ? val : out;
@@ -498,7 +519,7 @@ FA_HD void tw_skip(const Src& s, Cursor& c, uint32_t end) {
     const uint32_t s1 = fa_ffbl(~c.y & 0x80808080u) | 32u;  // stays 0xffffffff when there is no stop
     const uint32_t sb = s0 < s1 ? s0 : s1;
     const uint32_t pn = c.pos + (sb >> 3) + 1u;
-    const bool ok = m && pn <= end;
+    const bool ok = m && fa_lands<Src>(c.pos, pn, end);
     c.pos = ok ? pn : c.pos;
     if (!LAST) cur_load(s, c);
 }
@@ -518,7 +539,7 @@ FA_HD void tw_skip7(const Src& s, Cursor& c, uint32_t end) {
     const uint32_t s01 = s0 < s1 ? s0 : s1;
     const uint32_t sb = s01 < s2 ? s01 : s2;
     const uint32_t pn = c.pos + (sb >> 3) + 1u;
-    const bool ok = m && pn <= end;
+    const bool ok = m && fa_lands<Src>(c.pos, pn, end);
     c.pos = ok ? pn : c.pos;
     cur_load(s, c);
 }
@@ -530,7 +551,7 @@ FA_HD void tw_time5(const Src& s, Cursor& c, uint32_t end, uint64_t& out) {
     const bool m = TL == 1 ? ((c.x & 0x808080ffu) == (0x80808000u | TAG) && (c.y & 0x00008080u) == 0x00000080u)
                            : ((c.x & 0x8080ffffu) == (0x80800000u | TAG) && (c.y & 0x00808080u) == 0x00008080u);
     const uint32_t pn = c.pos + TL + 5u;
-    const bool ok = m && pn <= end;
+    const bool ok = m && fa_lands<Src>(c.pos, pn, end);
     if (WANT) {
         const uint32_t v = fa_alignbyte(c.y, c.x, TL) & 0x7f7f7f7fu;  // value bytes 0..3, payload bits
         const uint32_t t = v - ((v & 0x7f007f00u) >> 1);
@@ -547,7 +568,7 @@ FA_HD void tw_addr(const Src& s, Cursor& c, uint32_t end, uint32_t out[4]) {
     const bool m = (c.x & 0xffu) == TAG;
     const uint32_t len = fa_ubfe(c.x, 8u, 8u);
     const uint32_t pn = c.pos + 2u + len;
-    const bool ok = m && len <= 16u && pn <= end;
+    const bool ok = m && len <= 16u && fa_lands<Src>(c.pos, pn, end);
     if (WANT) {
         uint32_t a16[4];
         load_fixed16(s, c.pos + 2u, len > 16u ? 16u : len, a16);
@@ -706,7 +727,9 @@ FA_HD uint32_t seq_learn(const Src& s, uint32_t pos, uint32_t end, uint32_t* ste
         for (uint32_t k = 0; k < n; k++)
             if ((steps[k] & 0xffffu) == tag) return 0u;
         steps[n++] = seq_step_of(tag);
-        pos += 1u + two + body;
+        const uint32_t nx = pos + 1u + two + body;
+        if (Src::ABS && nx < pos) return 0u;  // (wrapped past 2^32: beyond end)
+        pos = nx;
     }
     return pos == end ? n : 0u;
 }
@@ -716,8 +739,8 @@ FA_HD bool sq_short(const Src& s, Cursor& c, uint32_t end, uint32_t tag, uint32_
     const bool m = (c.x & (tl == 1u ? 0xffu : 0xffffu)) == tag;
     const uint32_t v = fa_alignbyte(c.y, c.x, tl);  // value bytes 0..3
     const uint32_t sb = fa_ffbl(~v & 0x80808080u);
-    const uint32_t pn = c.pos + (sb >> 3) + (tl + 1u);  // sb = 0xffffffff (no stop) -> far beyond end
-    const bool ok = m && pn <= end;
+    const uint32_t pn = c.pos + (sb >> 3) + (tl + 1u);  // sb = 0xffffffff (no stop) -> far beyond end (fa_lands: also where the sum wraps)
+    const bool ok = m && fa_lands<Src>(c.pos, pn, end);
     val = varint28(v, sb);
     c.pos = ok ? pn : c.pos;
     cur_load(s, c);
@@ -730,7 +753,7 @@ FA_HD bool sq_long(const Src& s, Cursor& c, uint32_t end, uint32_t tag, uint32_t
     const uint32_t s1 = fa_ffbl(~c.y & 0x80808080u) | 32u;  // stays 0xffffffff when there is no stop
     const uint32_t sb = s0 < s1 ? s0 : s1;
     const uint32_t pn = c.pos + (sb >> 3) + 1u;
-    const bool ok = m && pn <= end;
+    const bool ok = m && fa_lands<Src>(c.pos, pn, end);
     const uint32_t lo = fa_alignbyte(c.y, c.x, tl);
     const uint32_t hi = c.y >> (8u * tl);
     const uint32_t sv = (sb - 8u * tl) & 63u;
@@ -747,7 +770,7 @@ FA_HD bool sq_addr(const Src& s, Cursor& c, uint32_t end, uint32_t tag, uint32_t
     const bool m = (c.x & 0xffu) == tag;
     const uint32_t len = (c.x >> 8) & 0xffu;
     const uint32_t pn = c.pos + 2u + len;
-    const bool ok = m && len <= 16u && pn <= end;
+    const bool ok = m && len <= 16u && fa_lands<Src>(c.pos, pn, end);
     load_fixed16(s, c.pos + 2u, len > 16u ? 16u : len, a16);
     c.pos = ok ? pn : c.pos;
     cur_load(s, c);

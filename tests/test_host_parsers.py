@@ -112,3 +112,48 @@ def test_time_bucket_reciprocal_is_exact():
             assert np.array_equal(got, t // np.uint64(g)), g
         t = rng.integers(0, 2**32, 20000, dtype=np.uint64)
         assert np.array_equal(np.floor(t.astype(np.float64) * c).astype(np.uint64), t // np.uint64(g)), g
+
+
+def build_host_positions(po):
+    """tests/host_positions.hip -> its executable (also run by tests/test_positions_4gib_gpu.py before any byte reaches the GPU)."""
+    po.build()
+    out = os.path.join(ROOT, "tests", "_build")
+    os.makedirs(out, exist_ok=True)
+    exe = os.path.join(out, "host_positions")
+    src = os.path.join(ROOT, "tests", "host_positions.hip")
+    deps = [src, os.path.join(ROOT, "flow-pipeline_amd", "csrc", "wire.cuh"), os.path.join(ROOT, "oracle", "liboracle.so")]
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
+        subprocess.check_call([
+            "/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wno-unused-value", "-o", exe, src,
+            "-L" + os.path.join(ROOT, "oracle"), "-loracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle")])
+    return exe
+
+
+def test_parsers_are_position_invariant_up_to_4gib(po):
+    """Every tier that reads through a Src (parse_canon lean / FULL, the template walks, parse_seq, parse_fast, seq_learn,
+    frame_fast + window64) gives the verdict and the 15 columns it gives at base 0 when the record sits across 2^31, in the last
+    MiB below 2^32 or ends at 2^32 - 1, and reads a bounded number of dwords - generator records of every mode, mutations,
+    truncations and records built to wrap (truncated LEN claims up to 2^20 - 1, varints without a stop byte).  A cursor that
+    wraps past 2^32 ends the harness with status 3 at its first read past the cap (tests/host_positions.hip)."""
+    exe = build_host_positions(po)
+    res = subprocess.run([exe, "3000"], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-4000:] + res.stderr
+    lines = {l.split("records=")[0].strip(): dict(kv.split("=") for kv in l.split() if "=" in kv)
+             for l in res.stdout.splitlines() if "records=" in l}
+    assert int(lines["generator (6 modes)"]["fast_sure"]) > 0 and int(lines["built to wrap"]["placements"]) > 20000, res.stdout
+
+
+def test_framing_arithmetic_at_the_top_of_the_offset_range():
+    """framing.cuh compiled for the host: for every stream length in (2^32 - 16384 - 300, 2^32 - 2] the emit pass's sub-blocks
+    tile the last blocks exactly and the stage never admits a byte at or past len; a chain of frames ending there is walked and
+    emitted exactly as at base 0 (tests/host_framing_positions.hip)."""
+    out = os.path.join(ROOT, "tests", "_build")
+    os.makedirs(out, exist_ok=True)
+    exe = os.path.join(out, "host_framing_positions")
+    src = os.path.join(ROOT, "tests", "host_framing_positions.hip")
+    csrc = os.path.join(ROOT, "flow-pipeline_amd", "csrc")
+    deps = [src, os.path.join(csrc, "framing.cuh"), os.path.join(csrc, "wire.cuh")]
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-Wno-unused-value", "-o", exe, src])
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-4000:] + res.stderr
