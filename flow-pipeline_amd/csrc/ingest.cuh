@@ -444,8 +444,10 @@ __global__ __launch_bounds__(BLOCK) void tile_kernel(KArgs a) {
     constexpr uint32_t COLS = MODE == MODE_DECODE ? (uint32_t)COL_ALL : cols_for_keysets<KEYSETS>();
     __shared__ __attribute__((aligned(16))) uint32_t tile[TILE_STRIDE / 4];
     __shared__ LdsTable<LDS_SLOTS> lt;
-    __shared__ uint32_t ctr_scratch[NPART_MAX];  // block_counters_add (5 words; the LDS footprint stays the one measured at 6 workgroups per CU)
+    __shared__ uint32_t ctr_scratch[NPART_MAX];  // block_counters_add (5 words; the LDS footprint stays within the one measured at 6 workgroups per CU:
+                                                 // 240 bytes below it since the multi-pass loop's __syncthreads_count, 256 bytes, gave way to run_len)
     __shared__ LdsMinutes lm;                    // per-minute series pre-aggregation (KS_ALL variant only)
+    __shared__ uint32_t run_len[BLOCK / 64];     // multi-pass tiles: every wave's leading run of records that fit the pass
 
     const uint32_t tid = threadIdx.x;
     if (MODE == MODE_INGEST && (KEYSETS & FA_KEYS_AS_PAIR)) lds_table_clear(lt);
@@ -521,7 +523,20 @@ __global__ __launch_bounds__(BLOCK) void tile_kernel(KArgs a) {
                     mine = p1 <= climit && p1 >= p0 && p0 >= cbase && p1 <= cur.hi;
                 }
                 dma_wait_all();
-                const int nfit = __syncthreads_count(mine);  // offsets are monotone: a prefix fits
+                // The pass takes the LEADING RUN of records that fit: it ends in front of the first lane that is not `mine`, and
+                // the lanes behind that one wait for a later pass.  With monotone offsets the records that fit are a prefix and
+                // the run is all of them; the caller's offsets need not be monotone, and a record with a broken bound in the
+                // middle must neither be skipped nor make the next pass start short of the lanes parsed in this one.
+                const unsigned long long fitm = __builtin_amdgcn_ballot_w64(mine);
+                if ((tid & 63u) == 0u) run_len[tid >> 6] = fitm == ~0ull ? 64u : (uint32_t)__builtin_ctzll(~fitm);
+                __syncthreads();
+                uint32_t nfit = 0;
+#pragma unroll
+                for (uint32_t w = 0; w < (uint32_t)BLOCK / 64u; w++) {
+                    const uint32_t f = run_len[w];
+                    if (nfit == 64u * w) nfit += f;
+                }
+                mine = mine && tid < nfit;
                 if (nfit == 0) {
                     // one record larger than the LDS buffer (or broken offsets): generic path
                     if (tid == 0) {

@@ -13,6 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from device_columns import fetch_columns
+
 pytestmark = pytest.mark.gpu
 
 TOP = 0xFFFFFFFF          # the largest len of the offsets path
@@ -268,28 +270,13 @@ def test_malformed_records_in_the_last_mib(gpu_lib, fa, po, big):
     with fa.FlowAgg(framed=True, max_batch_records=k) as agg:
         cols = agg.decode_device(big["d_buf"].data_ptr(), TOP, d_off.data_ptr() + 4 * (n - k), k)
         agg.sync()
-        got = _fetch_columns(cols, k)
+        got = fetch_columns(cols, k)
     host = big["d_buf"][int(top[0]):TOP].cpu().numpy()
     wrows, wstatus = po.decode_batch(host, top - top[0], framed=1)
     assert (got["status"] == wstatus).all() and int(wstatus.sum()) == 6
     for name in ("time_received", "time_flow_start", "sampling_rate", "bytes", "packets", "sequence_num", "src_as", "dst_as", "etype",
                  "proto", "src_port", "dst_port", "sampler_address", "src_addr", "dst_addr"):
         assert np.array_equal(got[name], wrows[name]), name
-
-
-def _fetch_columns(cols, k):
-    hip = C.CDLL("libamdhip64.so")
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    out = {}
-    for name, dt, w in (("time_received", np.uint64, 1), ("time_flow_start", np.uint64, 1), ("sampling_rate", np.uint64, 1),
-                        ("bytes", np.uint64, 1), ("packets", np.uint64, 1), ("sequence_num", np.uint32, 1), ("src_as", np.uint32, 1),
-                        ("dst_as", np.uint32, 1), ("etype", np.uint32, 1), ("proto", np.uint32, 1), ("src_port", np.uint32, 1),
-                        ("dst_port", np.uint32, 1), ("sampler_address", np.uint8, 16), ("src_addr", np.uint8, 16), ("dst_addr", np.uint8, 16),
-                        ("status", np.uint8, 1)):
-        a = np.zeros((k, w) if w > 1 else k, dtype=dt)
-        assert hip.hipMemcpy(a.ctypes.data, getattr(cols, name), a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
-        out[name] = a
-    return out
 
 
 @pytest.mark.parametrize("len_", [TOP - 1, 0xFFFFFF80], ids=["2^32-2", "2^32-128"])
