@@ -73,6 +73,18 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TalkersStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "used_src", "used_dst", "capacity_src", "capacity_dst", "records_folded", "records_absorbed", "grows",
+        "fold_launches", "fold_ns_total")]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["used"] = [d.pop("used_src"), d.pop("used_dst")]
+        d["capacity"] = [d.pop("capacity_src"), d.pop("capacity_dst")]
+        return d
+
+
 class MockParams(C.Structure):
     _fields_ = [
         ("mode", C.c_uint32), ("framed", C.c_uint32), ("seed", C.c_uint64),
@@ -113,6 +125,10 @@ ROW_APP_DTYPE = np.dtype([
 ROW_APP48_DTYPE = np.dtype([("src_addr", "u1", 16), ("dst_port", "<u4"), ("proto", "<u4"), ("bytes", "<u8"), ("packets", "<u8"), ("count", "<u8")])
 PORT_ROW_DTYPE = np.dtype([("port", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
 MINUTE_ROW_DTYPE = np.dtype([("minute", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
+TALKER_ROW_DTYPE = np.dtype([("key", "u1", 16), ("etype", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
+assert TALKER_ROW_DTYPE.itemsize == 40
+# geometry of the fold kernel (csrc/talkers.cuh): threads per workgroup, LDS cache entries per direction, workgroups per CU
+TALK_BLOCK, TALK_LDS_ENTRIES, TALK_WG_PER_CU = 512, 512, 2
 assert ROW5M_DTYPE.itemsize == 48 and FLOW_ROW_DTYPE.itemsize == 120
 assert ROW_APP_DTYPE.itemsize == 56 and PORT_ROW_DTYPE.itemsize == 24 and MINUTE_ROW_DTYPE.itemsize == 24
 ROW_DTYPES = [ROW5M_DTYPE, ROW_APP_DTYPE, PORT_ROW_DTYPE, PORT_ROW_DTYPE, MINUTE_ROW_DTYPE, TOPK_DTYPE, TOPK_DTYPE]  # by row kind
@@ -131,6 +147,7 @@ EXPORTS = [
     "fa_group_read_window", "fa_group_close_window", "fa_group_read_window_partitioned", "fa_group_close_window_partitioned",
     "fa_group_allreduce_sketches", "fa_group_topk", "fa_group_stats", "fa_read_window_app48", "fa_close_window_app48",
     "fa_reserve_ingest",
+    "fa_talkers_enable", "fa_talkers_fold_columns_device", "fa_top_talkers", "fa_merge_talkers", "fa_talkers_reset", "fa_talkers_stats",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -289,6 +306,12 @@ def lib():
     L.fa_group_allreduce_sketches.argtypes = [vp]
     L.fa_group_topk.argtypes = [vp, u32, sz, vp, sz, szp]
     L.fa_group_stats.argtypes = [vp, C.POINTER(Stats)]
+    L.fa_talkers_enable.argtypes = [vp, u32]
+    L.fa_talkers_fold_columns_device.argtypes = [vp, C.POINTER(Columns), sz]
+    L.fa_top_talkers.argtypes = [vp, C.c_int, sz, vp, sz, szp]
+    L.fa_merge_talkers.argtypes = [vp, C.c_int, vp, sz]
+    L.fa_talkers_reset.argtypes = [vp]
+    L.fa_talkers_stats.argtypes = [vp, C.POINTER(TalkersStats)]
     _LIB = L
     return L
 
@@ -624,6 +647,43 @@ class FlowAgg:
 
     def dashboard_reset(self):
         self._chk(self._L.fa_dashboard_reset(self._h))
+
+    # -- exact top talkers (opt-in second pass) ---------------------------------------------
+    def talkers_enable(self, capacity_log2=0):
+        """From now on every ingest also folds its records' SrcAddr / DstAddr into two exact tables, grouped as the
+        dashboards' top-talker panels group them (viz-ch.json:233,479)."""
+        self._chk(self._L.fa_talkers_enable(self._h, capacity_log2))
+
+    def fold_columns_device(self, cols: Columns, n: int):
+        """The same fold for columns that are already decoded (device pointers; src_addr, dst_addr, etype, bytes,
+        sampling_rate and status are read)."""
+        self._chk(self._L.fa_talkers_fold_columns_device(self._h, C.byref(cols), n))
+
+    def top_talkers(self, dst: int, k: int = 0) -> np.ndarray:
+        """GROUP BY the rendered SrcAddr (dst=0) / DstAddr (dst=1) ORDER BY sum(Bytes*SamplingRate) DESC, key bytes, etype:
+        every group (k=0) or the first k.  format_addr(row["key"], row["etype"]) is the string the panel shows."""
+        n = C.c_size_t()
+        cap = max(int(k), 1) if k else 1 << 12
+        while True:
+            out = np.zeros(cap, dtype=TALKER_ROW_DTYPE)
+            rc = self._L.fa_top_talkers(self._h, dst, int(k), out.ctypes.data, cap, C.byref(n))
+            if rc == -6:
+                cap = n.value
+                continue
+            self._chk(rc)
+            return out[:n.value].copy()
+
+    def merge_talkers(self, dst: int, rows: np.ndarray):
+        r = np.ascontiguousarray(rows, dtype=TALKER_ROW_DTYPE)
+        self._chk(self._L.fa_merge_talkers(self._h, dst, r.ctypes.data, len(r)))
+
+    def talkers_reset(self):
+        self._chk(self._L.fa_talkers_reset(self._h))
+
+    def talkers_stats(self) -> dict:
+        s = TalkersStats()
+        self._chk(self._L.fa_talkers_stats(self._h, C.byref(s)))
+        return s.as_dict()
 
     # -- sketches -------------------------------------------------------------------
     def cms_read(self, key_set) -> np.ndarray:

@@ -36,12 +36,18 @@ static int ensure_columns(fa_ctx* c, size_t n) {
     return FA_OK;
 }
 
+// len = bytes of the whole buffer the offsets point into (the bound the kernel clamps to); bytes = wire bytes of THESE n
+// records (exact or estimated: tile sizing only) - the sub-range convention of ingest_device_records.
+static int decode_device_records(fa_ctx* c, const void* d_buf, size_t len, size_t bytes, const void* d_off, size_t n, fa_columns* out);
 extern "C" int fa_decode_device(fa_ctx* c, const void* d_buf, size_t len, const void* d_off, size_t n,
                                 fa_columns* out) {
     FA_ON_DEVICE(c);
     FA_ON_DEVICE(c);
     if (!c || !out) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;
+    return decode_device_records(c, d_buf, len, len, d_off, n, out);
+}
+static int decode_device_records(fa_ctx* c, const void* d_buf, size_t len, size_t bytes, const void* d_off, size_t n, fa_columns* out) {
     if (!d_buf || !d_off || len >= (1ull << 32) || n > c->cfg.max_batch_records || ((uintptr_t)d_buf & 15))
         return fail(c, FA_ERR_ARG, "fa_decode_device: bad buffer");
     int rc = ensure_columns(c, std::max<size_t>(n, 1));
@@ -54,7 +60,7 @@ extern "C" int fa_decode_device(fa_ctx* c, const void* d_buf, size_t len, const 
         a.off = (const uint32_t*)d_off;
         a.n = (uint32_t)n;
         a.len = (uint32_t)len;
-        a.tile_recs = tile_recs_for(len, n);
+        a.tile_recs = tile_recs_for(bytes, n);
         if (c->dev_used == c->dev_pool.size()) {
             if (c->dev_pool.size() >= 1024) {  // bound the pool: fold what is pending
                 rc = settle(c);

@@ -232,6 +232,8 @@ struct fa_ctx {
     uint64_t wide_dead = 0;       // slots of the wide table whose rows a window close zeroed (wdrop_kernel): occupied, but no rows - purged by the next rebuild
     ulonglong2* port_hist = nullptr;  // [2][PORT_DENSE]
 
+    struct TalkState* talk = nullptr;  // exact top talkers (fa_talkers_enable; talkers_host.inc), nullptr = not enabled
+
     fa_stats_t stats{};
     uint64_t used_base = 0;  // groups created before the current counter epoch
     std::string err;
@@ -262,6 +264,9 @@ static int fail(fa_ctx* c, int code, const char* msg) {
     if (c) c->err = msg;
     return code;
 }
+// exact top talkers (talkers_host.inc): the second pass behind an ingest call's launches, and the state's release
+static int talk_fold_records(fa_ctx* c, const void* d_buf, size_t len, const uint32_t* d_off, size_t n);
+static void talk_destroy(fa_ctx* c);
 
 extern "C" uint32_t fa_abi_version(void) { return FA_ABI_VERSION; }
 
@@ -607,6 +612,7 @@ extern "C" void fa_destroy(fa_ctx* c) {
     (void)hipFree(c->wtab);
     (void)hipFree(c->wspill);
     (void)hipFree(c->port_hist);
+    talk_destroy(c);
     for (auto* pool : {&c->ev_pool, &c->dev_pool})
         for (auto& p : *pool) {
             (void)hipEventDestroy(p.e0);
@@ -641,6 +647,7 @@ static bool bucket_range(const fa_ctx* c, uint32_t timeslot, uint32_t& lo, uint3
 
 #include "rows_host.inc"
 #include "group_host.inc"
+#include "talkers_host.inc"
 
 extern "C" int fa_stats(fa_ctx* c, fa_stats_t* out) {
     FA_ON_DEVICE(c);

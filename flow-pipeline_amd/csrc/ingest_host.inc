@@ -456,12 +456,15 @@ static int ingest_device_any(fa_ctx* c, const void* d_buf, size_t len, const voi
             used += bytes;
             i += m;
         }
-        return FA_OK;
+        // exact top talkers: the second pass, once per call, behind everything the call queued (the offsets of the split above)
+        return c->talk ? talk_fold_records(c, d_buf, len, off, total) : FA_OK;
     }
     if (n == 0) return FA_OK;
     if (!d_buf || len >= (1ull << 32) || n > c->cfg.max_batch_records || ((uintptr_t)d_buf & 15) || ((uintptr_t)d_off & 3))
         return fail(c, FA_ERR_ARG, "fa_ingest_device: bad buffer (16-byte aligned, < 4 GiB, n <= max_batch_records)");
-    return ingest_device_records(c, d_buf, len, len, d_off, n);
+    const int rc = ingest_device_records(c, d_buf, len, len, d_off, n);
+    if (rc || !c->talk) return rc;
+    return talk_fold_records(c, d_buf, len, (const uint32_t*)d_off, n);
 }
 
 // the launch arguments that name a table (settle / rebuild_* replace them)

@@ -20,6 +20,7 @@
 //   framing.cuh   offsets == NULL: the framed chain cut into records on the device (guess, fixed-point proof, emit);
 //   merge.cuh     window close in HBM: rows collected, sorted over the key bits that differ (rowplan.cuh), equal keys summed,
 //                 emit order; hash partition of a row set for the multi-GPU close (row_partition_kernel);
+//   talkers.cuh   exact GROUP BY SrcAddr / DstAddr (opt-in second pass): the decoded columns folded into two tables of their own;
 //   maintenance.cuh  table scans, rebuilds, the wide log's reads / folds / drops (wdrop_kernel: a close zeroes sums in place).
 //
 // Roofline: HBM-bound integer/byte work; algorithmic bytes = wire bytes, read
@@ -32,3 +33,4 @@
 #include "maintenance.cuh"
 #include "merge.cuh"
 #include "framing.cuh"
+#include "talkers.cuh"

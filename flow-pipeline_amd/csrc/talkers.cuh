@@ -1,0 +1,313 @@
+// talkers.cuh - exact GROUP BY SrcAddr / DstAddr "top talkers", grouped as the dashboards do (gfx950).
+//
+// The two top-talker panels (viz-ch.json:233 SrcAddr, :479 DstAddr) group by the RENDERED string
+//   if(EType = 0x800, IPv4NumToString(first four bytes), IPv6NumToString(Addr))
+// so the group key is the string's preimage (talker_canon below):
+//   EType == 0x800   family 0x800, key = bytes 0..3 followed by twelve zero bytes (fa_format_addr ignores bytes 4..15);
+//   any other EType  family 0,     key = all 16 bytes (0x86dd, 0, 0x1234 ... fall into one group).
+// The same 16 bytes under the two families are two groups: a dotted quad is never an IPv6NumToString output.
+// value = sum(Bytes * SamplingRate) mod 2^64 and count(); a group of weight 0 is still a row.
+//
+// State: two open-addressed tables of their own (SrcAddr, DstAddr) - never the ctx's wide table.  Slot = one 64-byte line:
+// three key words + weight + count.  Every key word has bit 63 set, so 0 is EMPTY for each; a slot is claimed word by
+// word with 64-bit CAS in the order w0..w2 (the argument of wide.cuh: a word is written once, a contender that loses
+// word j leaves the slot, so the lane that wins w2 matched w0 and w1).  Probing is linear over the WHOLE table and has
+// no limit: the host keeps the load at or below 1/2 before every launch (talkers_host.inc), so a probe sequence ends
+// and no update is ever parked or lost.
+//
+// talker_fold_kernel, the hot part: one lane per record of the decoded columns (six of them, 53 bytes per record), both
+// tables in one pass.  A workgroup-private LDS cache of (key, family) -> (weight, count) per direction absorbs repeats -
+// mocker-shaped and Zipf streams would otherwise put millions of same-address atomics on a handful of L2 lines (why the
+// ingest kernel has its hot-address cache and LdsMinutes).  An entry's key is three words too, claimed word by word with
+// LDS CAS; a lane that loses a word tries the next entry (TALK_LDS_PROBES of them), then goes straight to the global
+// table.  The cache is cleared at the start and flushed at the end, one global upsert per occupied entry.
+//
+// Invariants:
+//   - an LDS entry or a global slot only ever holds ONE key (write-once words, claimed in order);
+//   - every (record, direction) update is applied exactly once: to the cache (and from there once by the flush) or to
+//     the global table, never both;
+//   - u64 wrap-around adds commute: any order of updates, chunks, growths and merges gives bit-identical sums.
+//
+// Sizes (reasoned, not yet measured on hardware - DESIGN.md 3.7): 512 threads and 512 entries per direction = 40 KiB of LDS per
+// workgroup, two workgroups per CU = 16 waves per CU behind the random-access latency of the global upserts, half of
+// the CU's 160 KiB of LDS.  A launch flushes at most 2 x 512 entries per workgroup: 2^19 upserts for a chunk of 2^20
+// records whose 2^21 updates would otherwise all be global.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "table.cuh"
+
+namespace fa {
+
+constexpr uint32_t TALK_FAMILY_V4 = 0x800u;
+
+// (lo, hi) = the FixedString(16) as two little-endian u64 (lo = bytes 0..7).  Returns the family.
+__host__ __device__ __forceinline__ uint32_t talker_canon_words(uint64_t& lo, uint64_t& hi, uint32_t etype) {
+    if (etype != TALK_FAMILY_V4) return 0u;
+    lo &= 0xffffffffull;  // bytes 0..3
+    hi = 0;
+    return TALK_FAMILY_V4;
+}
+__host__ __device__ __forceinline__ void talker_canon(const uint8_t addr[16], uint32_t etype, uint64_t* lo, uint64_t* hi, uint32_t* family) {
+    uint64_t l = 0, h = 0;
+    for (int i = 0; i < 8; i++) {
+        l |= (uint64_t)addr[i] << (8 * i);
+        h |= (uint64_t)addr[8 + i] << (8 * i);
+    }
+    *family = talker_canon_words(l, h, etype);
+    *lo = l;
+    *hi = h;
+}
+
+struct TKey {
+    unsigned long long w[3];
+};
+// 128 key bits + the family bit in three words that are never 0
+__host__ __device__ __forceinline__ void tkey_pack(uint64_t lo, uint64_t hi, uint32_t family, TKey& k) {
+    constexpr unsigned long long B63 = 1ull << 63, M63 = B63 - 1;
+    k.w[0] = B63 | (lo & M63);
+    k.w[1] = B63 | (((lo >> 63) | (hi << 1)) & M63);
+    k.w[2] = B63 | (hi >> 62) | (family ? 4ull : 0ull);
+}
+__host__ __device__ __forceinline__ void tkey_unpack(const unsigned long long w[3], unsigned long long& lo, unsigned long long& hi, uint32_t& family) {
+    constexpr unsigned long long M63 = (1ull << 63) - 1;
+    const unsigned long long a = w[0] & M63, b = w[1] & M63;
+    lo = a | (b << 63);
+    hi = (b >> 1) | ((w[2] & 3ull) << 62);
+    family = (w[2] & 4ull) ? TALK_FAMILY_V4 : 0u;
+}
+__host__ __device__ __forceinline__ uint32_t tkey_hash(const TKey& k) {
+    return key_hash(k.w[0] ^ (k.w[2] * 0x9E3779B97F4A7C15ull), k.w[1]);
+}
+
+struct __attribute__((aligned(64))) TSlot {
+    unsigned long long w[3], pad0;
+    unsigned long long weight, count, pad1, pad2;
+};
+static_assert(sizeof(TSlot) == 64, "one talker slot per 64-byte line");
+
+struct TalkCounters {
+    unsigned long long used[2];   // occupied slots: the lane that wins the last key word counts the key, the counts are summed per wave /
+                                  // workgroup and added once at the end of the kernel (one word for every creation of the chip serialises)
+    unsigned long long folded;    // status == 0 records folded
+    unsigned long long absorbed;  // (record, direction) updates that ended in an LDS cache
+    unsigned long long lost;      // updates that met a full table: the host's capacity rule was broken (never on a correct host)
+};
+
+// One public row (include/flowagg.h: fa_talker_row), 40 bytes.
+struct TalkRow {
+    unsigned long long key[2];  // the 16 canonical bytes
+    uint32_t etype, pad;
+    unsigned long long weight, count;
+};
+static_assert(sizeof(TalkRow) == 40, "fa_talker_row");
+
+// Adds (w, cnt) to k's slot of table `d`, claiming one if the key is new.  Stale plain reads (per-XCD L2s are not
+// coherent) can only show EMPTY or the final word - never a false match; an EMPTY that is stale is settled by the CAS.
+// created: the lane's count of keys it created (talk_count_created adds the wave's sum to TalkCounters::used).
+__device__ __forceinline__ void talk_upsert(TSlot* tab, uint32_t mask, const TKey& k, uint32_t h, uint64_t w, uint64_t cnt, TalkCounters* ctr, uint32_t& created) {
+    uint32_t i = h & mask;
+    // (the bound is the table itself: with the load at or below 1/2 an EMPTY slot is met long before it)
+    for (uint32_t probe = 0; probe <= mask; probe++, i = (i + 1u) & mask) {
+        TSlot* s = &tab[i];
+        const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(&s->w[0]);
+        unsigned long long c[3] = {k01.x, k01.y, s->w[2]};
+        bool mine = true;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            if (!mine) break;
+            if (c[j] == 0) {
+                c[j] = atomicCAS(&s->w[j], 0ull, k.w[j]);
+                if (c[j] == 0) {
+                    c[j] = k.w[j];
+                    if (j == 2) created++;  // this lane created the group
+                }
+            }
+            mine = c[j] == k.w[j];
+        }
+        if (mine) {
+            if (w) atomicAdd(&s->weight, (unsigned long long)w);
+            atomicAdd(&s->count, (unsigned long long)cnt);
+            return;
+        }
+    }
+    atomicAdd(&ctr->lost, 1ull);
+}
+
+// (all lanes of the wave: after the kernel's loop)
+__device__ __forceinline__ void talk_count_created(unsigned long long* used, uint32_t created) {
+    const uint64_t s = wave_sum_u64(created);
+    if (__lane_id() == 0 && s) atomicAdd(used, (unsigned long long)s);
+}
+
+constexpr int TALK_BLOCK = 512;
+#ifndef FA_TALK_LDS_ENTRIES
+#define FA_TALK_LDS_ENTRIES 512
+#endif
+constexpr int TALK_LDS_ENTRIES = FA_TALK_LDS_ENTRIES;  // per direction, a power of two
+constexpr int TALK_LDS_PROBES = 4;
+constexpr int TALK_WG_PER_CU = 2;
+static_assert((TALK_LDS_ENTRIES & (TALK_LDS_ENTRIES - 1)) == 0, "the cache is indexed by hash bits");
+
+struct TalkLds {
+    unsigned long long k0[2][TALK_LDS_ENTRIES], k1[2][TALK_LDS_ENTRIES], k2[2][TALK_LDS_ENTRIES];
+    unsigned long long w[2][TALK_LDS_ENTRIES], c[2][TALK_LDS_ENTRIES];
+    unsigned long long absorbed, folded, created[2];
+};
+
+// one key word of an entry: EMPTY is claimed, then it must be ours.  (A plain read that shows a word is final.)
+__device__ __forceinline__ bool talk_lds_word(unsigned long long* p, unsigned long long want) {
+    unsigned long long cur = *p;
+    if (cur == 0) {
+        cur = atomicCAS(p, 0ull, want);
+        if (cur == 0) cur = want;
+    }
+    return cur == want;
+}
+// true = absorbed by the workgroup's cache
+__device__ __forceinline__ bool talk_lds_add(TalkLds& L, int d, const TKey& k, uint32_t h, uint64_t w) {
+    uint32_t i = (h >> 9) & (TALK_LDS_ENTRIES - 1);
+#pragma unroll 1
+    for (int probe = 0; probe < TALK_LDS_PROBES; probe++, i = (i + 1u) & (TALK_LDS_ENTRIES - 1)) {
+        if (!talk_lds_word(&L.k0[d][i], k.w[0])) continue;
+        if (!talk_lds_word(&L.k1[d][i], k.w[1])) continue;
+        if (!talk_lds_word(&L.k2[d][i], k.w[2])) continue;
+        if (w) atomicAdd(&L.w[d][i], (unsigned long long)w);
+        atomicAdd(&L.c[d][i], 1ull);  // (count even when the weight is 0)
+        return true;
+    }
+    return false;
+}
+
+struct TalkFoldArgs {
+    const uint4* src_addr;
+    const uint4* dst_addr;
+    const uint32_t* etype;
+    const uint64_t* bytes;
+    const uint64_t* sampling_rate;
+    const uint8_t* status;
+    uint32_t n;
+    TSlot* tab[2];
+    uint32_t mask[2];
+    TalkCounters* ctr;
+};
+
+__global__ __launch_bounds__(TALK_BLOCK) void talker_fold_kernel(TalkFoldArgs a) {
+    __shared__ TalkLds L;
+    for (int i = threadIdx.x; i < 2 * TALK_LDS_ENTRIES; i += TALK_BLOCK) {
+        (&L.k0[0][0])[i] = 0;
+        (&L.k1[0][0])[i] = 0;
+        (&L.k2[0][0])[i] = 0;
+        (&L.w[0][0])[i] = 0;
+        (&L.c[0][0])[i] = 0;
+    }
+    if (threadIdx.x == 0) L.absorbed = L.folded = L.created[0] = L.created[1] = 0;
+    __syncthreads();
+    uint32_t absorbed = 0, folded = 0, created[2] = {0, 0};
+    for (uint64_t i = (uint64_t)blockIdx.x * TALK_BLOCK + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * TALK_BLOCK) {
+        if (a.status[i]) continue;  // malformed: dropped, whatever the other columns hold
+        folded++;
+        const uint32_t et = a.etype[i];
+        const uint64_t w = a.bytes[i] * a.sampling_rate[i];
+#pragma unroll
+        for (int d = 0; d < 2; d++) {
+            const uint4 q = (d ? a.dst_addr : a.src_addr)[i];
+            uint64_t lo = (uint64_t)q.y << 32 | q.x, hi = (uint64_t)q.w << 32 | q.z;
+            const uint32_t fam = talker_canon_words(lo, hi, et);
+            TKey k;
+            tkey_pack(lo, hi, fam, k);
+            const uint32_t h = tkey_hash(k);
+            if (talk_lds_add(L, d, k, h, w)) absorbed++;
+            else talk_upsert(a.tab[d], a.mask[d], k, h, w, 1, a.ctr, created[d]);
+        }
+    }
+    const uint64_t wa = wave_sum_u64(absorbed), wf = wave_sum_u64(folded);
+    if (__lane_id() == 0) {
+        if (wa) atomicAdd(&L.absorbed, (unsigned long long)wa);
+        if (wf) atomicAdd(&L.folded, (unsigned long long)wf);
+    }
+    __syncthreads();
+    // flush: every occupied entry is complete by now (the lane that claimed w0 went on to w1 and w2, or met them claimed)
+    for (int e = threadIdx.x; e < 2 * TALK_LDS_ENTRIES; e += TALK_BLOCK) {
+        const int d = e / TALK_LDS_ENTRIES, j = e % TALK_LDS_ENTRIES;
+        if (L.k0[d][j] == 0) continue;
+        TKey k;
+        k.w[0] = L.k0[d][j];
+        k.w[1] = L.k1[d][j];
+        k.w[2] = L.k2[d][j];
+        talk_upsert(a.tab[d], a.mask[d], k, tkey_hash(k), L.w[d][j], L.c[d][j], a.ctr, created[d]);
+    }
+#pragma unroll
+    for (int d = 0; d < 2; d++) {
+        const uint64_t wc = wave_sum_u64(created[d]);
+        if (__lane_id() == 0 && wc) atomicAdd(&L.created[d], (unsigned long long)wc);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {  // one atomic per workgroup and counter
+        if (L.absorbed) atomicAdd(&a.ctr->absorbed, L.absorbed);
+        if (L.folded) atomicAdd(&a.ctr->folded, L.folded);
+        if (L.created[0]) atomicAdd(&a.ctr->used[0], L.created[0]);
+        if (L.created[1]) atomicAdd(&a.ctr->used[1], L.created[1]);
+    }
+}
+
+// Growth: every occupied slot of the old table is inserted again (key, weight, count) - the sums stay exact.
+__global__ __launch_bounds__(256) void talker_rehash_kernel(const TSlot* old_tab, uint64_t old_slots, TSlot* tab, uint32_t mask, TalkCounters* ctr, int d) {
+    uint32_t created = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_slots; i += (uint64_t)gridDim.x * blockDim.x) {
+        const TSlot* s = &old_tab[i];
+        if (s->w[0] == 0) continue;
+        TKey k;
+        k.w[0] = s->w[0];
+        k.w[1] = s->w[1];
+        k.w[2] = s->w[2];
+        talk_upsert(tab, mask, k, tkey_hash(k), s->weight, s->count, ctr, created);
+    }
+    talk_count_created(&ctr->used[d], created);
+}
+
+// fa_merge_talkers: canonical rows of another ctx.
+__global__ __launch_bounds__(256) void talker_merge_kernel(const TalkRow* rows, uint32_t n, TSlot* tab, uint32_t mask, TalkCounters* ctr, int d) {
+    uint32_t created = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        TKey k;
+        tkey_pack(rows[i].key[0], rows[i].key[1], rows[i].etype, k);
+        talk_upsert(tab, mask, k, tkey_hash(k), rows[i].weight, rows[i].count, ctr, created);
+    }
+    talk_count_created(&ctr->used[d], created);
+}
+
+// ---- read side: compaction, sort keys, emit ---------------------------------------------------------------------
+__global__ __launch_bounds__(256) void talker_collect_kernel(const TSlot* tab, uint64_t slots, TalkRow* rows, uint32_t cap, unsigned int* cursor) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * blockDim.x) {
+        const TSlot* s = &tab[i];
+        if (s->w[0] == 0) continue;
+        const unsigned int j = atomicAdd(cursor, 1u);
+        if (j >= cap) continue;  // (cannot happen: cap = the table's own count of occupied slots)
+        TalkRow r;
+        tkey_unpack(s->w, r.key[0], r.key[1], r.etype);
+        r.pad = 0;
+        r.weight = s->weight;
+        r.count = s->count;
+        rows[j] = r;
+    }
+}
+__device__ __forceinline__ unsigned long long talk_bswap64(unsigned long long v) { return __builtin_bswap64(v); }
+// Sort key of pass p over the rows in their current order (perm == nullptr: the identity, which is written to perm_out).
+// Emit order = weight DESC, key bytes ascending (memcmp), etype ascending - least significant criterion first, stable passes:
+//   0 etype   1 bytes 8..15 as a big-endian word   2 bytes 0..7 as a big-endian word   3 the inverted weight
+__global__ __launch_bounds__(256) void talker_sortkey_kernel(const TalkRow* rows, const uint32_t* perm, uint32_t n, int pass, unsigned long long* keys, uint32_t* perm_out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t j = perm ? perm[i] : i;
+        if (!perm) perm_out[i] = i;
+        const TalkRow& r = rows[j];
+        keys[i] = pass == 0 ? (unsigned long long)r.etype : pass == 1 ? talk_bswap64(r.key[1]) : pass == 2 ? talk_bswap64(r.key[0]) : ~r.weight;
+    }
+}
+__global__ __launch_bounds__(256) void talker_emit_kernel(const TalkRow* rows, const uint32_t* perm, uint32_t n, TalkRow* out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = rows[perm[i]];
+}
+
+}  // namespace fa

@@ -1,0 +1,349 @@
+// talkers_host.inc - host side of the exact top talkers (included by flowagg.hip: one translation unit; device side: talkers.cuh).
+//
+// Capacity rule.  Per table the host keeps an upper bound used_ub of the occupied slots: a chunk of m records (or m merged
+// rows) adds at most m keys.  Before a launch, if (used_ub + m) * 2 > capacity, the stream is synchronised and the device's
+// exact count replaces the bound; while the inequality still holds the table doubles (talker_rehash_kernel re-inserts every
+// slot).  So every launch finds its table at or below half full when it ends - the unbounded probe loops of talkers.cuh end.
+// 2^30 slots is the limit: FA_ERR_TABLE_FULL BEFORE the chunk is folded.
+// Chunks: at most FA_TALK_CHUNK records (default 2^20), and at most max(2^16, capacity / 4) so that a small table grows in
+// steps instead of jumping to the worst case of a large chunk.
+
+struct TalkState {
+    TSlot* tab[2] = {nullptr, nullptr};
+    uint32_t log2[2] = {16, 16};
+    uint64_t used_ub[2] = {0, 0};
+    TalkCounters* d_ctr = nullptr;
+    size_t chunk = (size_t)1 << 20;  // env FA_TALK_CHUNK
+    uint32_t wgpc = TALK_WG_PER_CU;  // env FA_TALK_WGPC (A/B: workgroups per CU of the fold kernel)
+    uint64_t grows = 0, fold_launches = 0, fold_ns_total = 0;
+    struct Ev { hipEvent_t e0, e1; };
+    std::vector<Ev> ev;   // one pair per fold launch that has not been read yet
+    size_t ev_used = 0;
+    void* scratch = nullptr;  // fa_top_talkers: rows, ordered rows, sort keys, permutations, hipcub storage
+    size_t scratch_cap = 0;
+};
+
+static void talk_destroy(fa_ctx* c) {
+    TalkState* t = c->talk;
+    if (!t) return;
+    (void)hipFree(t->tab[0]);
+    (void)hipFree(t->tab[1]);
+    (void)hipFree(t->d_ctr);
+    (void)hipFree(t->scratch);
+    for (auto& e : t->ev) {
+        (void)hipEventDestroy(e.e0);
+        (void)hipEventDestroy(e.e1);
+    }
+    delete t;
+    c->talk = nullptr;
+}
+
+#define TALK_ENTER(c)                                                                                  \
+    FA_ON_DEVICE(c);                                                                                   \
+    if (!(c)) return FA_ERR_ARG;                                                                       \
+    if ((c)->sticky) return (c)->sticky;                                                               \
+    if (!(c)->talk) return fail((c), FA_ERR_UNSUPPORTED, "top talkers are not enabled on this ctx (fa_talkers_enable)")
+
+extern "C" int fa_talkers_enable(fa_ctx* c, uint32_t capacity_log2) {
+    FA_ON_DEVICE(c);
+    if (!c) return FA_ERR_ARG;
+    if (c->sticky) return c->sticky;
+    if (c->talk) return fail(c, FA_ERR_ARG, "fa_talkers_enable: already enabled");
+    if (capacity_log2 == 0) capacity_log2 = 16;
+    if (capacity_log2 < 8 || capacity_log2 > 30) return fail(c, FA_ERR_ARG, "fa_talkers_enable: capacity_log2 is 0 or 8..30");
+    TalkState* t = new TalkState();
+    if (const char* d = getenv("FA_TALK_CHUNK")) t->chunk = (size_t)std::min<long long>(1ll << 28, std::max<long long>(1, atoll(d)));
+    if (const char* d = getenv("FA_TALK_WGPC")) t->wgpc = (uint32_t)std::min(8, std::max(1, atoi(d)));
+    c->talk = t;
+    bool ok = hipMalloc(&t->d_ctr, sizeof(TalkCounters)) == hipSuccess && hipMemsetAsync(t->d_ctr, 0, sizeof(TalkCounters), c->stream) == hipSuccess;
+    for (int d = 0; d < 2 && ok; d++) {
+        t->log2[d] = capacity_log2;
+        ok = hipMalloc(&t->tab[d], sizeof(TSlot) << capacity_log2) == hipSuccess && hipMemsetAsync(t->tab[d], 0, sizeof(TSlot) << capacity_log2, c->stream) == hipSuccess;
+    }
+    ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        talk_destroy(c);
+        return fail(c, FA_ERR_NOMEM, "fa_talkers_enable: allocating the tables failed");
+    }
+    return FA_OK;
+}
+
+// Waits for the stream; the device counters and the fold launches' times.
+static int talk_settle(fa_ctx* c, TalkCounters& h) {
+    TalkState* t = c->talk;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(&h, t->d_ctr, sizeof h, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < t->ev_used; i++) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, t->ev[i].e0, t->ev[i].e1) == hipSuccess) t->fold_ns_total += (uint64_t)((double)ms * 1e6);
+    }
+    t->ev_used = 0;
+    if (h.lost) {
+        c->sticky = FA_ERR_TABLE_FULL;
+        return fail(c, FA_ERR_TABLE_FULL, "internal: a talker table was full during a launch; updates were lost");
+    }
+    return FA_OK;
+}
+
+static int talk_grow(fa_ctx* c, int d) {
+    TalkState* t = c->talk;
+    const uint32_t nl = t->log2[d] + 1;
+    TSlot* nt = nullptr;
+    if (hipMalloc(&nt, sizeof(TSlot) << nl) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, FA_ERR_NOMEM, "hipMalloc(talker table) failed");
+    }
+    hipError_t e = hipMemsetAsync(nt, 0, sizeof(TSlot) << nl, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(&t->d_ctr->used[d], 0, sizeof(unsigned long long), c->stream);  // (the rehash counts every key again)
+    if (e == hipSuccess) {
+        const uint64_t slots = 1ull << t->log2[d];
+        const unsigned g = (unsigned)std::min<uint64_t>((slots + 255) / 256, (uint64_t)c->num_cus * 8);
+        hipLaunchKernelGGL(talker_rehash_kernel, dim3(g), dim3(256), 0, c->stream, (const TSlot*)t->tab[d], slots, nt, (uint32_t)((1ull << nl) - 1), t->d_ctr, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(nt);
+        c->sticky = FA_ERR_HIP;  // (the occupied-slot counter was reset: the state is no longer trustworthy)
+        c->err = std::string("talker table growth: ") + hipGetErrorString(e);
+        return FA_ERR_HIP;
+    }
+    (void)hipFree(t->tab[d]);
+    t->tab[d] = nt;
+    t->log2[d] = nl;
+    t->grows++;
+    return FA_OK;
+}
+
+// Room for m more keys in table d at a load of at most 1/2 (the capacity rule above).
+static int talk_reserve(fa_ctx* c, int d, uint64_t m) {
+    TalkState* t = c->talk;
+    if ((t->used_ub[d] + m) * 2 <= (1ull << t->log2[d])) return FA_OK;
+    TalkCounters h;
+    int rc = talk_settle(c, h);
+    if (rc) return rc;
+    t->used_ub[0] = h.used[0];
+    t->used_ub[1] = h.used[1];
+    while ((t->used_ub[d] + m) * 2 > (1ull << t->log2[d])) {
+        if (t->log2[d] >= 30) return fail(c, FA_ERR_TABLE_FULL, "a talker table cannot grow further (2^30 slots)");
+        rc = talk_grow(c, d);
+        if (rc) return rc;
+    }
+    return FA_OK;
+}
+
+static size_t talk_chunk_cap(const fa_ctx* c) {
+    const TalkState* t = c->talk;
+    const uint64_t cap = 1ull << std::min(t->log2[0], t->log2[1]);
+    return (size_t)std::min<uint64_t>(t->chunk, std::max<uint64_t>(1ull << 16, cap / 4));
+}
+
+struct TalkCols {
+    const void *src_addr, *dst_addr, *etype, *bytes, *sampling_rate, *status;
+};
+
+static int talk_fold_cols(fa_ctx* c, const TalkCols& p, size_t n) {
+    TalkState* t = c->talk;
+    for (size_t i = 0; i < n;) {
+        const size_t m = std::min(n - i, talk_chunk_cap(c));
+        for (int d = 0; d < 2; d++) {
+            int rc = talk_reserve(c, d, m);
+            if (rc) return rc;
+        }
+        if (t->ev_used == t->ev.size()) {
+            if (t->ev.size() >= 1024) {  // bound the pool: read what is pending
+                TalkCounters h;
+                int rc = talk_settle(c, h);
+                if (rc) return rc;
+            } else {
+                TalkState::Ev e{};
+                HIPCHK(c, hipEventCreate(&e.e0));
+                if (hipEventCreate(&e.e1) != hipSuccess) {
+                    (void)hipEventDestroy(e.e0);
+                    return fail(c, FA_ERR_HIP, "hipEventCreate failed");
+                }
+                t->ev.push_back(e);
+            }
+        }
+        TalkFoldArgs a{};
+        a.src_addr = (const uint4*)p.src_addr + i;
+        a.dst_addr = (const uint4*)p.dst_addr + i;
+        a.etype = (const uint32_t*)p.etype + i;
+        a.bytes = (const uint64_t*)p.bytes + i;
+        a.sampling_rate = (const uint64_t*)p.sampling_rate + i;
+        a.status = (const uint8_t*)p.status + i;
+        a.n = (uint32_t)m;
+        for (int d = 0; d < 2; d++) {
+            a.tab[d] = t->tab[d];
+            a.mask[d] = (uint32_t)((1ull << t->log2[d]) - 1);
+        }
+        a.ctr = t->d_ctr;
+        // persistent grid: the workgroups that are co-resident, records grid-strided
+        const uint32_t grid = (uint32_t)std::max<size_t>(1, std::min<size_t>((m + TALK_BLOCK - 1) / TALK_BLOCK, (size_t)c->num_cus * t->wgpc));
+        TalkState::Ev& ev = t->ev[t->ev_used++];
+        (void)hipEventRecord(ev.e0, c->stream);
+        hipLaunchKernelGGL(talker_fold_kernel, dim3(grid), dim3(TALK_BLOCK), 0, c->stream, a);
+        (void)hipEventRecord(ev.e1, c->stream);
+        HIPCHK(c, hipGetLastError());
+        t->fold_launches++;
+        t->used_ub[0] += m;
+        t->used_ub[1] += m;
+        i += m;
+    }
+    return FA_OK;
+}
+
+// The second pass of an enabled ctx's ingest call (ingest_device_any): the call's n records decoded again in chunks -
+// fa_decode_device's launch on the sub-range (d_buf, len, d_off + i, m) - and each chunk's columns folded, all on the ctx stream
+// behind the launches of the ingest itself.
+static int talk_fold_records(fa_ctx* c, const void* d_buf, size_t len, const uint32_t* d_off, size_t n) {
+    for (size_t i = 0; i < n;) {
+        const size_t m = std::min({n - i, talk_chunk_cap(c), (size_t)c->cfg.max_batch_records});
+        fa_columns cols;
+        int rc = decode_device_records(c, d_buf, len, (size_t)((double)len * (double)m / (double)n), d_off + i, m, &cols);
+        if (rc) return rc;
+        const TalkCols p{cols.src_addr, cols.dst_addr, cols.etype, cols.bytes, cols.sampling_rate, cols.status};
+        rc = talk_fold_cols(c, p, m);
+        if (rc) return rc;
+        i += m;
+    }
+    return FA_OK;
+}
+
+extern "C" int fa_talkers_fold_columns_device(fa_ctx* c, const fa_columns* cols, size_t n) {
+    TALK_ENTER(c);
+    if (n == 0) return FA_OK;
+    if (!cols || !cols->src_addr || !cols->dst_addr || !cols->etype || !cols->bytes || !cols->sampling_rate || !cols->status)
+        return fail(c, FA_ERR_ARG, "fa_talkers_fold_columns_device: src_addr, dst_addr, etype, bytes, sampling_rate and status are needed");
+    if ((((uintptr_t)cols->src_addr | (uintptr_t)cols->dst_addr) & 15) || (((uintptr_t)cols->bytes | (uintptr_t)cols->sampling_rate) & 7) || ((uintptr_t)cols->etype & 3))
+        return fail(c, FA_ERR_ARG, "fa_talkers_fold_columns_device: the address columns must be 16-byte aligned (the others naturally)");
+    const TalkCols p{cols->src_addr, cols->dst_addr, cols->etype, cols->bytes, cols->sampling_rate, cols->status};
+    return talk_fold_cols(c, p, n);
+}
+
+extern "C" int fa_merge_talkers(fa_ctx* c, int dst, const fa_talker_row* rows, size_t n) {
+    TALK_ENTER(c);
+    if ((!rows && n) || (dst != 0 && dst != 1)) return fail(c, FA_ERR_ARG, "fa_merge_talkers: bad argument");
+    static_assert(sizeof(fa_talker_row) == sizeof(TalkRow), "row layout");
+    for (size_t i = 0; i < n; i++) {  // all rows are looked at before the first is merged
+        bool ok = rows[i].etype == 0 || rows[i].etype == TALK_FAMILY_V4;
+        if (ok && rows[i].etype == TALK_FAMILY_V4)
+            for (int b = 4; b < 16; b++) ok = ok && rows[i].key[b] == 0;
+        if (!ok) return fail(c, FA_ERR_ARG, "fa_merge_talkers: a row is not canonical (etype 0 or 0x800; bytes 4..15 zero under 0x800)");
+    }
+    TalkState* t = c->talk;
+    for (size_t i = 0; i < n;) {
+        const size_t m = std::min(n - i, talk_chunk_cap(c));
+        int rc = talk_reserve(c, dst, m);
+        if (rc) return rc;
+        TalkRow* d = nullptr;
+        if (hipMalloc(&d, m * sizeof(TalkRow)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, FA_ERR_NOMEM, "hipMalloc failed");
+        }
+        hipError_t e = hipMemcpyAsync(d, rows + i, m * sizeof(TalkRow), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(talker_merge_kernel, dim3((unsigned)std::min<size_t>((m + 255) / 256, 1024)), dim3(256), 0, c->stream, (const TalkRow*)d, (uint32_t)m,
+                               t->tab[dst], (uint32_t)((1ull << t->log2[dst]) - 1), t->d_ctr, dst);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (the caller's rows are not referenced after the call)
+        (void)hipFree(d);
+        if (e != hipSuccess) {
+            c->err = std::string("fa_merge_talkers: ") + hipGetErrorString(e);
+            return FA_ERR_HIP;
+        }
+        t->used_ub[dst] += m;
+        i += m;
+    }
+    return FA_OK;
+}
+
+extern "C" int fa_talkers_reset(fa_ctx* c) {
+    TALK_ENTER(c);
+    TalkState* t = c->talk;
+    TalkCounters h;
+    int rc = talk_settle(c, h);
+    if (rc) return rc;
+    for (int d = 0; d < 2; d++) HIPCHK(c, hipMemsetAsync(t->tab[d], 0, sizeof(TSlot) << t->log2[d], c->stream));
+    HIPCHK(c, hipMemsetAsync(&t->d_ctr->used[0], 0, 2 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    t->used_ub[0] = t->used_ub[1] = 0;
+    return FA_OK;
+}
+
+extern "C" int fa_talkers_stats(fa_ctx* c, fa_talkers_stats_t* out) {
+    TALK_ENTER(c);
+    if (!out) return fail(c, FA_ERR_ARG, "fa_talkers_stats: null argument");
+    TalkState* t = c->talk;
+    TalkCounters h;
+    int rc = talk_settle(c, h);
+    if (rc) return rc;
+    for (int d = 0; d < 2; d++) {
+        t->used_ub[d] = h.used[d];
+        out->used[d] = h.used[d];
+        out->capacity[d] = 1ull << t->log2[d];
+    }
+    out->records_folded = h.folded;
+    out->records_absorbed = h.absorbed;
+    out->grows = t->grows;
+    out->fold_launches = t->fold_launches;
+    out->fold_ns_total = t->fold_ns_total;
+    return FA_OK;
+}
+
+// Every group, or the first k, in emit order: the occupied slots are compacted into rows, ordered ON THE DEVICE by four stable
+// radix sorts over (key word, index) - least significant criterion first - and only the rows returned are copied out.
+extern "C" int fa_top_talkers(fa_ctx* c, int dst, size_t k, fa_talker_row* out, size_t cap, size_t* n_out) {
+    TALK_ENTER(c);
+    if ((dst != 0 && dst != 1) || !n_out || (!out && cap)) return fail(c, FA_ERR_ARG, "fa_top_talkers: bad argument");
+    TalkState* t = c->talk;
+    TalkCounters h;
+    int rc = talk_settle(c, h);
+    if (rc) return rc;
+    t->used_ub[0] = h.used[0];
+    t->used_ub[1] = h.used[1];
+    const size_t used = (size_t)h.used[dst];
+    const size_t need = k ? std::min(k, used) : used;
+    *n_out = need;
+    if (need > cap) return fail(c, FA_ERR_CAPACITY, "fa_top_talkers: output buffer too small");
+    if (need == 0) return FA_OK;
+    const uint32_t n = (uint32_t)used;  // (<= 2^29: the load is at most 1/2)
+    size_t tmp_bytes = 0;
+    if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0,
+                                           64, c->stream) != hipSuccess)
+        return fail(c, FA_ERR_HIP, "fa_top_talkers: sort sizing failed");
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t rows_b = al((size_t)n * sizeof(TalkRow)), out_b = al(need * sizeof(TalkRow)), key_b = al((size_t)n * 8), perm_b = al((size_t)n * 4);
+    rc = ensure_dev(c, &t->scratch, &t->scratch_cap, rows_b + out_b + 2 * key_b + 2 * perm_b + 256 + al(tmp_bytes), "talker rows");
+    if (rc) return rc;
+    uint8_t* p = (uint8_t*)t->scratch;
+    TalkRow* rows = (TalkRow*)p;
+    TalkRow* ordered = (TalkRow*)(p + rows_b);
+    unsigned long long* keys[2] = {(unsigned long long*)(p + rows_b + out_b), (unsigned long long*)(p + rows_b + out_b + key_b)};
+    uint32_t* perm[2] = {(uint32_t*)(p + rows_b + out_b + 2 * key_b), (uint32_t*)(p + rows_b + out_b + 2 * key_b + perm_b)};
+    unsigned int* cursor = (unsigned int*)(p + rows_b + out_b + 2 * key_b + 2 * perm_b);
+    void* tmp = p + rows_b + out_b + 2 * key_b + 2 * perm_b + 256;
+    HIPCHK(c, hipMemsetAsync(cursor, 0, sizeof(unsigned int), c->stream));
+    const uint64_t slots = 1ull << t->log2[dst];
+    const unsigned gs = (unsigned)std::min<uint64_t>((slots + 255) / 256, (uint64_t)c->num_cus * 8);
+    const unsigned gn = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, (uint64_t)c->num_cus * 8);
+    hipLaunchKernelGGL(talker_collect_kernel, dim3(gs), dim3(256), 0, c->stream, (const TSlot*)t->tab[dst], slots, rows, n, cursor);
+    int cur = 0;
+    for (int pass = 0; pass < 4; pass++) {
+        hipLaunchKernelGGL(talker_sortkey_kernel, dim3(gn), dim3(256), 0, c->stream, (const TalkRow*)rows, pass ? (const uint32_t*)perm[cur] : (const uint32_t*)nullptr, n, pass, keys[0],
+                           perm[cur]);
+        size_t tb = tmp_bytes;
+        if (hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const unsigned long long*)keys[0], keys[1], (const uint32_t*)perm[cur], perm[cur ^ 1], (int)n, 0, pass == 0 ? 16 : 64,
+                                               c->stream) != hipSuccess)
+            return fail(c, FA_ERR_HIP, "fa_top_talkers: sort failed");
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL(talker_emit_kernel, dim3((unsigned)std::min<uint64_t>(((uint64_t)need + 255) / 256, (uint64_t)c->num_cus * 8)), dim3(256), 0, c->stream, (const TalkRow*)rows,
+                       (const uint32_t*)perm[cur], (uint32_t)need, ordered);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, ordered, need * sizeof(TalkRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FA_OK;
+}

@@ -373,6 +373,61 @@ int fa_merge_minutes(fa_ctx*, const fa_minute_row* rows, size_t n);
 /* Clears the port groups and the minute series (start of a new $timeFilter range). */
 int fa_dashboard_reset(fa_ctx*);
 
+/* ---- ABI 8, addition: exact top talkers, grouped as the dashboards do ------------ */
+/* The two top-talker panels (viz-ch.json:233 SrcAddr, :479 DstAddr)
+ *   SELECT if(EType = 0x800, IPv4NumToString(...first four bytes...), IPv6NumToString(Addr)) AS ip,
+ *          sum(Bytes*SamplingRate) AS sumbytes ... GROUP BY ip ORDER BY sumbytes DESC
+ * answered exactly (fa_topk ranks by Count-Min estimates).  The group key is the rendered string's preimage:
+ * EType == 0x800 -> family 0x800, address bytes 0..3 followed by twelve zero bytes (bytes 4..15 are ignored, as
+ * fa_format_addr ignores them); any other EType -> family 0, all 16 bytes (records that differ only in a non-0x800
+ * EType are one group).  The same bytes under the two families are two groups.  Only well-formed records count.
+ * Opt-in per ctx and additive: no key_sets bit, no change to any other call's result.  It is a SECOND pass over every
+ * ingested batch - fa_decode_device on sub-ranges of at most FA_TALK_CHUNK records (environment, read by
+ * fa_talkers_enable; default 2^20), each chunk's columns folded into two exact hash tables of their own on the ctx stream.
+ * Consequences on an enabled ctx:
+ *  - every fa_ingest / fa_ingest_device OVERWRITES the ctx's column block: a fa_columns from an earlier fa_decode_device
+ *    is dead after it;
+ *  - fa_stats' decode_launches / decode_ns_total (and records_slow, which the decode pass counts too) include the second pass;
+ *  - if the fold fails after the ingest itself succeeded (FA_ERR_NOMEM / FA_ERR_TABLE_FULL while a table grows), the ingest
+ *    call returns that error, text in fa_last_error: the batch IS in every other aggregate, and in no talker table from
+ *    the failing chunk on.
+ * Every call below except fa_talkers_enable returns FA_ERR_UNSUPPORTED on a ctx that was not enabled. */
+typedef struct {
+    uint8_t key[16];   /* canonical: bytes 4..15 zero when etype == 0x800 */
+    uint32_t etype;    /* 0x800 (IPv4 branch) or 0: fa_format_addr(key, etype) is the string the panel shows */
+    uint32_t _pad;
+    uint64_t weight;   /* exact sum(Bytes*SamplingRate), wraps mod 2^64 */
+    uint64_t count;
+} fa_talker_row;       /* 40 bytes */
+
+typedef struct {
+    uint64_t used[2], capacity[2];   /* SrcAddr, DstAddr tables: occupied slots / slots */
+    uint64_t records_folded;         /* status == 0 records folded so far */
+    uint64_t records_absorbed;       /* (record, direction) updates that ended in a workgroup's LDS cache, not in a global atomic */
+    uint64_t grows;                  /* table rebuilds */
+    uint64_t fold_launches, fold_ns_total; /* the fold kernel alone, hipEvent */
+} fa_talkers_stats_t;
+
+/* Allocates both tables (2^capacity_log2 slots of 64 bytes each; 0 -> 16; 8..30, FA_ERR_ARG otherwise) and the counters.
+ * From then on every successful fa_ingest / fa_ingest_device of the ctx also folds its records' addresses - with offsets
+ * or without, whatever number of launches the library makes of the call.  The tables grow by themselves (doubling, load
+ * kept at or below 1/2; FA_ERR_TABLE_FULL beyond 2^30 slots, before the chunk that would need them is folded).  A second
+ * call is FA_ERR_ARG. */
+int fa_talkers_enable(fa_ctx*, uint32_t capacity_log2);
+/* The same fold for callers that already decode: n records of `cols` - any DEVICE pointers; only src_addr, dst_addr (both
+ * 16-byte aligned), etype, bytes, sampling_rate and status are read.  Asynchronous on the ctx stream. */
+int fa_talkers_fold_columns_device(fa_ctx*, const fa_columns* cols, size_t n);
+/* dst = 0: GROUP BY SrcAddr, 1: DstAddr.  Every group (k = 0) or the first k, ORDER BY weight DESC, ties by key bytes
+ * ascending (memcmp), then etype ascending.  Ordered on the device: only the rows returned cross PCIe.
+ * FA_ERR_CAPACITY: *n_out = rows needed. */
+int fa_top_talkers(fa_ctx*, int dst, size_t k, fa_talker_row* out, size_t cap, size_t* n_out);
+/* Adds rows produced by another ctx / rank (sums commute: two partitions merged equal one ctx over both, bit for bit).
+ * A row that is not canonical (etype not 0 / 0x800, non-zero bytes 4..15 under 0x800) -> FA_ERR_ARG, nothing is merged. */
+int fa_merge_talkers(fa_ctx*, int dst, const fa_talker_row* rows, size_t n);
+/* Empties both tables (they keep their size); the counters of fa_talkers_stats go on counting. */
+int fa_talkers_reset(fa_ctx*);
+int fa_talkers_stats(fa_ctx*, fa_talkers_stats_t* out);
+
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
  *   if(EType = 0x800, IPv4NumToString(reinterpretAsUInt32(substring(reverse(Addr), 13, 4))), IPv6NumToString(Addr))
