@@ -2,15 +2,14 @@
 
 // ---- decode + project ---------------------------------------------------------------------
 static int ensure_columns(fa_ctx* c, size_t n) {
-    if (c->col_cap >= n) return FA_OK;
+    const size_t rec = 5 * 8 + 7 * 4 + 3 * 16 + 1;  // bytes of one record's columns
+    if (c->col_block.bytes() >= n * rec) return FA_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->col_block);
-    c->col_block = nullptr;
+    c->cols = ColumnPtrs{};  // (they point into the block that goes)
     size_t cap = std::max<size_t>(n, 1 << 16);
     cap = (cap + 63) & ~(size_t)63;
-    size_t bytes = cap * (5 * 8 + 7 * 4 + 3 * 16 + 1);
-    if (hipMalloc(&c->col_block, bytes) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(columns) failed");
-    uint8_t* p = (uint8_t*)c->col_block;
+    if (!c->col_block.grow(n * rec, cap * rec)) return fail(c, FA_ERR_NOMEM, "hipMalloc(columns) failed");
+    uint8_t* p = (uint8_t*)c->col_block.get();
     auto take = [&](size_t elem) {
         uint8_t* r = p;
         p += cap * elem;
@@ -32,7 +31,6 @@ static int ensure_columns(fa_ctx* c, size_t n) {
     c->cols.src_port = (uint32_t*)take(4);
     c->cols.dst_port = (uint32_t*)take(4);
     c->cols.status = (uint8_t*)take(1);
-    c->col_cap = cap;
     return FA_OK;
 }
 

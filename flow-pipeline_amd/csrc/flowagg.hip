@@ -27,11 +27,25 @@
 #include <vector>
 
 #include "../../include/flowagg.h"
+#include "buffers.h"
 #include "kernels.cuh"
 
 using namespace fa;
 
 static thread_local std::string g_create_error;
+
+// Every device or pinned allocation of the library is owned by a Buf (buffers.h) over one of these two; nothing else
+// calls the HIP allocation functions.
+struct DevAlloc {
+    static bool alloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; }
+    static void free(void* p) { (void)hipFree(p); }
+};
+struct PinnedAlloc {
+    static bool alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes) == hipSuccess; }
+    static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T = void> using DevBuf = Buf<DevAlloc, T>;
+template <class T = void> using PinnedBuf = Buf<PinnedAlloc, T>;
 
 struct fa_ctx {
     fa_config cfg{};
@@ -44,46 +58,41 @@ struct fa_ctx {
     std::vector<LaunchEvents> dev_pool;  // ... of fa_decode_device launches
     size_t dev_used = 0;
 
-    Slot* tab = nullptr;
+    DevBuf<Slot> tab;
     uint32_t cap_log2 = 20;
-    SpillEntry* spill = nullptr;
+    DevBuf<SpillEntry> spill;
     // Parked updates that met a full table.  A record parks at most one update, so 2 x max_batch_records (+ slack for
     // the per-workgroup flushes) covers everything the host may have in flight before it looks at the counters again
     // (pre_launch_guard): aggregates are never dropped, the table grows and the parked updates are replayed.
     uint32_t spill_cap = 0;
-    Counters* d_ctr = nullptr;
-    Counters* h_ctr = nullptr;  // pinned
+    DevBuf<Counters> d_ctr;
+    PinnedBuf<Counters> h_ctr;
     // counter snapshots, one per ingest launch (ring): what the device had counted when that launch finished
     static constexpr int NSNAP = 8;
-    Counters* h_snap = nullptr;  // pinned, NSNAP entries
+    PinnedBuf<Counters> h_snap;  // NSNAP entries
     hipEvent_t snap_ev[NSNAP] = {};
     uint64_t snap_records[NSNAP] = {};  // records launched up to and including the snapshot's batch
     uint64_t snap_seq[NSNAP] = {};      // launch sequence number (0 = unused)
     uint64_t launch_seq = 0, known_seq = 0;
     uint64_t launched_records = 0, known_records = 0;
     Counters known{};                   // newest snapshot (or settle) the host has seen
-    uint32_t* d_exotic = nullptr;  // deferral lists: [0,cap) exotic, [cap,2cap) retry
-    size_t exotic_cap = 0;
+    DevBuf<uint32_t> d_exotic;  // deferral lists: [0,cap) exotic, [cap,2cap) retry
+    size_t exotic_cap() const { return d_exotic.bytes() / (2 * sizeof(uint32_t)); }
     // scatter sink
-    uint4* seg = nullptr;
-    size_t seg_bytes = 0;
-    uint32_t* seg_counts = nullptr;
-    size_t seg_counts_cap = 0;
+    DevBuf<uint4> seg;
+    DevBuf<uint32_t> seg_counts;
     // Count-Min scatter sink (sinks.cuh): sketch tuples' segments
-    uint4* cseg = nullptr;
-    size_t cseg_bytes = 0;
-    uint32_t* cseg_counts = nullptr;
-    size_t cseg_counts_cap = 0;
-    HotSeed* hot_seed = nullptr;   // [hot_seed_wgs][CMS_SETS][HOT_SLOTS] entries of the hot-address caches that survive a launch
-    uint32_t* hot_seed_tag = nullptr;
+    DevBuf<uint4> cseg;
+    DevBuf<uint32_t> cseg_counts;
+    DevBuf<HotSeed> hot_seed;   // [hot_seed_wgs][CMS_SETS][HOT_SLOTS] entries of the hot-address caches that survive a launch
+    DevBuf<uint32_t> hot_seed_tag;
     uint32_t hot_seed_wgs = 0, hot_epoch = 0;
     uint32_t cms_par = 0;          // parity of the next cms_agg_kernel launch (its size copies and unit counters)
-    uint32_t* cms_psize = nullptr;  // [2][CMS_SETS * CMS_NPART] tuples per sketch partition, last launch / this launch (cms_agg_kernel: heaviest first)
+    DevBuf<uint32_t> cms_psize;  // [2][CMS_SETS * CMS_NPART] tuples per sketch partition, last launch / this launch (cms_agg_kernel: heaviest first)
     // scatter sink of the (SrcAddr,DstPort,Proto) key set (wagg.cuh)
-    uint4* wseg = nullptr;
-    size_t wseg_bytes = 0;
-    uint32_t* wseg_counts = nullptr;
-    size_t wseg_counts_cap = 0;
+    DevBuf<uint4> wseg;
+    DevBuf<uint32_t> wseg_counts;   // [nparts][nwg] + 4 words: the time base and bucket range of a log chunk
+    static size_t wcounts_cap(const DevBuf<uint32_t>& b) { return b ? b.bytes() / sizeof(uint32_t) - 4 : 0; }  // ... where they start
     int wide_mode = 0;         // env FA_WIDE: 0 adaptive, 1 "atomic" (every update through memory-side atomics), 2 "scatter" (always the scatter sink),
                                // 3 "log": scatter, and the launch's tuples stay in their segments (wlog below) instead of being folded at once
     // ---- wide log (FA_WIDE=log) ----
@@ -94,10 +103,9 @@ struct fa_ctx {
     // the table is rebuilt) the oldest is folded into the table after all (wagg_kernel, or the atomic replay when the
     // table's geometry has changed since).
     struct WChunk {
-        uint4* seg = nullptr;
-        size_t seg_bytes = 0;
-        uint32_t* counts = nullptr;   // [nparts][nwg] (+ 4 words: [counts_cap] = the launch's time base)
-        size_t counts_cap = 0;
+        DevBuf<uint4> seg;            // a chunk owns its two buffers: chunks are moved between wlog, wlog_free and the ctx's current pair, never copied
+        DevBuf<uint32_t> counts;      // [nparts][nwg] (+ 4 words: tail()[0] = the launch's time base)
+        uint32_t* tail() const { return counts + wcounts_cap(counts); }
         uint32_t nwg = 0, wcapq = 0, wplog2 = 0, wmask = 0, wm = 0;  // wm: buckets below it were dropped after this launch
         size_t wregion = 0;
         uint64_t n = 0;               // records of the launch (upper bound of its tuples)
@@ -151,64 +159,47 @@ struct fa_ctx {
     uint32_t plog2 = PART_LOG2_MAX, wgpc_cap = 0;  // experiment knobs (env FA_PLOG2, FA_WGPC)
 
     // host-fed path: pinned staging (double buffered) + device input
-    uint8_t* h_stage[2] = {nullptr, nullptr};
-    size_t h_stage_cap[2] = {0, 0};
+    PinnedBuf<uint8_t> h_stage[2];
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     int stage_cur = 0;
-    uint8_t* d_in[2] = {nullptr, nullptr};
-    size_t d_in_cap[2] = {0, 0};
+    DevBuf<uint8_t> d_in[2];
 
     // SoA projection
-    void* col_block = nullptr;
-    size_t col_cap = 0;
+    DevBuf<> col_block;
     ColumnPtrs cols{};
 
     // window close (rows_host.inc): rows collected out of the device state, merge scratch, merged / ordered rows
-    void* rc_buf = nullptr;          // collected rows (public format, unsorted)
-    size_t rc_cap = 0;
-    void* rw_buf = nullptr;          // port / minute rows (wide-table rows + the dense histogram's entries)
-    size_t rw_cap = 0;
-    void* m_scratch = nullptr;       // sort scratch: 2 key arrays, 4 index arrays, hipcub temporary storage
-    size_t m_scratch_cap = 0;
-    void* m_out[2] = {nullptr, nullptr};  // merged rows; rows in emit order
-    size_t m_out_cap[2] = {0, 0};
-    void* cut_buf = nullptr;         // fa_read_window_app48 into page-locked memory: the window's rows cut in two by key (rows_host.inc)
-    size_t cut_cap = 0;
+    DevBuf<> rc_buf;          // collected rows (public format, unsorted)
+    DevBuf<> rw_buf;          // port / minute rows (wide-table rows + the dense histogram's entries)
+    DevBuf<> m_scratch;       // sort scratch: 2 key arrays, 4 index arrays, hipcub temporary storage
+    DevBuf<> m_out[2];  // merged rows; rows in emit order
+    DevBuf<> cut_buf;         // fa_read_window_app48 into page-locked memory: the window's rows cut in two by key (rows_host.inc)
     hipStream_t copy_stream = nullptr;  // ... the first half's rows leave on it while the second half is sorted
     // contexts with a sketch: the flows_5m tuple aggregation of a launch runs on a stream of its own BESIDE the sketch fold (and the
     // candidates mode's boundary kernels) - it touches neither sketch nor set, they touch neither tuple segments nor table (launch_tiles)
     hipStream_t cand_stream = nullptr;
     hipEvent_t cand_ev[2] = {nullptr, nullptr};  // ingest + second-chance kernels done (main -> side), aggregation done (side -> main)
-    void* fs_scratch = nullptr;      // device-side framing (framing.cuh): block starts, exits, counts, bases, error / trust flags, sub-block entries, counters
-    size_t fs_scratch_cap = 0;
-    void* fs_off = nullptr;          // ... the offsets it produces
-    size_t fs_off_cap = 0;
-    void* wl_scratch = nullptr;      // window reads of log chunks: per-segment counts, their scan, hipcub storage
-    size_t wl_scratch_cap = 0;
+    DevBuf<> fs_scratch;      // device-side framing (framing.cuh): block starts, exits, counts, bases, error / trust flags, sub-block entries, counters
+    DevBuf<> fs_off;          // ... the offsets it produces
+    DevBuf<> wl_scratch;      // window reads of log chunks: per-segment counts, their scan, hipcub storage
     void* read_clk = nullptr;        // FA_VERBOSE: the ReadClock of the read in progress (collect's own phases report into it)
-    void* part_buf = nullptr;        // fa_rows_partition_device: the rows grouped by destination rank
-    size_t part_cap = 0;
-    unsigned int* part_cnt = nullptr;  // [3][RPART_MAX_WORLD]: counts, starts, cursors
+    DevBuf<> part_buf;        // fa_rows_partition_device: the rows grouped by destination rank
+    DevBuf<unsigned int> part_cnt;  // [3][RPART_MAX_WORLD]: counts, starts, cursors
     // fa_group_*: the buffer the group's exchange writes into (peer copies from the other members), owned by the ctx so that it
     // can be reserved where the rows it will hold come into being (reserve_window_read) instead of inside the first close
-    void* xch_buf = nullptr;
-    size_t xch_cap = 0;
+    DevBuf<> xch_buf;
     uint32_t group_members = 0;        // > 0 while the ctx is a member of a group (of that many contexts)
-    void* h_rows = nullptr;          // pinned: rows on their way to the caller
-    size_t h_rows_cap = 0;
+    PinnedBuf<> h_rows;              // rows on their way to the caller
     hipEvent_t copy_ev[2] = {nullptr, nullptr};  // the two halves of h_rows while a large result leaves in pieces (rows_host.inc)
 
-    unsigned long long* cms_src = nullptr;
-    unsigned long long* cms_dst = nullptr;
+    DevBuf<unsigned long long> cms_src, cms_dst;
     size_t cms_words = 0;   // words of ONE copy; the buffers hold CMS_REPLICAS copies
     bool cms_dirty = false;  // copies > 0 may hold counts (cms_fold)
     // merged view (window close across GPUs): all-rank sums of the sketches, filled by fa_merge_allreduce or by the
     // caller's collective (fa_device_state_get + fa_merged_view_set); stale as soon as this ctx ingests again
-    unsigned long long* cms_src_m = nullptr;
-    unsigned long long* cms_dst_m = nullptr;
+    DevBuf<unsigned long long> cms_src_m, cms_dst_m;
     bool merged_valid = false;
-    KeySlot* ks_src = nullptr;  // distinct-address sets (fa_topk)
-    KeySlot* ks_dst = nullptr;
+    DevBuf<KeySlot> ks_src, ks_dst;  // distinct-address sets (fa_topk)
     uint32_t ks_log2 = 20;
     // candidates mode (cfg.topk_mode = FA_TOPK_CANDIDATES; maintenance.cuh "candidates mode"): one bit per sketch counter, rebuilt
     // behind every ingest launch; the sets then hold candidates only
@@ -217,20 +208,20 @@ struct fa_ctx {
     uint32_t tk_lb_bin[2] = {0, 0};
     size_t tk_lb_k[2] = {0, 0};
     bool tk_lb_merged[2] = {false, false};
-    unsigned short* cand_chunkmax = nullptr;  // candidates mode: scratch of the boundary's scan (2 sets)
-    uint32_t* cand_bits[2] = {nullptr, nullptr};
+    DevBuf<unsigned short> cand_chunkmax;  // candidates mode: scratch of the boundary's scan (2 sets)
+    DevBuf<uint32_t> cand_bits[2];
     size_t cand_bits_bytes = 0;
-    CandState* cand_state = nullptr;  // [2]
+    DevBuf<CandState> cand_state;  // [2]
 
     // wide key sets (wide.cuh): one table + the dense port histograms
-    WSlot* wtab = nullptr;
+    DevBuf<WSlot> wtab;
     uint32_t wcap_log2 = 20;
-    WSpillEntry* wspill = nullptr;
+    DevBuf<WSpillEntry> wspill;
     uint32_t wspill_cap = 0;      // (updates a record can park in the wide table) x 2 x max_batch_records + slack
     uint32_t wide_per_record = 0;  // wide-table updates one record can cause (enabled wide key sets)
     uint64_t wused_base = 0;
     uint64_t wide_dead = 0;       // slots of the wide table whose rows a window close zeroed (wdrop_kernel): occupied, but no rows - purged by the next rebuild
-    ulonglong2* port_hist = nullptr;  // [2][PORT_DENSE]
+    DevBuf<ulonglong2> port_hist;  // [2][PORT_DENSE]
 
     struct TalkState* talk = nullptr;  // exact top talkers (fa_talkers_enable; talkers_host.inc), nullptr = not enabled
 
@@ -297,7 +288,7 @@ static KArgs make_args(fa_ctx* c) {
     a.cols = c->cols;
     a.dbg = c->dbg;
     a.tile_recs = BLOCK;
-    a.retry_idx = c->d_exotic ? c->d_exotic + c->exotic_cap : nullptr;
+    a.retry_idx = c->d_exotic ? c->d_exotic + c->exotic_cap() : nullptr;
     a.key_sets = c->cfg.key_sets;
     a.wtab = c->wtab;
     a.wmask = (1u << c->wcap_log2) - 1;
@@ -410,30 +401,30 @@ extern "C" int fa_create(const fa_config* cfg_in, fa_ctx** out) {
             return bail("hipEventCreate", e);
     for (int i = 0; i < fa_ctx::NSNAP; i++)
         if ((e = hipEventCreateWithFlags(&c->snap_ev[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipHostMalloc(&c->h_snap, sizeof(Counters) * fa_ctx::NSNAP)) != hipSuccess) return bail("hipHostMalloc", e);
+    if (!c->h_snap.grow(sizeof(Counters) * fa_ctx::NSNAP)) return bail("hipHostMalloc", hipGetLastError());
     c->spill_cap = 2u * cfg.max_batch_records + (1u << 21);
     c->wide_per_record = ((cfg.key_sets & FA_KEYS_ADDR_PORT_PROTO) ? 1u : 0u) + ((cfg.key_sets & FA_KEYS_PORT_HIST) ? 2u : 0u) +
                          ((cfg.key_sets & FA_KEYS_MINUTE_SERIES) ? 1u : 0u);
     // (capped at 2^25 entries = 1.9 GB: launches that could park more are split, fa_ingest_device)
     c->wspill_cap = (uint32_t)std::min<uint64_t>((uint64_t)c->wide_per_record * 2u * cfg.max_batch_records + (1u << 21), 1u << 25);
     size_t tab_bytes = sizeof(Slot) << c->cap_log2;
-    if ((e = hipMalloc(&c->tab, tab_bytes)) != hipSuccess) return bail("hipMalloc(table)", e);
+    if (!c->tab.grow(tab_bytes)) return bail("hipMalloc(table)", hipGetLastError());
     if ((e = hipMemsetAsync(c->tab, 0, tab_bytes, c->stream)) != hipSuccess) return bail("memset", e);
-    if ((e = hipMalloc(&c->spill, sizeof(SpillEntry) * c->spill_cap)) != hipSuccess)
-        return bail("hipMalloc(spill)", e);
-    if ((e = hipMalloc(&c->d_ctr, sizeof(Counters))) != hipSuccess) return bail("hipMalloc(ctr)", e);
+    if (!c->spill.grow(sizeof(SpillEntry) * c->spill_cap))
+        return bail("hipMalloc(spill)", hipGetLastError());
+    if (!c->d_ctr.grow(sizeof(Counters))) return bail("hipMalloc(ctr)", hipGetLastError());
     if ((e = hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), c->stream)) != hipSuccess)
         return bail("memset", e);
-    if ((e = hipHostMalloc(&c->h_ctr, sizeof(Counters))) != hipSuccess) return bail("hipHostMalloc", e);
+    if (!c->h_ctr.grow(sizeof(Counters))) return bail("hipHostMalloc", hipGetLastError());
     if (cfg.key_sets & (FA_KEYS_SRCADDR_CMS | FA_KEYS_DSTADDR_CMS)) {
         c->cms_words = (size_t)cfg.cms_depth << cfg.cms_width_log2;
         if (cfg.key_sets & FA_KEYS_SRCADDR_CMS) {
-            if ((e = hipMalloc(&c->cms_src, c->cms_words * 8 * CMS_REPLICAS)) != hipSuccess) return bail("hipMalloc(cms)", e);
+            if (!c->cms_src.grow(c->cms_words * 8 * CMS_REPLICAS)) return bail("hipMalloc(cms)", hipGetLastError());
             if ((e = hipMemsetAsync(c->cms_src, 0, c->cms_words * 8 * CMS_REPLICAS, c->stream)) != hipSuccess)
                 return bail("memset", e);
         }
         if (cfg.key_sets & FA_KEYS_DSTADDR_CMS) {
-            if ((e = hipMalloc(&c->cms_dst, c->cms_words * 8 * CMS_REPLICAS)) != hipSuccess) return bail("hipMalloc(cms)", e);
+            if (!c->cms_dst.grow(c->cms_words * 8 * CMS_REPLICAS)) return bail("hipMalloc(cms)", hipGetLastError());
             if ((e = hipMemsetAsync(c->cms_dst, 0, c->cms_words * 8 * CMS_REPLICAS, c->stream)) != hipSuccess)
                 return bail("memset", e);
         }
@@ -447,43 +438,42 @@ extern "C" int fa_create(const fa_config* cfg_in, fa_ctx** out) {
         c->ks_log2 = cfg.topk_capacity_log2;
         const size_t ks_bytes = sizeof(KeySlot) << c->ks_log2;
         if (cfg.key_sets & FA_KEYS_SRCADDR_CMS) {
-            if ((e = hipMalloc(&c->ks_src, ks_bytes)) != hipSuccess) return bail("hipMalloc(key set)", e);
+            if (!c->ks_src.grow(ks_bytes)) return bail("hipMalloc(key set)", hipGetLastError());
             if ((e = hipMemsetAsync(c->ks_src, 0, ks_bytes, c->stream)) != hipSuccess) return bail("memset", e);
         }
         if (cfg.key_sets & FA_KEYS_DSTADDR_CMS) {
-            if ((e = hipMalloc(&c->ks_dst, ks_bytes)) != hipSuccess) return bail("hipMalloc(key set)", e);
+            if (!c->ks_dst.grow(ks_bytes)) return bail("hipMalloc(key set)", hipGetLastError());
             if ((e = hipMemsetAsync(c->ks_dst, 0, ks_bytes, c->stream)) != hipSuccess) return bail("memset", e);
         }
         if (cfg.topk_mode == FA_TOPK_CANDIDATES) {
             c->cand_bits_bytes = std::max<size_t>(c->cms_words / 8, 8) + 8;
             for (int d = 0; d < 2; d++)
                 if (cfg.key_sets & (d ? FA_KEYS_DSTADDR_CMS : FA_KEYS_SRCADDR_CMS)) {
-                    if ((e = hipMalloc(&c->cand_bits[d], c->cand_bits_bytes)) != hipSuccess) return bail("hipMalloc(candidate bits)", e);
+                    if (!c->cand_bits[d].grow(c->cand_bits_bytes)) return bail("hipMalloc(candidate bits)", hipGetLastError());
                     if ((e = hipMemsetAsync(c->cand_bits[d], 0, c->cand_bits_bytes, c->stream)) != hipSuccess) return bail("memset", e);
                 }
-            if ((e = hipMalloc(&c->cand_chunkmax, 2 * ((sizeof(unsigned short) << c->ks_log2 >> 6) + 256))) != hipSuccess) return bail("hipMalloc(candidate scan scratch)", e);
-            if ((e = hipMalloc(&c->cand_state, 2 * sizeof(CandState))) != hipSuccess) return bail("hipMalloc(candidate state)", e);
+            if (!c->cand_chunkmax.grow(2 * ((sizeof(unsigned short) << c->ks_log2 >> 6) + 256))) return bail("hipMalloc(candidate scan scratch)", hipGetLastError());
+            if (!c->cand_state.grow(2 * sizeof(CandState))) return bail("hipMalloc(candidate state)", hipGetLastError());
             if ((e = hipMemsetAsync(c->cand_state, 0, 2 * sizeof(CandState), c->stream)) != hipSuccess) return bail("memset", e);
         }
     }
     if (cfg.key_sets & FA_KEYS_WIDE) {
         c->wcap_log2 = cfg.wide_capacity_log2;
         const size_t wbytes = sizeof(WSlot) << c->wcap_log2;
-        if ((e = hipMalloc(&c->wtab, wbytes)) != hipSuccess) return bail("hipMalloc(wide table)", e);
+        if (!c->wtab.grow(wbytes)) return bail("hipMalloc(wide table)", hipGetLastError());
         if ((e = hipMemsetAsync(c->wtab, 0, wbytes, c->stream)) != hipSuccess) return bail("memset", e);
-        if ((e = hipMalloc(&c->wspill, sizeof(WSpillEntry) * c->wspill_cap)) != hipSuccess) return bail("hipMalloc(wide spill)", e);
+        if (!c->wspill.grow(sizeof(WSpillEntry) * c->wspill_cap)) return bail("hipMalloc(wide spill)", hipGetLastError());
         c->stats.wide_capacity = 1ull << c->wcap_log2;
     }
     if (cfg.key_sets & FA_KEYS_PORT_HIST) {
         const size_t hbytes = sizeof(ulonglong2) * 2 * PORT_DENSE;
-        if ((e = hipMalloc(&c->port_hist, hbytes)) != hipSuccess) return bail("hipMalloc(port histograms)", e);
+        if (!c->port_hist.grow(hbytes)) return bail("hipMalloc(port histograms)", hipGetLastError());
         if ((e = hipMemsetAsync(c->port_hist, 0, hbytes, c->stream)) != hipSuccess) return bail("memset", e);
     }
     {  // pinned staging of window-close rows, sized for the initial table (grows with it): pinning at the first close
        // would cost more than the close itself
         const size_t bytes = std::min<size_t>((size_t)sizeof(Row5m) << c->cap_log2, (size_t)64 << 20);
-        if (hipHostMalloc(&c->h_rows, bytes) == hipSuccess) c->h_rows_cap = bytes;
-        else c->h_rows = nullptr;
+        (void)c->h_rows.grow(bytes);  // (a failure is not an error: ensure_pinned tries again, the copy falls back to a plain hipMemcpy)
     }
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return bail("sync", e);
     c->stats.table_capacity = 1ull << c->cap_log2;
@@ -553,74 +543,24 @@ extern "C" void fa_destroy(fa_ctx* c) {
                     (double)tot / (double)np, mx, (double)mx * (double)np / (double)std::max(1ull, tot), mxseg, (double)tot / (double)(np * c->last_nwg));
         }
     }
-    (void)hipFree(c->tab);
-    (void)hipFree(c->spill);
-    (void)hipFree(c->d_ctr);
-    if (c->h_ctr) (void)hipHostFree(c->h_ctr);
-    if (c->h_snap) (void)hipHostFree(c->h_snap);
     for (int i = 0; i < fa_ctx::NSNAP; i++)
         if (c->snap_ev[i]) (void)hipEventDestroy(c->snap_ev[i]);
-    (void)hipFree(c->d_exotic);
-    (void)hipFree(c->seg);
-    (void)hipFree(c->seg_counts);
-    (void)hipFree(c->cseg);
-    (void)hipFree(c->cseg_counts);
-    (void)hipFree(c->cms_psize);
-    (void)hipFree(c->hot_seed);
-    (void)hipFree(c->hot_seed_tag);
-    (void)hipFree(c->wseg);
-    (void)hipFree(c->wseg_counts);
-    for (auto* v : {&c->wlog, &c->wlog_free})
-        for (auto& k : *v) {
-            (void)hipFree(k.seg);
-            (void)hipFree(k.counts);
-        }
     for (int i = 0; i < 2; i++) {
-        if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
-        (void)hipFree(c->d_in[i]);
         if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]);
         if (c->copy_ev[i]) (void)hipEventDestroy(c->copy_ev[i]);
-    }
-    (void)hipFree(c->col_block);
-    (void)hipFree(c->rc_buf);
-    (void)hipFree(c->rw_buf);
-    (void)hipFree(c->m_scratch);
-    (void)hipFree(c->cut_buf);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->cand_stream) (void)hipStreamDestroy(c->cand_stream);
-    for (int i = 0; i < 2; i++)
         if (c->cand_ev[i]) (void)hipEventDestroy(c->cand_ev[i]);
-    (void)hipFree(c->m_out[0]);
-    (void)hipFree(c->m_out[1]);
-    (void)hipFree(c->fs_scratch);
-    (void)hipFree(c->fs_off);
-    (void)hipFree(c->wl_scratch);
-    (void)hipFree(c->part_buf);
-    (void)hipFree(c->part_cnt);
-    (void)hipFree(c->xch_buf);
-    if (c->h_rows) (void)hipHostFree(c->h_rows);
-    (void)hipFree(c->cms_src);
-    (void)hipFree(c->cms_dst);
-    (void)hipFree(c->cms_src_m);
-    (void)hipFree(c->cms_dst_m);
-    (void)hipFree(c->ks_src);
-    (void)hipFree(c->ks_dst);
-    (void)hipFree(c->cand_bits[0]);
-    (void)hipFree(c->cand_bits[1]);
-    (void)hipFree(c->cand_state);
-    (void)hipFree(c->cand_chunkmax);
-    (void)hipFree(c->wtab);
-    (void)hipFree(c->wspill);
-    (void)hipFree(c->port_hist);
-    talk_destroy(c);
+    }
     for (auto* pool : {&c->ev_pool, &c->dev_pool})
         for (auto& p : *pool) {
             (void)hipEventDestroy(p.e0);
             (void)hipEventDestroy(p.e1);
             (void)hipEventDestroy(p.e2);
         }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    talk_destroy(c);
+    const hipStream_t streams[3] = {c->copy_stream, c->cand_stream, c->stream};
+    delete c;  // every buffer is released here (fa_ctx's members own them): before the streams go, as ever
+    for (hipStream_t s : streams)
+        if (s) (void)hipStreamDestroy(s);
 }
 
 #include "maintain_host.inc"
@@ -656,10 +596,10 @@ extern "C" int fa_stats(fa_ctx* c, fa_stats_t* out) {
     c->stats.wide_log_chunks = c->wlog.size();
     uint64_t lb = 0, lr = 0;
     for (const auto& k : c->wlog) {
-        lb += k.seg_bytes + (k.counts_cap + 4) * sizeof(uint32_t);
+        lb += k.seg.bytes() + k.counts.bytes();
         lr += k.n;
     }
-    for (const auto& k : c->wlog_free) lb += k.seg_bytes + (k.counts_cap + 4) * sizeof(uint32_t);
+    for (const auto& k : c->wlog_free) lb += k.seg.bytes() + k.counts.bytes();
     c->stats.wide_log_bytes = lb;
     c->stats.wide_log_records = lr;
     c->stats.wide_log_recorded = c->wlog_recorded;
@@ -696,40 +636,44 @@ extern "C" int fa_mock_generate_device(fa_ctx* c, const fa_mock_params* g, uint6
     FA_ON_DEVICE(c);
     if (!c || !g || !d_buf || !d_off || n == 0 || n >= (1ull << 31)) return FA_ERR_ARG;
     uint32_t* off = (uint32_t*)d_off;
-    uint32_t* len = nullptr;
-    void* tmp = nullptr;
+    DevBuf<uint32_t> len;
+    DevBuf<> tmp;
     size_t tmp_bytes = 0;
-    HIPCHK(c, hipMalloc(&len, (n + 1) * sizeof(uint32_t) + 16));
-    int rc = FA_OK;
-    bool too_big = false;
-    do {
-        hipLaunchKernelGGL(gen_len_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, *g, i0, (uint32_t)n, len);
-        if (hipMemsetAsync(len + n, 0, 4, c->stream) != hipSuccess) { rc = FA_ERR_HIP; break; }
-        unsigned long long* sum64 = reinterpret_cast<unsigned long long*>(len + ((n + 1 + 1) & ~(uint64_t)1));  // (8-byte aligned, behind the lengths)
-        unsigned long long h_sum = 0;
-        if (hipMemsetAsync(sum64, 0, 8, c->stream) != hipSuccess) { rc = FA_ERR_HIP; break; }
-        hipLaunchKernelGGL(mock_len_sum_kernel, dim3(1024), dim3(256), 0, c->stream, (const uint32_t*)len, (uint32_t)n, sum64);
-        if (hipMemcpyAsync(&h_sum, sum64, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { rc = FA_ERR_HIP; break; }
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = FA_ERR_HIP; break; }
-        if (h_sum >= (1ull << 32) - 64) { rc = FA_ERR_ARG; too_big = true; if (bytes_out) *bytes_out = h_sum; break; }
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, len, off, (int)(n + 1), c->stream);
-        if (hipMalloc(&tmp, tmp_bytes) != hipSuccess) { rc = FA_ERR_NOMEM; break; }
-        if (hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, len, off, (int)(n + 1), c->stream) != hipSuccess) { rc = FA_ERR_HIP; break; }
-        uint32_t total = 0;
-        if (hipMemcpyAsync(&total, off + n, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { rc = FA_ERR_HIP; break; }
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = FA_ERR_HIP; break; }
-        if ((size_t)total + 32 > cap) { rc = FA_ERR_CAPACITY; if (bytes_out) *bytes_out = total; break; }
-        hipLaunchKernelGGL(gen_write_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, *g, i0, (uint32_t)n, off, (uint8_t*)d_buf);
-        if (hipMemsetAsync((uint8_t*)d_buf + total, 0, 32, c->stream) != hipSuccess) { rc = FA_ERR_HIP; break; }
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = FA_ERR_HIP; break; }
+    if (!len.grow((n + 1) * sizeof(uint32_t) + 16)) {
+        c->err = std::string("hipMalloc(&len, (n + 1) * sizeof(uint32_t) + 16): ") + hipGetErrorString(hipGetLastError());
+        return FA_ERR_HIP;
+    }
+    auto hip_failed = [&] {
+        c->err = std::string("fa_mock_generate_device: ") + hipGetErrorString(hipGetLastError());
+        return FA_ERR_HIP;
+    };
+    hipLaunchKernelGGL(gen_len_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, *g, i0, (uint32_t)n, len.get());
+    if (hipMemsetAsync(len + n, 0, 4, c->stream) != hipSuccess) return hip_failed();
+    unsigned long long* sum64 = reinterpret_cast<unsigned long long*>(len + ((n + 1 + 1) & ~(uint64_t)1));  // (8-byte aligned, behind the lengths)
+    unsigned long long h_sum = 0;
+    if (hipMemsetAsync(sum64, 0, 8, c->stream) != hipSuccess) return hip_failed();
+    hipLaunchKernelGGL(mock_len_sum_kernel, dim3(1024), dim3(256), 0, c->stream, (const uint32_t*)len, (uint32_t)n, sum64);
+    if (hipMemcpyAsync(&h_sum, sum64, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return hip_failed();
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return hip_failed();
+    if (h_sum >= (1ull << 32) - 64) {
+        if (bytes_out) *bytes_out = h_sum;
+        return fail(c, FA_ERR_ARG, "fa_mock_generate_device: 4 GiB or more of records in one call (device offsets are 32-bit): generate fewer records per call");
+    }
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, len.get(), off, (int)(n + 1), c->stream);
+    if (!tmp.grow(tmp_bytes)) return FA_ERR_NOMEM;
+    if (hipcub::DeviceScan::ExclusiveSum(tmp.get(), tmp_bytes, len.get(), off, (int)(n + 1), c->stream) != hipSuccess) return hip_failed();
+    uint32_t total = 0;
+    if (hipMemcpyAsync(&total, off + n, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return hip_failed();
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return hip_failed();
+    if ((size_t)total + 32 > cap) {
         if (bytes_out) *bytes_out = total;
-    } while (0);
-    (void)hipFree(len);
-    (void)hipFree(tmp);
-    if (rc == FA_ERR_HIP) c->err = std::string("fa_mock_generate_device: ") + hipGetErrorString(hipGetLastError());
-    if (rc == FA_ERR_CAPACITY) c->err = "fa_mock_generate_device: buffer too small (needs bytes + 32 slack)";
-    if (too_big) c->err = "fa_mock_generate_device: 4 GiB or more of records in one call (device offsets are 32-bit): generate fewer records per call";
-    return rc;
+        return fail(c, FA_ERR_CAPACITY, "fa_mock_generate_device: buffer too small (needs bytes + 32 slack)");
+    }
+    hipLaunchKernelGGL(gen_write_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, *g, i0, (uint32_t)n, off, (uint8_t*)d_buf);
+    if (hipMemsetAsync((uint8_t*)d_buf + total, 0, 32, c->stream) != hipSuccess) return hip_failed();
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return hip_failed();
+    if (bytes_out) *bytes_out = total;
+    return FA_OK;
 }
 
 extern "C" int fa_mock_generate_host(const fa_mock_params* g, uint64_t i0, uint64_t n, uint8_t* buf, size_t cap,

@@ -191,7 +191,7 @@ static int group_each(fa_group* g, const char* what, F f) {
 static int group_recv(fa_group* g, size_t r, size_t bytes) {
     fa_ctx* c = g->m[r];
     (void)hipSetDevice(c->cfg.device);
-    return ensure_dev(c, &c->xch_buf, &c->xch_cap, std::max<size_t>(bytes, 256), "group exchange buffer");
+    return ensure_dev(c, c->xch_buf, std::max<size_t>(bytes, 256), "group exchange buffer");
 }
 // `bytes` from member p's HBM into member r's, queued on r's stream: a plain device copy when both live on one GPU, a peer
 // copy otherwise (xGMI when the peers can reach each other - enabled at fa_group_create -, staged by the runtime when not)
@@ -305,7 +305,7 @@ extern "C" int fa_group_create(fa_ctx* const* ctxs, size_t n, uint32_t flags, fa
             (void)ensure_merged_view(c);
             if (g->transport == FA_GROUP_PEER) {
                 const size_t slice = ((c->cms_words + n - 1) / n + 1) & ~(size_t)1;
-                (void)ensure_dev(c, &c->xch_buf, &c->xch_cap, (n - 1) * slice * 8, "group exchange buffer");
+                (void)ensure_dev(c, c->xch_buf, (n - 1) * slice * 8, "group exchange buffer");
             }
         }
         if (n > 1 && c->wtab && (c->cfg.key_sets & FA_KEYS_ADDR_PORT_PROTO)) {
@@ -395,8 +395,8 @@ static int group_allreduce(fa_group* g) {
         }
         for (int d = 0; d < 2; d++) {
             if (!(d ? c0->cms_dst : c0->cms_src)) continue;
-            auto own = [&](size_t i) { return d ? g->m[i]->cms_dst : g->m[i]->cms_src; };
-            auto mv = [&](size_t i) { return d ? g->m[i]->cms_dst_m : g->m[i]->cms_src_m; };
+            auto own = [&](size_t i) -> unsigned long long* { return d ? g->m[i]->cms_dst : g->m[i]->cms_src; };
+            auto mv = [&](size_t i) -> unsigned long long* { return d ? g->m[i]->cms_dst_m : g->m[i]->cms_src_m; };
             for (size_t r = 0; r < n; r++) {  // reduce-scatter: member r sums slice r
                 const size_t lo = std::min(words, r * slice), w = std::min(words, lo + slice) - lo;
                 if (!w) continue;

@@ -121,7 +121,7 @@ static int launch_tiles(fa_ctx* c, KArgs& a, int grid, fa_ctx::LaunchEvents* ev 
         if (MODE == MODE_INGEST && wave_tiles && a.wseg) {
             if (c->wlog_now) {  // log mode: the tuples stay where they are (the chunk is taken over behind the launch: wlog_record)
                 // (the time base and the tuples' bucket range, three words: Counters::tb_base, wtb_min, wtb_nmax)
-                HIPCHK(c, hipMemcpyAsync(c->wseg_counts + c->wseg_counts_cap, &c->d_ctr->tb_base, 3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipMemcpyAsync(c->wseg_counts + fa_ctx::wcounts_cap(c->wseg_counts), &c->d_ctr->tb_base, 3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
             } else {
                 hipLaunchKernelGGL(wagg_kernel, dim3(1u << a.wplog2), dim3(WAGG_BLOCK), 0, c->stream, a, (const uint32_t*)nullptr, 0u);
             }
@@ -157,14 +157,10 @@ static int tile_grid(fa_ctx* c, uint32_t n, uint32_t tile_recs) {
 
 // deferral lists for n records: exotic [0,cap) and retry [cap,2cap)
 static int ensure_exotic(fa_ctx* c, size_t n) {
-    if (c->exotic_cap >= n) return FA_OK;
+    if (c->exotic_cap() >= n) return FA_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_exotic);
-    c->d_exotic = nullptr;
-    size_t cap = std::max<size_t>(n, 1 << 16);
-    if (hipMalloc(&c->d_exotic, 2 * cap * sizeof(uint32_t)) != hipSuccess)
-        return fail(c, FA_ERR_NOMEM, "hipMalloc(deferral lists) failed");
-    c->exotic_cap = cap;
+    const size_t cap = std::max<size_t>(n, 1 << 16);
+    if (!c->d_exotic.grow(2 * n * sizeof(uint32_t), 2 * cap * sizeof(uint32_t))) return fail(c, FA_ERR_NOMEM, "hipMalloc(deferral lists) failed");
     return FA_OK;
 }
 
@@ -180,22 +176,14 @@ static int ensure_segments(fa_ctx* c, size_t n, uint32_t nwg, bool t8, KArgs& a)
     if (c->seg_cap_limit) capq = std::max<uint32_t>(std::min(capq, c->seg_cap_limit) & ~(tpl - 1), 2 * tpl);  // (tests: force the segment-overflow fallbacks)
     const size_t region = (size_t)nwg * capq + 3 * tpl;
     const size_t bytes = region * NPART * (t8 ? 8 : 16);
-    if (c->seg_bytes < bytes) {
+    if (c->seg.bytes() < bytes) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->seg);
-        c->seg = nullptr;
-        c->seg_bytes = 0;
-        if (hipMalloc(&c->seg, bytes) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(tuple segments) failed");
-        c->seg_bytes = bytes;
+        if (!c->seg.grow(bytes)) return fail(c, FA_ERR_NOMEM, "hipMalloc(tuple segments) failed");
     }
     const size_t ncnt = (size_t)nwg * NPART_MAX * 2;  // front and back counts
-    if (c->seg_counts_cap < ncnt) {
+    if (c->seg_counts.bytes() < ncnt * sizeof(uint32_t)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->seg_counts);
-        c->seg_counts = nullptr;
-        c->seg_counts_cap = 0;
-        if (hipMalloc(&c->seg_counts, ncnt * sizeof(uint32_t)) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(segment counts) failed");
-        c->seg_counts_cap = ncnt;
+        if (!c->seg_counts.grow(ncnt * sizeof(uint32_t))) return fail(c, FA_ERR_NOMEM, "hipMalloc(segment counts) failed");
     }
     a.seg = c->seg;
     a.seg_counts = c->seg_counts;
@@ -222,33 +210,20 @@ static int ensure_csegments(fa_ctx* c, size_t n, uint32_t nwg, KArgs& a) {
     if (c->seg_cap_limit) capq = std::max<uint32_t>(std::min(capq, c->seg_cap_limit) & ~3u, 32u);  // (tests: force the overflow fallbacks)
     const size_t region = (size_t)nwg * capq + 12;
     const size_t bytes = region * nparts * sizeof(uint4);
-    if (c->cseg_bytes < bytes) {
+    if (c->cseg.bytes() < bytes) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->cseg);
-        c->cseg = nullptr;
-        c->cseg_bytes = 0;
-        if (hipMalloc(&c->cseg, bytes) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(sketch tuple segments) failed");
-        c->cseg_bytes = bytes;
+        if (!c->cseg.grow(bytes)) return fail(c, FA_ERR_NOMEM, "hipMalloc(sketch tuple segments) failed");
     }
     const size_t ncnt = (size_t)nwg * nparts * 2;
-    if (c->cseg_counts_cap < ncnt) {
+    if (c->cseg_counts.bytes() < ncnt * sizeof(uint32_t)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->cseg_counts);
-        c->cseg_counts = nullptr;
-        c->cseg_counts_cap = 0;
-        if (hipMalloc(&c->cseg_counts, ncnt * sizeof(uint32_t)) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(sketch segment counts) failed");
-        c->cseg_counts_cap = ncnt;
+        if (!c->cseg_counts.grow(ncnt * sizeof(uint32_t))) return fail(c, FA_ERR_NOMEM, "hipMalloc(sketch segment counts) failed");
     }
     if (c->hot_seed_wgs < nwg) {  // the hot-address caches' surviving entries, one set per workgroup (sinks.cuh, HotAddrs)
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->hot_seed);
-        (void)hipFree(c->hot_seed_tag);
-        c->hot_seed = nullptr;
-        c->hot_seed_tag = nullptr;
         c->hot_seed_wgs = 0;
         const size_t ne = (size_t)nwg * CMS_SETS * HOT_SLOTS;
-        if (hipMalloc(&c->hot_seed, ne * sizeof(HotSeed)) != hipSuccess || hipMalloc(&c->hot_seed_tag, ne * sizeof(uint32_t)) != hipSuccess)
-            return fail(c, FA_ERR_NOMEM, "hipMalloc(hot-address seeds) failed");
+        if (!c->hot_seed.grow(ne * sizeof(HotSeed)) || !c->hot_seed_tag.grow(ne * sizeof(uint32_t))) return fail(c, FA_ERR_NOMEM, "hipMalloc(hot-address seeds) failed");
         HIPCHK(c, hipMemsetAsync(c->hot_seed_tag, 0, ne * sizeof(uint32_t), c->stream));
         c->hot_seed_wgs = nwg;
     }
@@ -257,7 +232,7 @@ static int ensure_csegments(fa_ctx* c, size_t n, uint32_t nwg, KArgs& a) {
     a.hot_epoch = c->hot_epoch++;
     if (!c->cms_psize) {
         const size_t bytes = (2 * (size_t)CMS_SETS * CMS_NPART + 2) * sizeof(uint32_t);  // (+ the two unit counters)
-        if (hipMalloc(&c->cms_psize, bytes) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(sketch partition sizes) failed");
+        if (!c->cms_psize.grow(bytes)) return fail(c, FA_ERR_NOMEM, "hipMalloc(sketch partition sizes) failed");
         HIPCHK(c, hipMemsetAsync(c->cms_psize, 0, bytes, c->stream));
     }
     a.cms_psize = c->cms_psize;
@@ -288,32 +263,20 @@ static int ensure_wsegments(fa_ctx* c, size_t n, uint32_t nwg, KArgs& a) {
     auto held = [&]() { return (uint32_t)((c->wseg || c->wseg_counts ? 1 : 0) + c->wlog.size() + c->wlog_free.size()); };
     for (;;) {
         if (!c->wseg && !c->wseg_counts && !c->wlog_free.empty()) {  // the buffers of a chunk that has been folded or dropped
-            const fa_ctx::WChunk k = c->wlog_free.back();
+            c->wseg = std::move(c->wlog_free.back().seg);
+            c->wseg_counts = std::move(c->wlog_free.back().counts);
             c->wlog_free.pop_back();
-            c->wseg = k.seg;
-            c->wseg_bytes = k.seg_bytes;
-            c->wseg_counts = k.counts;
-            c->wseg_counts_cap = k.counts_cap;
         }
         bool ok = true;
-        if (c->wseg_bytes < bytes || c->wseg_counts_cap < ncnt) {
+        if (c->wseg.bytes() < bytes || fa_ctx::wcounts_cap(c->wseg_counts) < ncnt) {
             HIPCHK(c, hipStreamSynchronize(c->stream));  // (a recycled pair may still be read by its chunk's fold)
-            (void)hipFree(c->wseg);
-            (void)hipFree(c->wseg_counts);
-            c->wseg = nullptr;
-            c->wseg_counts = nullptr;
-            c->wseg_bytes = c->wseg_counts_cap = 0;
-            ok = !(c->wseg_budget && held() + 1u > c->wseg_budget) && hipMalloc(&c->wseg, bytes) == hipSuccess;
-            if (ok) {
-                c->wseg_bytes = bytes;
-                ok = hipMalloc(&c->wseg_counts, (ncnt + 4) * sizeof(uint32_t)) == hipSuccess;  // (+ the time base and minimum bucket words of a log chunk)
-                if (ok) c->wseg_counts_cap = ncnt;
-            }
+            c->wseg.reset();  // (both go, so that the pair no longer counts as held)
+            c->wseg_counts.reset();
+            ok = !(c->wseg_budget && held() + 1u > c->wseg_budget) && c->wseg.grow(bytes) &&
+                 c->wseg_counts.grow((ncnt + 4) * sizeof(uint32_t));  // (+ the time base and minimum bucket words of a log chunk)
             if (!ok) {
                 (void)hipGetLastError();
-                (void)hipFree(c->wseg);
-                c->wseg = nullptr;
-                c->wseg_bytes = 0;
+                c->wseg.reset();
             }
         }
         if (ok) break;
@@ -331,7 +294,7 @@ static int ensure_wsegments(fa_ctx* c, size_t n, uint32_t nwg, KArgs& a) {
     return FA_OK;
 }
 
-static int ensure_dev(fa_ctx* c, void** p, size_t* cap, size_t bytes, const char* what);
+static int ensure_dev(fa_ctx* c, DevBuf<>& b, size_t bytes, const char* what);
 static int frame_split_host(const uint8_t* buf, size_t len, std::vector<uint64_t>& off);
 // Device-side framing (framing.cuh): d_buf[0, len) is a chain of varint(len)-framed records -> *d_off = n + 1 offsets in HBM
 // (owned by the ctx, valid until the next split), *n_out = records.  FA_ERR_FRAMING when it is not such a chain.
@@ -346,7 +309,7 @@ static int frame_split_device(fa_ctx* c, const uint8_t* d_buf, size_t len, const
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)nb, c->stream);
     const size_t arr = ((size_t)nb * 4 + 255) & ~(size_t)255;
     const size_t ent_bytes = ((size_t)nb * FS_NSUB + 255) & ~(size_t)255;
-    int rc = ensure_dev(c, &c->fs_scratch, &c->fs_scratch_cap, 11 * arr + ent_bytes + tmp_scan + 512, "framing scratch");
+    int rc = ensure_dev(c, c->fs_scratch, 11 * arr + ent_bytes + tmp_scan + 512, "framing scratch");
     if (rc) return rc;
     uint8_t* base = (uint8_t*)c->fs_scratch;
     uint32_t* start = (uint32_t*)base;
@@ -398,7 +361,7 @@ static int frame_split_device(fa_ctx* c, const uint8_t* d_buf, size_t len, const
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (bad) return fail(c, FA_ERR_FRAMING, "stream is not a chain of varint-framed records");
         const size_t n = (size_t)last[0] + last[1];
-        rc = ensure_dev(c, &c->fs_off, &c->fs_off_cap, (n + 1) * sizeof(uint32_t), "frame offsets");
+        rc = ensure_dev(c, c->fs_off, (n + 1) * sizeof(uint32_t), "frame offsets");
         if (rc) return rc;
         hipLaunchKernelGGL(fs_emit_kernel, dim3((nb + 3) / 4), dim3(256), 0, c->stream, d_buf, (uint32_t)len, nb, (const uint8_t*)ent8, (const unsigned long long*)present,
                            (const uint32_t*)bases, (uint32_t*)c->fs_off, (uint32_t)n);
@@ -418,7 +381,7 @@ static int frame_split_device(fa_ctx* c, const uint8_t* d_buf, size_t len, const
     rc = frame_split_host(h_buf, len, off64);
     if (rc) return fail(c, rc, "stream is not a chain of varint-framed records");
     h_off.assign(off64.begin(), off64.end());
-    rc = ensure_dev(c, &c->fs_off, &c->fs_off_cap, h_off.size() * sizeof(uint32_t), "frame offsets");
+    rc = ensure_dev(c, c->fs_off, h_off.size() * sizeof(uint32_t), "frame offsets");
     if (rc) return rc;
     HIPCHK(c, hipMemcpy(c->fs_off, h_off.data(), h_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     *d_off = (const uint32_t*)c->fs_off;
@@ -645,20 +608,9 @@ static int frame_split_host(const uint8_t* buf, size_t len, std::vector<uint64_t
 }
 
 static int ensure_stage(fa_ctx* c, int s, size_t bytes) {
-    if (c->h_stage_cap[s] < bytes) {
-        if (c->h_stage[s]) (void)hipHostFree(c->h_stage[s]);
-        c->h_stage[s] = nullptr;
-        size_t cap = std::max<size_t>(bytes + bytes / 4, 1 << 20);
-        if (hipHostMalloc(&c->h_stage[s], cap) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipHostMalloc(staging) failed");
-        c->h_stage_cap[s] = cap;
-    }
-    if (c->d_in_cap[s] < bytes) {
-        (void)hipFree(c->d_in[s]);
-        c->d_in[s] = nullptr;
-        size_t cap = std::max<size_t>(bytes + bytes / 4, 1 << 20);
-        if (hipMalloc(&c->d_in[s], cap) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(input) failed");
-        c->d_in_cap[s] = cap;
-    }
+    const size_t cap = std::max<size_t>(bytes + bytes / 4, 1 << 20);
+    if (!c->h_stage[s].grow(bytes, cap)) return fail(c, FA_ERR_NOMEM, "hipHostMalloc(staging) failed");
+    if (!c->d_in[s].grow(bytes, cap)) return fail(c, FA_ERR_NOMEM, "hipMalloc(input) failed");
     return FA_OK;
 }
 
@@ -782,7 +734,7 @@ extern "C" int fa_reserve_ingest(fa_ctx* c, size_t bytes, size_t records) {
         HIPCHK(c, hipEventSynchronize(c->stage_ev[s]));
         int rc = ensure_stage(c, s, total);
         if (rc) return rc;
-        memset(c->h_stage[s], 0, std::min<size_t>(total, c->h_stage_cap[s]));  // (first touch of the pinned pages: here, not in the loop)
+        memset(c->h_stage[s], 0, std::min<size_t>(total, c->h_stage[s].bytes()));  // (first touch of the pinned pages: here, not in the loop)
     }
     return records ? ensure_exotic(c, records) : FA_OK;
 }

@@ -3,25 +3,23 @@
 // ---- table maintenance -------------------------------------------------------------
 // Builds a fresh table of 2^new_log2 slots holding every row outside [tb_lo,tb_hi).
 static int rebuild_table(fa_ctx* c, uint32_t new_log2, uint32_t tb_lo, uint32_t tb_hi) {
-    Slot* nt = nullptr;
+    DevBuf<Slot> nt;
     size_t bytes = sizeof(Slot) << new_log2;
-    hipError_t e = hipMalloc(&nt, bytes);
-    if (e != hipSuccess) return fail(c, FA_ERR_NOMEM, "rebuild_table: hipMalloc failed");
+    if (!nt.grow(bytes)) return fail(c, FA_ERR_NOMEM, "rebuild_table: hipMalloc failed");
+    hipError_t e;
     if ((e = hipMemsetAsync(nt, 0, bytes, c->stream)) != hipSuccess ||
         (e = hipMemsetAsync(&c->d_ctr->used, 0, sizeof(unsigned long long), c->stream)) != hipSuccess) {
-        (void)hipFree(nt);  // the old table stays in place
-        c->err = std::string("rebuild_table: ") + hipGetErrorString(e);
+        c->err = std::string("rebuild_table: ") + hipGetErrorString(e);  // (the old table stays in place)
         return FA_ERR_HIP;
     }
-    Slot* old = c->tab;
+    DevBuf<Slot> old = std::move(c->tab);  // released on every way out of here, after the kernel that reads it
+    c->tab = std::move(nt);
     uint32_t old_slots = 1u << c->cap_log2;
-    c->tab = nt;
     c->cap_log2 = new_log2;
     KArgs a = make_args(c);
-    hipLaunchKernelGGL(rebuild_kernel, dim3(1024), dim3(256), 0, c->stream, old, old_slots, tb_lo, tb_hi, a);
+    hipLaunchKernelGGL(rebuild_kernel, dim3(1024), dim3(256), 0, c->stream, old.get(), old_slots, tb_lo, tb_hi, a);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(old));
     c->used_base = 0;
     c->stats.table_capacity = 1ull << c->cap_log2;
     return FA_OK;
@@ -30,25 +28,23 @@ static int rebuild_table(fa_ctx* c, uint32_t new_log2, uint32_t tb_lo, uint32_t 
 // Wide table: fresh table of 2^new_log2 slots holding every row that is not selected by
 // (kind_mask, [tb_lo,tb_hi)) - see wrow_selected().
 static int rebuild_wide(fa_ctx* c, uint32_t new_log2, uint32_t kind_mask, uint32_t tb_lo, uint32_t tb_hi) {
-    WSlot* nt = nullptr;
+    DevBuf<WSlot> nt;
     size_t bytes = sizeof(WSlot) << new_log2;
-    if (hipMalloc(&nt, bytes) != hipSuccess) return fail(c, FA_ERR_NOMEM, "rebuild_wide: hipMalloc failed");
+    if (!nt.grow(bytes)) return fail(c, FA_ERR_NOMEM, "rebuild_wide: hipMalloc failed");
     hipError_t e;
     if ((e = hipMemsetAsync(nt, 0, bytes, c->stream)) != hipSuccess ||
         (e = hipMemsetAsync(&c->d_ctr->wused, 0, sizeof(unsigned long long), c->stream)) != hipSuccess) {
-        (void)hipFree(nt);  // the old table stays in place
-        c->err = std::string("rebuild_wide: ") + hipGetErrorString(e);
+        c->err = std::string("rebuild_wide: ") + hipGetErrorString(e);  // (the old table stays in place)
         return FA_ERR_HIP;
     }
-    WSlot* old = c->wtab;
+    DevBuf<WSlot> old = std::move(c->wtab);  // released on every way out of here, after the kernel that reads it
+    c->wtab = std::move(nt);
     uint32_t old_slots = 1u << c->wcap_log2;
-    c->wtab = nt;
     c->wcap_log2 = new_log2;
     KArgs a = make_args(c);
-    hipLaunchKernelGGL(wrebuild_kernel, dim3(1024), dim3(256), 0, c->stream, old, old_slots, kind_mask, tb_lo, tb_hi, a);
+    hipLaunchKernelGGL(wrebuild_kernel, dim3(1024), dim3(256), 0, c->stream, old.get(), old_slots, kind_mask, tb_lo, tb_hi, a);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(old));
     c->wused_base = 0;
     c->wide_dead = 0;  // (slots without rows were not carried over)
     c->stats.wide_capacity = 1ull << c->wcap_log2;
@@ -80,21 +76,19 @@ static int settle_wide(fa_ctx* c, Counters& h) {
         const uint32_t nspill = h.wspill_count;
         // the parked updates move to a private copy and the buffer is emptied BEFORE the rebuild, so that anything the
         // rebuild or the replay parks again is kept for the next round of this loop
-        WSpillEntry* tmp = nullptr;
+        DevBuf<WSpillEntry> tmp;
         if (nspill) {
-            if (hipMalloc(&tmp, sizeof(WSpillEntry) * nspill) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(wide spill copy) failed");
-            hipError_t e = hipMemcpyAsync(tmp, c->wspill, sizeof(WSpillEntry) * nspill, hipMemcpyDeviceToDevice, c->stream);
-            if (e != hipSuccess) { (void)hipFree(tmp); c->err = "settle_wide: copy failed"; return FA_ERR_HIP; }
+            if (!tmp.grow(sizeof(WSpillEntry) * nspill)) return fail(c, FA_ERR_NOMEM, "hipMalloc(wide spill copy) failed");
+            if (hipMemcpyAsync(tmp, c->wspill, sizeof(WSpillEntry) * nspill, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return fail(c, FA_ERR_HIP, "settle_wide: copy failed");
         }
         hipError_t e0 = hipMemsetAsync(&c->d_ctr->wspill_count, 0, sizeof(unsigned int), c->stream);
         int rc = e0 == hipSuccess ? rebuild_wide(c, want, 0, 0, 0 /* nothing selected: keep everything */) : FA_ERR_HIP;
         if (rc == FA_OK && nspill) {
             KArgs a = make_args(c);
             static_assert(sizeof(WSpillEntry) == sizeof(WRow), "spill entries replay as rows");
-            hipLaunchKernelGGL(wmerge_kernel, dim3(256), dim3(256), 0, c->stream, (const WRow*)tmp, nspill, a);
+            hipLaunchKernelGGL(wmerge_kernel, dim3(256), dim3(256), 0, c->stream, (const WRow*)tmp.get(), nspill, a);
             if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = FA_ERR_HIP;
         }
-        if (tmp) (void)hipFree(tmp);
         if (rc) return rc == FA_ERR_HIP ? fail(c, FA_ERR_HIP, "settle_wide: replay failed") : rc;
         HIPCHK(c, hipMemcpy(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost));
         h = *c->h_ctr;
@@ -212,20 +206,18 @@ static int settle(fa_ctx* c) {
         const uint32_t nspill = h.spill_count;
         // the parked aggregates move to a private copy and the buffer is emptied BEFORE the rebuild, so that anything
         // the rebuild or the replay parks again is kept for the next round of this loop
-        SpillEntry* tmp = nullptr;
+        DevBuf<SpillEntry> tmp;
         if (nspill) {
-            if (hipMalloc(&tmp, sizeof(SpillEntry) * nspill) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(spill copy) failed");
-            hipError_t e = hipMemcpyAsync(tmp, c->spill, sizeof(SpillEntry) * nspill, hipMemcpyDeviceToDevice, c->stream);
-            if (e != hipSuccess) { (void)hipFree(tmp); c->err = "settle: copy failed"; return FA_ERR_HIP; }
+            if (!tmp.grow(sizeof(SpillEntry) * nspill)) return fail(c, FA_ERR_NOMEM, "hipMalloc(spill copy) failed");
+            if (hipMemcpyAsync(tmp, c->spill, sizeof(SpillEntry) * nspill, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return fail(c, FA_ERR_HIP, "settle: copy failed");
         }
         hipError_t e0 = hipMemsetAsync(&c->d_ctr->spill_count, 0, sizeof(unsigned int), c->stream);
         int rc = e0 == hipSuccess ? rebuild_table(c, want, 1, 0 /* empty range: keep everything */) : FA_ERR_HIP;
         if (rc == FA_OK && nspill) {
             KArgs a = make_args(c);
-            hipLaunchKernelGGL(replay_spill_kernel, dim3(1024), dim3(256), 0, c->stream, tmp, nspill, a);
+            hipLaunchKernelGGL(replay_spill_kernel, dim3(1024), dim3(256), 0, c->stream, tmp.get(), nspill, a);
             if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = FA_ERR_HIP;
         }
-        if (tmp) (void)hipFree(tmp);
         if (rc) return rc == FA_ERR_HIP ? fail(c, FA_ERR_HIP, "settle: replay failed") : rc;
         HIPCHK(c, hipMemcpy(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost));
         h = *c->h_ctr;
@@ -243,7 +235,7 @@ static int settle(fa_ctx* c) {
 
 // ---- wide log (FA_WIDE=log; fa_ctx::wlog) -----------------------------------------------------------------------------
 static WChunkArgs wchunk_args(const fa_ctx::WChunk& k) {
-    return WChunkArgs{k.seg, k.counts, k.counts + k.counts_cap, 1u << k.wplog2, k.nwg, k.wcapq, k.wm, k.wregion};
+    return WChunkArgs{k.seg, k.counts, k.tail(), 1u << k.wplog2, k.nwg, k.wcapq, k.wm, k.wregion};
 }
 // room in the table for `more` new rows at <= 50 % load (host-side bound first; a settle - and a one-step growth - only when
 // the bound says so)
@@ -262,7 +254,7 @@ static int wlog_make_room(fa_ctx* c, uint64_t more) {
 }
 // one pending chunk into the table: wagg_kernel while the table still has the geometry the tuples were scattered for (its
 // workgroups own "their" regions' tuples), the atomic replay otherwise; the buffers go to the free list
-static int wlog_fold(fa_ctx* c, const fa_ctx::WChunk& k) {
+static int wlog_fold(fa_ctx* c, fa_ctx::WChunk k) {
     KArgs a = make_args(c);
     if (k.wplog2 == a.wplog2 && k.wmask == a.wmask) {
         a.wseg = k.seg;
@@ -270,7 +262,7 @@ static int wlog_fold(fa_ctx* c, const fa_ctx::WChunk& k) {
         a.nwg = k.nwg;
         a.wcapq = k.wcapq;
         a.wregion = k.wregion;
-        hipLaunchKernelGGL(wagg_kernel, dim3(1u << a.wplog2), dim3(WAGG_BLOCK), 0, c->stream, a, (const uint32_t*)(k.counts + k.counts_cap), k.wm);
+        hipLaunchKernelGGL(wagg_kernel, dim3(1u << a.wplog2), dim3(WAGG_BLOCK), 0, c->stream, a, (const uint32_t*)k.tail(), k.wm);
         c->wlog_folded++;
     } else {
         hipLaunchKernelGGL(wlog_replay_kernel, dim3(2048), dim3(256), 0, c->stream, wchunk_args(k), a);
@@ -278,15 +270,15 @@ static int wlog_fold(fa_ctx* c, const fa_ctx::WChunk& k) {
     }
     HIPCHK(c, hipGetLastError());
     c->wpot_total += k.n;
-    c->wlog_free.push_back(k);
+    c->wlog_free.push_back(std::move(k));
     return FA_OK;
 }
 static int wlog_flush_oldest(fa_ctx* c) {
-    const fa_ctx::WChunk k = c->wlog.front();
-    int rc = wlog_make_room(c, k.n);
+    int rc = wlog_make_room(c, c->wlog.front().n);
     if (rc) return rc;
+    fa_ctx::WChunk k = std::move(c->wlog.front());
     c->wlog.erase(c->wlog.begin());
-    return wlog_fold(c, k);
+    return wlog_fold(c, std::move(k));
 }
 static int wlog_flush_all(fa_ctx* c) {
     while (!c->wlog.empty()) {
@@ -300,25 +292,20 @@ static int wlog_flush_all(fa_ctx* c) {
 static void reserve_window_read(fa_ctx* c, uint64_t rows, uint32_t nseg);  // (rows_host.inc)
 static int wlog_record(fa_ctx* c, const KArgs& a, size_t n) {
     fa_ctx::WChunk k;
-    k.seg = c->wseg;
-    k.seg_bytes = c->wseg_bytes;
-    k.counts = c->wseg_counts;
-    k.counts_cap = c->wseg_counts_cap;
+    k.seg = std::move(c->wseg);
+    k.counts = std::move(c->wseg_counts);
     k.nwg = a.nwg;
     k.wcapq = a.wcapq;
     k.wplog2 = a.wplog2;
     k.wmask = a.wmask;
     k.wregion = a.wregion;
     k.n = n;
-    c->wlog.push_back(k);
+    const uint32_t nseg = (1u << k.wplog2) * k.nwg;
+    c->wlog.push_back(std::move(k));
     c->wlog_recorded++;
     // a window of this key set is about a chunk's worth of rows (Kafka partitions are close to time-ordered): what its read
     // will allocate is allocated here, outside the close
-    reserve_window_read(c, c->stats.wide_used + n + n / 16, (1u << k.wplog2) * k.nwg);
-    c->wseg = nullptr;
-    c->wseg_bytes = 0;
-    c->wseg_counts = nullptr;
-    c->wseg_counts_cap = 0;
+    reserve_window_read(c, c->stats.wide_used + n + n / 16, nseg);
     while (c->wlog.size() > c->wlog_max) {
         int rc = wlog_flush_oldest(c);
         if (rc) return rc;
@@ -341,13 +328,13 @@ static int wlog_bucket_ranges(fa_ctx* c) {
     const bool check = getenv("FA_WLOG_RANGE_CHECK") != nullptr;
     std::vector<uint32_t> mm(2 * c->wlog.size()), scan(2 * c->wlog.size());
     for (size_t i = 0; i < c->wlog.size(); i++)
-        if (!c->wlog[i].minb_known) HIPCHK(c, hipMemcpyAsync(&mm[2 * i], c->wlog[i].counts + c->wlog[i].counts_cap + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (!c->wlog[i].minb_known) HIPCHK(c, hipMemcpyAsync(&mm[2 * i], c->wlog[i].tail() + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (check) {
         for (size_t i = 0; i < c->wlog.size(); i++) {
             fa_ctx::WChunk& k = c->wlog[i];
             if (k.minb_known) continue;
-            uint32_t* word = k.counts + k.counts_cap + 1;  // (scanned over the kernel's words: they are on the host by now)
+            uint32_t* word = k.tail() + 1;  // (scanned over the kernel's words: they are on the host by now)
             HIPCHK(c, hipMemsetAsync(word, 0xff, sizeof(uint32_t), c->stream));
             HIPCHK(c, hipMemsetAsync(word + 1, 0, sizeof(uint32_t), c->stream));
             hipLaunchKernelGGL(wlog_minbucket_kernel, dim3(2048), dim3(256), 0, c->stream, wchunk_args(k), word);
@@ -384,7 +371,7 @@ static int wlog_drop(fa_ctx* c, uint32_t lo, uint32_t hi) {
             c->wlog_wm_moves++;
         }
         if (k.minb == 0xFFFFFFFFu || k.maxb < k.wm) {  // nothing of this chunk is alive
-            c->wlog_free.push_back(k);
+            c->wlog_free.push_back(std::move(k));
             c->wlog_dropped++;
             c->wlog.erase(c->wlog.begin() + (long)i);
         } else {

@@ -16,18 +16,10 @@ static size_t row_bytes_of(int kind) {
 }
 extern "C" size_t fa_row_bytes(int kind) { return row_bytes_of(kind); }
 
-static int ensure_dev(fa_ctx* c, void** p, size_t* cap, size_t bytes, const char* what) {
-    if (*cap >= bytes) return FA_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 8 + 4096;
-    if (hipMalloc(p, want) != hipSuccess) {
-        c->err = std::string("hipMalloc(") + what + ") failed";
-        return FA_ERR_NOMEM;
-    }
-    *cap = want;
-    return FA_OK;
+static int ensure_dev(fa_ctx* c, DevBuf<>& b, size_t bytes, const char* what) {
+    if (b.grow(bytes, bytes + bytes / 8 + 4096)) return FA_OK;
+    c->err = std::string("hipMalloc(") + what + ") failed";
+    return FA_ERR_NOMEM;
 }
 
 // ---- collect: rows of the device state, public format, unsorted, in c->rc_buf ----------------------------------------
@@ -35,7 +27,7 @@ static int collect_5m(fa_ctx* c, uint32_t tb_lo, uint32_t tb_hi, size_t& n) {
     int rc = settle(c);
     if (rc) return rc;
     const size_t need = std::max<uint64_t>(c->stats.table_used, 1024);
-    rc = ensure_dev(c, &c->rc_buf, &c->rc_cap, need * sizeof(Row5m), "rows");
+    rc = ensure_dev(c, c->rc_buf, need * sizeof(Row5m), "rows");
     if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(&c->d_ctr->rows_count, 0, sizeof(unsigned int), c->stream));
     hipLaunchKernelGGL(extract_kernel, dim3(1024), dim3(256), 0, c->stream, c->tab, 1u << c->cap_log2, c->gran, tb_lo, tb_hi,
@@ -93,7 +85,7 @@ static int collect_wide_raw(fa_ctx* c, uint32_t kind_mask, uint32_t tb_lo, uint3
             at += 2 * arr;
         }
         if (!sel.empty()) {
-            rc = ensure_dev(c, &c->wl_scratch, &c->wl_scratch_cap, at + tmp_max + 256, "log row scratch");
+            rc = ensure_dev(c, c->wl_scratch, at + tmp_max + 256, "log row scratch");
             if (rc) return rc;
             uint8_t* sb = (uint8_t*)c->wl_scratch;
             unsigned int* total = (unsigned int*)sb;
@@ -115,7 +107,7 @@ static int collect_wide_raw(fa_ctx* c, uint32_t kind_mask, uint32_t tb_lo, uint3
         }
     }
     if (need + pending + extra_rows >= (1ull << 32)) return fail(c, FA_ERR_CAPACITY, "too many wide rows for one read");
-    rc = ensure_dev(c, &c->rc_buf, &c->rc_cap, (need + pending + extra_rows) * sizeof(WRow), "wide rows");
+    rc = ensure_dev(c, c->rc_buf, (need + pending + extra_rows) * sizeof(WRow), "wide rows");
     if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(&c->d_ctr->wrows_count, 0, sizeof(unsigned int), c->stream));
     hipLaunchKernelGGL(wextract_kernel, dim3(512), dim3(WX_BLOCK), 0, c->stream, c->wtab, 1u << c->wcap_log2, kind_mask, tb_lo, tb_hi,
@@ -246,25 +238,25 @@ static void reserve_window_read(fa_ctx* c, uint64_t rows, uint32_t nseg) {
     if (c->group_members > 1) rows = std::min<uint64_t>(rows + rows / 8, (1ull << 31) - 2048);
     const std::string keep = c->err;
     // (a window lives in one or two chunks; three when a close lags)
-    if (nseg) (void)ensure_dev(c, &c->wl_scratch, &c->wl_scratch_cap, wl_scratch_bytes(c, nseg, 3), "log row scratch");
+    if (nseg) (void)ensure_dev(c, c->wl_scratch, wl_scratch_bytes(c, nseg, 3), "log row scratch");
     size_t karr, iarr, tmp_bytes;
     const size_t scratch_bytes = merge_scratch_bytes(c, (uint32_t)rows, karr, iarr, tmp_bytes);
-    const bool grow = c->rc_cap < rows * sizeof(WRow) || c->m_scratch_cap < scratch_bytes || c->m_out_cap[0] < rows * sizeof(RowApp);
+    const bool grow = c->rc_buf.bytes() < rows * sizeof(WRow) || c->m_scratch.bytes() < scratch_bytes || c->m_out[0].bytes() < rows * sizeof(RowApp);
     if (grow) (void)hipStreamSynchronize(c->stream);  // (ensure_dev frees what it replaces)
-    (void)ensure_dev(c, &c->rc_buf, &c->rc_cap, rows * sizeof(WRow), "wide rows");
-    (void)ensure_dev(c, &c->m_scratch, &c->m_scratch_cap, scratch_bytes, "merge scratch");
-    (void)ensure_dev(c, &c->m_out[0], &c->m_out_cap[0], rows * sizeof(RowApp), "merged rows");
+    (void)ensure_dev(c, c->rc_buf, rows * sizeof(WRow), "wide rows");
+    (void)ensure_dev(c, c->m_scratch, scratch_bytes, "merge scratch");
+    (void)ensure_dev(c, c->m_out[0], rows * sizeof(RowApp), "merged rows");
     if (rows >= APP48_SPLIT_MIN) {  // (fa_read_window_app48 in two halves: the cut rows and the packed ones)
-        (void)ensure_dev(c, &c->cut_buf, &c->cut_cap, rows * sizeof(RowApp), "cut rows");
-        (void)ensure_dev(c, &c->m_out[1], &c->m_out_cap[1], rows * sizeof(RowApp48), "packed rows");
+        (void)ensure_dev(c, c->cut_buf, rows * sizeof(RowApp), "cut rows");
+        (void)ensure_dev(c, c->m_out[1], rows * sizeof(RowApp48), "packed rows");
     }
     (void)ensure_pinned(c, rows * sizeof(RowApp));
     if (c->group_members > 1) {
         // a member of a group (fa_group_*): its window leaves hash-partitioned - the rows regrouped by owner, and about as many
         // rows again received from the other members
-        (void)ensure_dev(c, &c->part_buf, &c->part_cap, rows * sizeof(RowApp), "partitioned rows");
-        (void)ensure_dev(c, &c->xch_buf, &c->xch_cap, rows * sizeof(RowApp), "group exchange buffer");
-        if (!c->part_cnt && hipMalloc(&c->part_cnt, 3 * RPART_MAX_WORLD * sizeof(unsigned int)) != hipSuccess) (void)hipGetLastError();
+        (void)ensure_dev(c, c->part_buf, rows * sizeof(RowApp), "partitioned rows");
+        (void)ensure_dev(c, c->xch_buf, rows * sizeof(RowApp), "group exchange buffer");
+        if (!c->part_cnt.grow(3 * RPART_MAX_WORLD * sizeof(unsigned int))) (void)hipGetLastError();
     }
     if (rows >= APP48_SPLIT_MIN && !c->copy_stream && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) == hipSuccess && c->h_rows && c->m_out[1]) {
         // (a stream's first copy sets its engine up: 3 ms inside the first window read otherwise)
@@ -288,11 +280,11 @@ static int rows_merge_t(fa_ctx* c, const void* d_rows, size_t n_in, uint32_t fol
     // (the caller's rows may be this ctx's own result of an earlier call - one rank feeding fa_rows_device's pointer back
     // in: the buffers below are about to be reused)
     for (int q = 0; q < 2; q++)
-        if (c->m_out[q] && (const uint8_t*)d_rows >= (const uint8_t*)c->m_out[q] && (const uint8_t*)d_rows < (const uint8_t*)c->m_out[q] + c->m_out_cap[q])
+        if (c->m_out[q] && (const uint8_t*)d_rows >= (const uint8_t*)c->m_out[q] && (const uint8_t*)d_rows < (const uint8_t*)c->m_out[q] + c->m_out[q].bytes())
             return fail(c, FA_ERR_ARG, "rows to merge alias the ctx's result buffer (copy them first)");
     size_t karr, iarr, tmp_bytes;
     const size_t scratch_bytes = merge_scratch_bytes(c, n, karr, iarr, tmp_bytes);
-    int rc = ensure_dev(c, &c->m_scratch, &c->m_scratch_cap, scratch_bytes, "merge scratch");
+    int rc = ensure_dev(c, c->m_scratch, scratch_bytes, "merge scratch");
     if (rc) return rc;
     uint8_t* base = (uint8_t*)c->m_scratch;
     SortScratch ss;
@@ -328,8 +320,8 @@ static int rows_merge_t(fa_ctx* c, const void* d_rows, size_t n_in, uint32_t fol
     if (clk) clk->mark("heads+scan");
     const uint32_t m = last[0] + last[1];  // groups
     const size_t m_emit = (k && k < m) ? k : m;
-    const bool host = to_host && c->h_rows && m_emit * sizeof(Row) <= c->h_rows_cap;
-    rc = ensure_dev(c, &c->m_out[0], &c->m_out_cap[0], (size_t)m * sizeof(Row), "merged rows");
+    const bool host = to_host && c->h_rows && m_emit * sizeof(Row) <= c->h_rows.bytes();
+    rc = ensure_dev(c, c->m_out[0], (size_t)m * sizeof(Row), "merged rows");
     if (rc) return rc;
     // the groups' rows: heads sum the first RUN_SERIAL rows of their run; longer runs (only a caller's degenerate input has
     // them) are finished with atomics by a second kernel, which needs the rows in device memory
@@ -379,7 +371,7 @@ static int rows_merge_t(fa_ctx* c, const void* d_rows, size_t n_in, uint32_t fol
         uint32_t* cur2 = nullptr;
         rc = rows_sort_order<KIND, true>(c, (const Row*)red, m, fold, ss, &cur2, &sorted_bits);
         if (rc) return rc;
-        rc = ensure_dev(c, &c->m_out[1], &c->m_out_cap[1], m_emit * sizeof(Row), "ordered rows");
+        rc = ensure_dev(c, c->m_out[1], m_emit * sizeof(Row), "ordered rows");
         if (rc) return rc;
         Row* dst = host ? (Row*)c->h_rows : (Row*)c->m_out[1];
         hipLaunchKernelGGL((row_gather_kernel<Row>), grid_n(m_emit), b, 0, c->stream, (const Row*)red, (const uint32_t*)cur2, (uint32_t)m_emit, dst);
@@ -465,7 +457,7 @@ again:
         rc = collect_wide_raw(c, 1u << (kind == RK_MINUTE ? WK_MINUTE : dst ? WK_DSTPORT : WK_SRCPORT), 0, 0, n);
         if (rc) break;
         const size_t cap_rows = n + (port ? PORT_DENSE : 0) + 16;
-        rc = ensure_dev(c, &c->rw_buf, &c->rw_cap, cap_rows * sizeof(RowW), "port / minute rows");
+        rc = ensure_dev(c, c->rw_buf, cap_rows * sizeof(RowW), "port / minute rows");
         if (rc) break;
         if (n) hipLaunchKernelGGL(wrows_to_w_kernel, grid_n(n), dim3(256), 0, c->stream, (const WRow*)c->rc_buf, (uint32_t)n, port ? 1u : 60u, (RowW*)c->rw_buf);
         if (port) {
@@ -501,7 +493,7 @@ again:
         bool done = false;
         if (lb_ok) {
             const size_t cap_rows = std::max<size_t>(8 * sel_k, 1u << 16);
-            rc = ensure_dev(c, &c->rc_buf, &c->rc_cap, cap_rows * sizeof(TopkRow), "top-k rows");
+            rc = ensure_dev(c, c->rc_buf, cap_rows * sizeof(TopkRow), "top-k rows");
             if (rc) break;
             HIPCHK(c, hipMemsetAsync(&c->d_ctr->ks_rows, 0, sizeof(unsigned int), c->stream));
             hipLaunchKernelGGL(topk_scan_kernel<TK_ONE>, dim3(1024), dim3(256), 0, c->stream, ks, nslots, (const unsigned long long*)cms, c->cfg.cms_depth, c->cfg.cms_width_log2,
@@ -519,7 +511,7 @@ again:
             // set with that bin (row-0 early-out) replaces the full-depth scan (40 M random sketch reads on BASELINE config 3's sets)
             const uint32_t ns = nslots >> 6;
             const size_t cm_bytes = ((size_t)(ns >> 6) * sizeof(unsigned short) + 255) & ~(size_t)255;
-            rc = ensure_dev(c, &c->rw_buf, &c->rw_cap, (TK_BINS + 4) * sizeof(unsigned int) + cm_bytes, "top-k histogram");
+            rc = ensure_dev(c, c->rw_buf, (TK_BINS + 4) * sizeof(unsigned int) + cm_bytes, "top-k histogram");
             if (rc) break;
             unsigned int* hist = (unsigned int*)c->rw_buf;
             HIPCHK(c, hipMemsetAsync(hist, 0, (TK_BINS + 4) * sizeof(unsigned int), c->stream));
@@ -532,7 +524,7 @@ again:
             clk->mark("sample");
             if (sel[2] >= sel_k && sel[0] > 0) {
                 const size_t cap_rows = std::max<size_t>(256 * sel_k, 1u << 16);
-                rc = ensure_dev(c, &c->rc_buf, &c->rc_cap, cap_rows * sizeof(TopkRow), "top-k rows");
+                rc = ensure_dev(c, c->rc_buf, cap_rows * sizeof(TopkRow), "top-k rows");
                 if (rc) break;
                 HIPCHK(c, hipMemsetAsync(&c->d_ctr->ks_rows, 0, sizeof(unsigned int), c->stream));
                 hipLaunchKernelGGL(topk_scan_kernel<TK_ONE>, dim3(1024), dim3(256), 0, c->stream, ks, nslots, (const unsigned long long*)cms, c->cfg.cms_depth,
@@ -546,7 +538,7 @@ again:
         }
         if (!done && sel_k && sel_k < nslots) {
             const size_t cm_bytes = ((size_t)(nslots >> 6) * sizeof(unsigned short) + 255) & ~(size_t)255;
-            rc = ensure_dev(c, &c->rw_buf, &c->rw_cap, (TK_BINS + 4) * sizeof(unsigned int) + cm_bytes, "top-k histogram");
+            rc = ensure_dev(c, c->rw_buf, (TK_BINS + 4) * sizeof(unsigned int) + cm_bytes, "top-k histogram");
             if (rc) break;
             unsigned int* hist = (unsigned int*)c->rw_buf;
             unsigned short* chunkmax = (unsigned short*)(hist + TK_BINS + 4);
@@ -560,7 +552,7 @@ again:
             clk->mark("estimates");
             const size_t cap_rows = std::max<size_t>(sel[1], 1);
             sel_partial = sel[1] < sel[2];
-            rc = ensure_dev(c, &c->rc_buf, &c->rc_cap, cap_rows * sizeof(TopkRow), "top-k rows");
+            rc = ensure_dev(c, c->rc_buf, cap_rows * sizeof(TopkRow), "top-k rows");
             if (rc) break;
             HIPCHK(c, hipMemsetAsync(&c->d_ctr->ks_rows, 0, sizeof(unsigned int), c->stream));
             hipLaunchKernelGGL(topk_pick_kernel, dim3(256), dim3(256), 0, c->stream, (const KeySlot*)ks, nslots, (const unsigned short*)chunkmax, sel[0], (TopkRow*)c->rc_buf,
@@ -571,7 +563,7 @@ again:
             done = true;
         }
         if (!done) {  // every row
-            rc = ensure_dev(c, &c->rc_buf, &c->rc_cap, (size_t)nslots * sizeof(TopkRow), "top-k rows");
+            rc = ensure_dev(c, c->rc_buf, (size_t)nslots * sizeof(TopkRow), "top-k rows");
             if (rc) break;
             HIPCHK(c, hipMemsetAsync(&c->d_ctr->ks_rows, 0, sizeof(unsigned int), c->stream));
             hipLaunchKernelGGL(topk_scan_kernel<TK_ONE>, dim3(1024), dim3(256), 0, c->stream, ks, nslots, (const unsigned long long*)cms, c->cfg.cms_depth, c->cfg.cms_width_log2,
@@ -659,7 +651,7 @@ static int copy_out_pipelined(fa_ctx* c, void* out, const void* d, size_t bytes)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return FA_OK;
     }
-    const size_t half = (c->h_rows_cap / 2) & ~(size_t)4095;
+    const size_t half = (c->h_rows.bytes() / 2) & ~(size_t)4095;
     if (!c->h_rows || bytes < ((size_t)8 << 20) || half < ((size_t)4 << 20)) {
         HIPCHK(c, hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost));
         return FA_OK;
@@ -684,13 +676,9 @@ static int copy_out_pipelined(fa_ctx* c, void* out, const void* d, size_t bytes)
 static int ensure_pinned(fa_ctx* c, size_t result_bytes) {
     constexpr size_t PIN_MAX = (size_t)64 << 20;
     const size_t want = std::min(PIN_MAX, result_bytes + result_bytes / 4 + 4096);
-    if (c->h_rows_cap >= want) return FA_OK;
+    if (c->h_rows.bytes() >= want) return FA_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_rows) (void)hipHostFree(c->h_rows);
-    c->h_rows = nullptr;
-    c->h_rows_cap = 0;
-    if (hipHostMalloc(&c->h_rows, want) == hipSuccess) c->h_rows_cap = want;
-    else c->h_rows = nullptr;  // (not an error: the copy falls back to a plain hipMemcpy)
+    (void)c->h_rows.grow(want);  // (a failure is not an error: the copy falls back to a plain hipMemcpy)
     return FA_OK;
 }
 // the rows behind `d` (device, or the pinned host buffer) into the caller's buffer
@@ -730,7 +718,7 @@ static int rows_read(fa_ctx* c, int kind, uint32_t timeslot, size_t k, void* out
 // one window's (SrcAddr,DstPort,Proto) rows as 48-byte rows (fa_row_app48): the merged rows are repacked in HBM - into the buffer
 // the read collected its input in, dead by now - and leave like any other result
 static int rows_read_app48_whole(fa_ctx* c, const void* d, size_t n, void* out, size_t cap, size_t* n_out, ReadClock& clk) {
-    int rc = ensure_dev(c, &c->rc_buf, &c->rc_cap, n * sizeof(RowApp48), "packed rows");
+    int rc = ensure_dev(c, c->rc_buf, n * sizeof(RowApp48), "packed rows");
     if (rc) return rc;
     hipLaunchKernelGGL(row_app48_kernel, grid_n(n), dim3(256), 0, c->stream, (const RowApp*)d, (uint32_t)n, (RowApp48*)c->rc_buf);
     HIPCHK(c, hipGetLastError());
@@ -753,7 +741,7 @@ static int rows_read_app48_split(fa_ctx* c, size_t n, uint32_t fold, void* out, 
     constexpr uint32_t NS = 2048;
     size_t karr, iarr, tmp_bytes;
     const size_t scratch_bytes = merge_scratch_bytes(c, (uint32_t)n, karr, iarr, tmp_bytes);
-    int rc = ensure_dev(c, &c->m_scratch, &c->m_scratch_cap, scratch_bytes, "merge scratch");
+    int rc = ensure_dev(c, c->m_scratch, scratch_bytes, "merge scratch");
     if (rc) return rc;
     unsigned long long* d_keys = (unsigned long long*)c->m_scratch;
     hipLaunchKernelGGL(app_key_sample_kernel, dim3(NS / 256), dim3(256), 0, c->stream, rows, (uint32_t)n, (uint32_t)(n / NS), d_keys, NS);
@@ -762,7 +750,7 @@ static int rows_read_app48_split(fa_ctx* c, size_t n, uint32_t fold, void* out, 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::nth_element(keys.begin(), keys.begin() + NS / 2, keys.end());
     const unsigned long long pivot = keys[NS / 2];
-    rc = ensure_dev(c, &c->cut_buf, &c->cut_cap, n * sizeof(RowApp), "cut rows");
+    rc = ensure_dev(c, c->cut_buf, n * sizeof(RowApp), "cut rows");
     if (rc) return rc;
     unsigned int* d_cnt = (unsigned int*)c->m_scratch;  // (two words; the sample has been read)
     HIPCHK(c, hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned int), c->stream));
@@ -772,7 +760,7 @@ static int rows_read_app48_split(fa_ctx* c, size_t n, uint32_t fold, void* out, 
     HIPCHK(c, hipMemcpyAsync(&na, d_cnt, sizeof na, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     clk.mark("cut");
-    rc = ensure_dev(c, &c->m_out[1], &c->m_out_cap[1], n * sizeof(RowApp48), "packed rows");  // (at most n rows come out)
+    rc = ensure_dev(c, c->m_out[1], n * sizeof(RowApp48), "packed rows");  // (at most n rows come out)
     if (rc) return rc;
     if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     RowApp48* packed = (RowApp48*)c->m_out[1];
@@ -1007,10 +995,10 @@ extern "C" int fa_rows_partition_device(fa_ctx* c, int kind, const void* d_rows,
     *d_out = nullptr;
     for (uint32_t d = 0; d < world; d++) counts[d] = 0;
     if (!n) return FA_OK;
-    int rc = ensure_dev(c, &c->part_buf, &c->part_cap, n * rb, "partitioned rows");
+    int rc = ensure_dev(c, c->part_buf, n * rb, "partitioned rows");
     if (rc) return rc;
-    if (!c->part_cnt && hipMalloc(&c->part_cnt, 3 * RPART_MAX_WORLD * sizeof(unsigned int)) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(partition counters) failed");
-    if ((const uint8_t*)d_rows >= (const uint8_t*)c->part_buf && (const uint8_t*)d_rows < (const uint8_t*)c->part_buf + c->part_cap)
+    if (!c->part_cnt.grow(3 * RPART_MAX_WORLD * sizeof(unsigned int))) return fail(c, FA_ERR_NOMEM, "hipMalloc(partition counters) failed");
+    if ((const uint8_t*)d_rows >= (const uint8_t*)c->part_buf && (const uint8_t*)d_rows < (const uint8_t*)c->part_buf + c->part_buf.bytes())
         return fail(c, FA_ERR_ARG, "rows to partition alias the ctx's partition buffer");
     switch (kind) {
     case RK_5M: rc = rows_partition_t<RK_5M>(c, d_rows, (uint32_t)n, world, counts); break;
@@ -1042,7 +1030,7 @@ extern "C" int fa_rows_fetch(fa_ctx* c, int kind, const void* d_rows, size_t n, 
         }
     } done{clk, kind, n};
     if (n) {
-        if (c->h_rows && (const uint8_t*)d_rows >= (const uint8_t*)c->h_rows && (const uint8_t*)d_rows < (const uint8_t*)c->h_rows + c->h_rows_cap) {
+        if (c->h_rows && (const uint8_t*)d_rows >= (const uint8_t*)c->h_rows && (const uint8_t*)d_rows < (const uint8_t*)c->h_rows + c->h_rows.bytes()) {
             copy_threads(c, out, d_rows, n * rb);  // (host memory: a result the last kernel wrote into the pinned buffer)
             return FA_OK;
         }
@@ -1099,7 +1087,7 @@ extern "C" int fa_open_timeslots(fa_ctx* c, uint32_t* out, size_t cap, size_t* n
         int rc0 = settle(c);
         if (rc0) return rc0;
         constexpr uint32_t MAXBITS = 1u << 16;
-        rc0 = ensure_dev(c, &c->rw_buf, &c->rw_cap, MAXBITS / 8 + 64, "timeslot bits");
+        rc0 = ensure_dev(c, c->rw_buf, MAXBITS / 8 + 64, "timeslot bits");
         if (rc0) return rc0;
         unsigned int* range = (unsigned int*)c->rw_buf;
         unsigned int* bits = range + 16;
@@ -1153,20 +1141,17 @@ extern "C" int fa_merge_rows(fa_ctx* c, const fa_row5m* rows, size_t n) {
     if (!n) return FA_OK;
     for (size_t i = 0; i < n; i++)
         if (rows[i].timeslot % c->gran) return fail(c, FA_ERR_ARG, "fa_merge_rows: timeslot not on this ctx's bucket grid");
-    Row5m* d = nullptr;
-    if (hipMalloc(&d, n * sizeof(Row5m)) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc failed");
-    hipError_t e = hipMemcpyAsync(d, rows, n * sizeof(Row5m), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        KArgs a = make_args(c);
-        hipLaunchKernelGGL(merge_rows_kernel, dim3(256), dim3(256), 0, c->stream, d, (uint32_t)n, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) {
+    DevBuf<Row5m> d;
+    if (!d.grow(n * sizeof(Row5m))) return fail(c, FA_ERR_NOMEM, "hipMalloc failed");
+    auto hip_failed = [&](hipError_t e) {
         c->err = std::string("fa_merge_rows: ") + hipGetErrorString(e);
         return FA_ERR_HIP;
-    }
+    };
+    hipError_t e = hipMemcpyAsync(d, rows, n * sizeof(Row5m), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return hip_failed(e);
+    KArgs a = make_args(c);
+    hipLaunchKernelGGL(merge_rows_kernel, dim3(256), dim3(256), 0, c->stream, d.get(), (uint32_t)n, a);
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_failed(e);
     return settle(c);
 }
 

@@ -5,20 +5,17 @@
 static int merge_wide(fa_ctx* c, const std::vector<WRow>& rows) {
     if (!c->wtab) return fail(c, FA_ERR_ARG, "key set not enabled");
     if (rows.empty()) return FA_OK;
-    WRow* d = nullptr;
-    if (hipMalloc(&d, rows.size() * sizeof(WRow)) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc failed");
-    hipError_t e = hipMemcpyAsync(d, rows.data(), rows.size() * sizeof(WRow), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        KArgs a = make_args(c);
-        hipLaunchKernelGGL(wmerge_kernel, dim3(256), dim3(256), 0, c->stream, d, (uint32_t)rows.size(), a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) {
+    DevBuf<WRow> d;
+    if (!d.grow(rows.size() * sizeof(WRow))) return fail(c, FA_ERR_NOMEM, "hipMalloc failed");
+    auto hip_failed = [&](hipError_t e) {
         c->err = std::string("merge_wide: ") + hipGetErrorString(e);
         return FA_ERR_HIP;
-    }
+    };
+    hipError_t e = hipMemcpyAsync(d, rows.data(), rows.size() * sizeof(WRow), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return hip_failed(e);
+    KArgs a = make_args(c);
+    hipLaunchKernelGGL(wmerge_kernel, dim3(256), dim3(256), 0, c->stream, d.get(), (uint32_t)rows.size(), a);
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_failed(e);
     return settle(c);
 }
 
@@ -65,20 +62,17 @@ extern "C" int fa_merge_ports(fa_ctx* c, int dst, const fa_port_row* rows, size_
         }
     }
     if (!small.empty()) {
-        fa_port_row* d = nullptr;
-        if (hipMalloc(&d, small.size() * sizeof(fa_port_row)) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc failed");
-        hipError_t e = hipMemcpyAsync(d, small.data(), small.size() * sizeof(fa_port_row), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(port_merge_kernel, dim3(64), dim3(256), 0, c->stream, d, (uint32_t)small.size(),
-                               c->port_hist + (size_t)dst * PORT_DENSE);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d);
-        if (e != hipSuccess) {
+        DevBuf<fa_port_row> d;
+        if (!d.grow(small.size() * sizeof(fa_port_row))) return fail(c, FA_ERR_NOMEM, "hipMalloc failed");
+        auto hip_failed = [&](hipError_t e) {
             c->err = std::string("fa_merge_ports: ") + hipGetErrorString(e);
             return FA_ERR_HIP;
-        }
+        };
+        hipError_t e = hipMemcpyAsync(d, small.data(), small.size() * sizeof(fa_port_row), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return hip_failed(e);
+        hipLaunchKernelGGL(port_merge_kernel, dim3(64), dim3(256), 0, c->stream, d.get(), (uint32_t)small.size(),
+                           c->port_hist + (size_t)dst * PORT_DENSE);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_failed(e);
     }
     return merge_wide(c, big);
 }
@@ -114,7 +108,7 @@ extern "C" int fa_dashboard_reset(fa_ctx* c) {
 // Sums the sketch copies into copy 0 (sinks.cuh, cms_add).  Every reader of a sketch calls this first.
 static int cms_fold(fa_ctx* c) {
     if (!c->cms_dirty) return FA_OK;
-    for (unsigned long long* p : {c->cms_src, c->cms_dst})
+    for (unsigned long long* p : {c->cms_src.get(), c->cms_dst.get()})
         if (p) hipLaunchKernelGGL(cms_fold_kernel, dim3(2048), dim3(256), 0, c->stream, p, c->cms_words);
     HIPCHK(c, hipGetLastError());
     c->cms_dirty = false;
@@ -130,8 +124,8 @@ static unsigned long long* cms_of(fa_ctx* c, uint32_t key_set) {
 static int ensure_merged_view(fa_ctx* c) {
     for (int d = 0; d < 2; d++) {
         unsigned long long* own = d ? c->cms_dst : c->cms_src;
-        unsigned long long** m = d ? &c->cms_dst_m : &c->cms_src_m;
-        if (own && !*m && hipMalloc(m, c->cms_words * 8) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc(merged sketch view) failed");
+        DevBuf<unsigned long long>& m = d ? c->cms_dst_m : c->cms_src_m;
+        if (own && !m.grow(c->cms_words * 8)) return fail(c, FA_ERR_NOMEM, "hipMalloc(merged sketch view) failed");
     }
     return FA_OK;
 }
@@ -196,19 +190,16 @@ extern "C" int fa_topk_merge_keys(fa_ctx* c, uint32_t key_set, const uint8_t* ke
     KeySlot* ks = key_set == FA_KEYS_SRCADDR_CMS ? c->ks_src : key_set == FA_KEYS_DSTADDR_CMS ? c->ks_dst : nullptr;
     if (!ks) return fail(c, FA_ERR_ARG, "fa_topk_merge_keys: key set not enabled");
     if (!n) return FA_OK;
-    uint4* d = nullptr;
-    if (hipMalloc(&d, n * 16) != hipSuccess) return fail(c, FA_ERR_NOMEM, "hipMalloc failed");
-    hipError_t e = hipMemcpyAsync(d, keys, n * 16, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        KArgs a = make_args(c);
-        hipLaunchKernelGGL(keyset_merge_kernel, dim3(256), dim3(256), 0, c->stream, d, (uint32_t)n, ks, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) {
+    DevBuf<uint4> d;
+    if (!d.grow(n * 16)) return fail(c, FA_ERR_NOMEM, "hipMalloc failed");
+    auto hip_failed = [&](hipError_t e) {
         c->err = std::string("fa_topk_merge_keys: ") + hipGetErrorString(e);
         return FA_ERR_HIP;
-    }
+    };
+    hipError_t e = hipMemcpyAsync(d, keys, n * 16, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return hip_failed(e);
+    KArgs a = make_args(c);
+    hipLaunchKernelGGL(keyset_merge_kernel, dim3(256), dim3(256), 0, c->stream, d.get(), (uint32_t)n, ks, a);
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_failed(e);
     return FA_OK;
 }

@@ -9,27 +9,22 @@
 // steps instead of jumping to the worst case of a large chunk.
 
 struct TalkState {
-    TSlot* tab[2] = {nullptr, nullptr};
+    DevBuf<TSlot> tab[2];
     uint32_t log2[2] = {16, 16};
     uint64_t used_ub[2] = {0, 0};
-    TalkCounters* d_ctr = nullptr;
+    DevBuf<TalkCounters> d_ctr;
     size_t chunk = (size_t)1 << 20;  // env FA_TALK_CHUNK
     uint32_t wgpc = TALK_WG_PER_CU;  // env FA_TALK_WGPC (A/B: workgroups per CU of the fold kernel)
     uint64_t grows = 0, fold_launches = 0, fold_ns_total = 0;
     struct Ev { hipEvent_t e0, e1; };
     std::vector<Ev> ev;   // one pair per fold launch that has not been read yet
     size_t ev_used = 0;
-    void* scratch = nullptr;  // fa_top_talkers: rows, ordered rows, sort keys, permutations, hipcub storage
-    size_t scratch_cap = 0;
+    DevBuf<> scratch;  // fa_top_talkers: rows, ordered rows, sort keys, permutations, hipcub storage
 };
 
 static void talk_destroy(fa_ctx* c) {
     TalkState* t = c->talk;
     if (!t) return;
-    (void)hipFree(t->tab[0]);
-    (void)hipFree(t->tab[1]);
-    (void)hipFree(t->d_ctr);
-    (void)hipFree(t->scratch);
     for (auto& e : t->ev) {
         (void)hipEventDestroy(e.e0);
         (void)hipEventDestroy(e.e1);
@@ -55,10 +50,10 @@ extern "C" int fa_talkers_enable(fa_ctx* c, uint32_t capacity_log2) {
     if (const char* d = getenv("FA_TALK_CHUNK")) t->chunk = (size_t)std::min<long long>(1ll << 28, std::max<long long>(1, atoll(d)));
     if (const char* d = getenv("FA_TALK_WGPC")) t->wgpc = (uint32_t)std::min(8, std::max(1, atoi(d)));
     c->talk = t;
-    bool ok = hipMalloc(&t->d_ctr, sizeof(TalkCounters)) == hipSuccess && hipMemsetAsync(t->d_ctr, 0, sizeof(TalkCounters), c->stream) == hipSuccess;
+    bool ok = t->d_ctr.grow(sizeof(TalkCounters)) && hipMemsetAsync(t->d_ctr, 0, sizeof(TalkCounters), c->stream) == hipSuccess;
     for (int d = 0; d < 2 && ok; d++) {
         t->log2[d] = capacity_log2;
-        ok = hipMalloc(&t->tab[d], sizeof(TSlot) << capacity_log2) == hipSuccess && hipMemsetAsync(t->tab[d], 0, sizeof(TSlot) << capacity_log2, c->stream) == hipSuccess;
+        ok = t->tab[d].grow(sizeof(TSlot) << capacity_log2) && hipMemsetAsync(t->tab[d], 0, sizeof(TSlot) << capacity_log2, c->stream) == hipSuccess;
     }
     ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) {
@@ -89,8 +84,8 @@ static int talk_settle(fa_ctx* c, TalkCounters& h) {
 static int talk_grow(fa_ctx* c, int d) {
     TalkState* t = c->talk;
     const uint32_t nl = t->log2[d] + 1;
-    TSlot* nt = nullptr;
-    if (hipMalloc(&nt, sizeof(TSlot) << nl) != hipSuccess) {
+    DevBuf<TSlot> nt;
+    if (!nt.grow(sizeof(TSlot) << nl)) {
         (void)hipGetLastError();
         return fail(c, FA_ERR_NOMEM, "hipMalloc(talker table) failed");
     }
@@ -99,18 +94,16 @@ static int talk_grow(fa_ctx* c, int d) {
     if (e == hipSuccess) {
         const uint64_t slots = 1ull << t->log2[d];
         const unsigned g = (unsigned)std::min<uint64_t>((slots + 255) / 256, (uint64_t)c->num_cus * 8);
-        hipLaunchKernelGGL(talker_rehash_kernel, dim3(g), dim3(256), 0, c->stream, (const TSlot*)t->tab[d], slots, nt, (uint32_t)((1ull << nl) - 1), t->d_ctr, d);
+        hipLaunchKernelGGL(talker_rehash_kernel, dim3(g), dim3(256), 0, c->stream, (const TSlot*)t->tab[d], slots, nt.get(), (uint32_t)((1ull << nl) - 1), t->d_ctr.get(), d);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-        (void)hipFree(nt);
         c->sticky = FA_ERR_HIP;  // (the occupied-slot counter was reset: the state is no longer trustworthy)
         c->err = std::string("talker table growth: ") + hipGetErrorString(e);
         return FA_ERR_HIP;
     }
-    (void)hipFree(t->tab[d]);
-    t->tab[d] = nt;
+    t->tab[d] = std::move(nt);  // (frees the old table: the rehash has been synchronised)
     t->log2[d] = nl;
     t->grows++;
     return FA_OK;
@@ -237,19 +230,18 @@ extern "C" int fa_merge_talkers(fa_ctx* c, int dst, const fa_talker_row* rows, s
         const size_t m = std::min(n - i, talk_chunk_cap(c));
         int rc = talk_reserve(c, dst, m);
         if (rc) return rc;
-        TalkRow* d = nullptr;
-        if (hipMalloc(&d, m * sizeof(TalkRow)) != hipSuccess) {
+        DevBuf<TalkRow> d;
+        if (!d.grow(m * sizeof(TalkRow))) {
             (void)hipGetLastError();
             return fail(c, FA_ERR_NOMEM, "hipMalloc failed");
         }
         hipError_t e = hipMemcpyAsync(d, rows + i, m * sizeof(TalkRow), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(talker_merge_kernel, dim3((unsigned)std::min<size_t>((m + 255) / 256, 1024)), dim3(256), 0, c->stream, (const TalkRow*)d, (uint32_t)m,
-                               t->tab[dst], (uint32_t)((1ull << t->log2[dst]) - 1), t->d_ctr, dst);
+                               t->tab[dst].get(), (uint32_t)((1ull << t->log2[dst]) - 1), t->d_ctr.get(), dst);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (the caller's rows are not referenced after the call)
-        (void)hipFree(d);
         if (e != hipSuccess) {
             c->err = std::string("fa_merge_talkers: ") + hipGetErrorString(e);
             return FA_ERR_HIP;
@@ -316,7 +308,7 @@ extern "C" int fa_top_talkers(fa_ctx* c, int dst, size_t k, fa_talker_row* out, 
         return fail(c, FA_ERR_HIP, "fa_top_talkers: sort sizing failed");
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t rows_b = al((size_t)n * sizeof(TalkRow)), out_b = al(need * sizeof(TalkRow)), key_b = al((size_t)n * 8), perm_b = al((size_t)n * 4);
-    rc = ensure_dev(c, &t->scratch, &t->scratch_cap, rows_b + out_b + 2 * key_b + 2 * perm_b + 256 + al(tmp_bytes), "talker rows");
+    rc = ensure_dev(c, t->scratch, rows_b + out_b + 2 * key_b + 2 * perm_b + 256 + al(tmp_bytes), "talker rows");
     if (rc) return rc;
     uint8_t* p = (uint8_t*)t->scratch;
     TalkRow* rows = (TalkRow*)p;
