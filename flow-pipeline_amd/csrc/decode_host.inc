@@ -40,7 +40,6 @@ static int decode_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
 extern "C" int fa_decode_device(fa_ctx* c, const void* d_buf, size_t len, const void* d_off, size_t n,
                                 fa_columns* out) {
     FA_ON_DEVICE(c);
-    FA_ON_DEVICE(c);
     if (!c || !out) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;
     return decode_device_records(c, d_buf, len, len, d_off, n, out);
@@ -58,20 +57,12 @@ static int decode_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
         a.off = (const uint32_t*)d_off;
         a.n = (uint32_t)n;
         a.len = (uint32_t)len;
-        a.tile_recs = tile_recs_for(bytes, n);
-        if (c->dev_used == c->dev_pool.size()) {
-            if (c->dev_pool.size() >= 1024) {  // bound the pool: fold what is pending
-                rc = settle(c);
-                if (rc) return rc;
-            } else {
-                fa_ctx::LaunchEvents e{};
-                HIPCHK(c, hipEventCreate(&e.e0));
-                HIPCHK(c, hipEventCreate(&e.e1));
-                HIPCHK(c, hipEventCreate(&e.e2));
-                c->dev_pool.push_back(e);
-            }
-        }
-        rc = launch_tiles<MODE_DECODE>(c, a, tile_grid<MODE_DECODE>(c, a.n, a.tile_recs), &c->dev_pool[c->dev_used++]);
+        LaunchPlan p;  // (the default: workgroup tiles, the flows_5m variant)
+        p.tile_recs = a.tile_recs = tile_recs_for(bytes, n);
+        p.grid = grid_for(c, tile_kernel<MODE_DECODE, 1u>, a.n, p.tile_recs);
+        rc = acquire_events(c, c->dev_pool, c->dev_used, 1024);
+        if (rc) return rc;
+        rc = launch_tiles<MODE_DECODE>(c, a, p, &c->dev_pool[c->dev_used++]);
         if (rc) return rc;
     }
     out->time_received = c->cols.time_received;
@@ -95,7 +86,6 @@ static int decode_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
 
 extern "C" int fa_decode(fa_ctx* c, const uint8_t* buf, size_t len, const uint64_t* offsets, size_t n,
                          fa_flow_row* out) {
-    FA_ON_DEVICE(c);
     FA_ON_DEVICE(c);
     if (!c || (!out && n)) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;

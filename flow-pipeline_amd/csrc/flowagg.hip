@@ -29,6 +29,7 @@
 #include "../../include/flowagg.h"
 #include "buffers.h"
 #include "kernels.cuh"
+#include "launch_plan.h"
 
 using namespace fa;
 
@@ -117,7 +118,6 @@ struct fa_ctx {
     bool wide_defer = false;       // adaptive (FA_WIDE unset): log mode from the moment more than half of a million records opened new rows - for
                                    // the rest of the ctx's life (deferred launches tell nothing about new rows; a stream that stops opening
                                    // rows folds its chunks through wagg_kernel once more than wlog_max are pending: the scatter sink's cost)
-    bool wlog_now = false;         // the launch being prepared runs in log mode
     uint64_t seen_wfold = 0;       // Counters::wfold_n at the last feedback look
     size_t wlog_max = 8;
     // Upper bound of the wide table's rows at any moment (wide_rows_bound): what the newest counter snapshot the host has
@@ -136,11 +136,8 @@ struct fa_ctx {
     bool cms_atomic = false;  // env FA_CMS=atomic (A/B, tests): every sketch update through memory-side atomics
     bool cms_scatter_ok = false;  // the sketch geometry fits the scatter sink (256 partitions of <= 2^14 counters)
     int sink_mode = 0;  // 0 auto, 1 direct, 2 scatter (env FA_SINK)
-    // decision for the batch being launched: the scatter sink, whose kernel is the wave-tile kernel (15-20 % faster than the
-    // 256-thread workgroup-tile kernel when most records leave as tuples); the workgroup-tile kernel serves the decode path,
-    // the direct sink (small batches) and key sets without the flows_5m rollup
-    bool use_wave_tiles = false;
-    bool use_t8 = false;          // ... compact 8-byte tuples (table.cuh) for it
+    // (what is decided for ONE launch - sink, tuple format, kernel variant, grid - is a LaunchPlan, launch_plan.h: a value that
+    // ingest_device_records builds and passes on, never a member here)
     // tuple format feedback: compact tuples while (almost) every record fits them.  A launch whose misfits (records
     // that only a wide tuple holds - they took the direct path) exceed 1/16 of its records switches the ctx to wide
     // tuples for the next 64 launches, then compact is tried again.  Only speed depends on this, never results.
@@ -314,18 +311,6 @@ static int grid_for(fa_ctx* c, K kernel, uint32_t n, uint32_t tile_recs) {
     if (c->wgpc_cap && (int)c->wgpc_cap < per_cu) per_cu = (int)c->wgpc_cap;
     uint32_t g = std::min<uint32_t>((uint32_t)c->num_cus * (uint32_t)per_cu, AGG_MAX_NWG);
     return (int)std::max(1u, std::min(tiles, g));
-}
-
-// Records per LDS tile: as many as fit one tile buffer at the batch's mean record
-// size (one record per lane, at most BLOCK).  Tiles that still overflow (outliers)
-// take the multi-pass path inside the kernel.
-static uint32_t tile_recs_for(size_t len, size_t n) {
-    if (n == 0) return BLOCK;
-    double avg = (double)len / (double)n + 0.5;
-    double r = ((double)TILE_BYTES - 15.0) / avg;
-    if (r >= (double)BLOCK) return BLOCK;
-    if (r < 1.0) return 1;
-    return (uint32_t)r;
 }
 
 extern "C" int fa_create(const fa_config* cfg_in, fa_ctx** out) {
@@ -632,7 +617,6 @@ __global__ __launch_bounds__(256) void mock_len_sum_kernel(const uint32_t* len, 
 }
 extern "C" int fa_mock_generate_device(fa_ctx* c, const fa_mock_params* g, uint64_t i0, uint64_t n, void* d_buf,
                                        size_t cap, void* d_off, uint64_t* bytes_out) {
-    FA_ON_DEVICE(c);
     FA_ON_DEVICE(c);
     if (!c || !g || !d_buf || !d_off || n == 0 || n >= (1ull << 31)) return FA_ERR_ARG;
     uint32_t* off = (uint32_t*)d_off;

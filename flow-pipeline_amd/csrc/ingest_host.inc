@@ -1,105 +1,75 @@
 // ingest_host.inc - the ingest path: tuple segments, device-side framing, launches, host staging (included by flowagg.hip: one translation unit, see kernels.cuh for the device side).
 
 // ---- ingest ---------------------------------------------------------------------------
+template <uint32_t KS, bool SEQ = false, int CANDM = -1>
+static void launch_wtile(fa_ctx* c, const KArgs& a, const LaunchPlan& p) {
+    const dim3 g(p.grid), b(wtile_block<KS>());
+    if (p.t8) hipLaunchKernelGGL((wtile_kernel<KS, true, SEQ, CANDM>), g, b, 0, c->stream, a);
+    else hipLaunchKernelGGL((wtile_kernel<KS, false, SEQ, CANDM>), g, b, 0, c->stream, a);
+}
+// The wave-tile kernel of a plan, for a variant with the flows_5m rollup.  The sketch variants exist once per top-k contract
+// (the contract as a template argument: the exact mode's kernel carries no candidate test, the candidates mode's no probe of
+// the big sets in its tile loop - config 3: 1.15 -> 1.08 ms and 1.115 -> 1.055 ms per launch, same box); without sketch
+// segments, and in KS_ALL: the kernel that reads the contract from its arguments.  The learnt-order kernel: flows_5m alone.
+template <uint32_t KS>
+static void launch_wave_tiles(fa_ctx* c, const KArgs& a, const LaunchPlan& p) {
+    if constexpr ((KS & (FA_KEYS_SRCADDR_CMS | FA_KEYS_DSTADDR_CMS)) != 0u && KS != KS_ALL)
+        if (p.cms_segments) return c->cand_state ? launch_wtile<KS, false, 1>(c, a, p) : launch_wtile<KS, false, 0>(c, a, p);
+    if constexpr (KS == 1u)
+        if (p.seq_variant) return launch_wtile<1u, true>(c, a, p);
+    launch_wtile<KS>(c, a, p);
+}
 // Launch order on the ctx stream: tile -> deferred -> [agg]   (the wave-tile kernel finds the batch's time base itself).
 template <int MODE>
-static int launch_tiles(fa_ctx* c, KArgs& a, int grid, fa_ctx::LaunchEvents* ev = nullptr) {
-    dim3 b(BLOCK);
-    dim3 g(grid);
-    dim3 ge(std::min(256u, (a.n + BLOCK - 1) / BLOCK));
+static int launch_tiles(fa_ctx* c, KArgs& a, const LaunchPlan& p, fa_ctx::LaunchEvents* ev) {
+    // (wave tiles only with tuple segments, which only an ingest with the flows_5m rollup has)
+    if (p.wave_tiles && (MODE != MODE_INGEST || !(p.variant & FA_KEYS_AS_PAIR) || !a.seg)) return fail(c, FA_ERR_ARG, "internal: wave tiles without tuple segments");
+    const dim3 b(BLOCK), ge(std::min(256u, (a.n + BLOCK - 1) / BLOCK));
     a.par = c->par;
     c->par ^= 1u;
-    const bool wave_tiles = MODE == MODE_INGEST && a.seg != nullptr && c->use_wave_tiles;
-    const bool t8 = wave_tiles && c->use_t8;
-    // (the second-chance kernel runs in line: on a side stream beside the aggregation it cost MORE - 66 vs 58 us for
-    // deferred + aggregation per launch, the cross-stream hand-over being slower than the 4.5 us kernel - and its atomic
-    // upserts would race with the region-owned plain stores of agg8_kernel / cms_agg_kernel; the knob is gone)
-    hipStream_t dstream = c->stream;
     if (ev) (void)hipEventRecord(ev->e0, c->stream);
-    // most records of the last launches needed the order-free parser: the kernel that learns a field order per wave (ingest.cuh tier 4)
-    const bool seq_variant = wave_tiles && c->cfg.key_sets == FA_KEYS_AS_PAIR && c->seq_mode != 2 && (c->seq_mode == 1 || c->stats.batches < c->seq_until);
-    if (seq_variant) c->stats.learnt_order_launches += 1;
-    // the sketch variants exist once per top-k contract (the contract as a template argument: the exact mode's kernel carries no
-    // candidate test, the candidates mode's no probe of the big sets in its tile loop - config 3: 1.15 -> 1.08 ms and 1.115 -> 1.055 ms
-    // per launch, same box); without sketch segments: the kernel that reads the contract from its arguments
-    if (wave_tiles) c->stats.wave_tile_launches += 1;
-    if (t8) c->stats.compact_tuple_launches += 1;
+    if (p.seq_variant) c->stats.learnt_order_launches += 1;
+    if (p.wave_tiles) c->stats.wave_tile_launches += 1;
+    if (p.t8) c->stats.compact_tuple_launches += 1;
     // the bucket range of the wide tuples this launch leaves in its segments starts empty (Counters::wtb_min, wtb_nmax)
-    if (MODE == MODE_INGEST && wave_tiles && a.wseg) HIPCHK(c, hipMemsetAsync(&c->d_ctr->wtb_min, 0xff, 2 * sizeof(unsigned int), c->stream));
-#define FA_LAUNCH_W(KS)                                                                         \
-    do {                                                                                        \
-        if constexpr ((KS & 6u) != 0u && KS != KS_ALL) {  /* a sketch: a kernel per top-k contract */ \
-            if (a.cseg) {                                                      \
-                if (c->cand_state) {                                                            \
-                    if (t8) hipLaunchKernelGGL((wtile_kernel<KS, true, false, 1>), g, dim3(wtile_block<KS>()), 0, c->stream, a); \
-                    else hipLaunchKernelGGL((wtile_kernel<KS, false, false, 1>), g, dim3(wtile_block<KS>()), 0, c->stream, a);   \
-                } else {                                                                        \
-                    if (t8) hipLaunchKernelGGL((wtile_kernel<KS, true, false, 0>), g, dim3(wtile_block<KS>()), 0, c->stream, a); \
-                    else hipLaunchKernelGGL((wtile_kernel<KS, false, false, 0>), g, dim3(wtile_block<KS>()), 0, c->stream, a);   \
-                }                                                                               \
-                break;                                                                          \
-            }                                                                                   \
-        }                                                                                       \
-        if constexpr (KS == 1u) {                                                               \
-            if (seq_variant) {                                                                  \
-                if (t8) hipLaunchKernelGGL((wtile_kernel<1u, true, true>), g, dim3(wtile_block<1u>()), 0, c->stream, a); \
-                else hipLaunchKernelGGL((wtile_kernel<1u, false, true>), g, dim3(wtile_block<1u>()), 0, c->stream, a);   \
-                break;                                                                          \
-            }                                                                                   \
-        }                                                                                       \
-        if (t8) hipLaunchKernelGGL((wtile_kernel<KS, true>), g, dim3(wtile_block<KS>()), 0, c->stream, a); \
-        else hipLaunchKernelGGL((wtile_kernel<KS, false>), g, dim3(wtile_block<KS>()), 0, c->stream, a);   \
-    } while (0)
-#define FA_LAUNCH(KS)                                                                           \
-    case KS: {                                                                                  \
-        if constexpr (MODE == MODE_INGEST && (KS & FA_KEYS_AS_PAIR) != 0u) {                    \
-            if (wave_tiles) FA_LAUNCH_W(KS);                                                    \
-            else hipLaunchKernelGGL((tile_kernel<MODE, KS>), g, b, 0, c->stream, a);            \
-        } else { /* no flows_5m rollup = no scatter sink: the wave-tile kernel is never chosen, and not compiled */ \
-            hipLaunchKernelGGL((tile_kernel<MODE, KS>), g, b, 0, c->stream, a);                 \
-        }                                                                                       \
-        if (ev) (void)hipEventRecord(ev->e1, c->stream);                                        \
-        hipLaunchKernelGGL((deferred_kernel<MODE, KS>), ge, b, 0, dstream, a);                  \
-        break;                                                                                  \
-    }
-    if constexpr (MODE == MODE_DECODE) {
-        switch (1u) { FA_LAUNCH(1u) }
-    } else {
-        switch (c->cfg.key_sets) {
-            FA_LAUNCH(1u) FA_LAUNCH(2u) FA_LAUNCH(3u) FA_LAUNCH(4u) FA_LAUNCH(5u) FA_LAUNCH(6u) FA_LAUNCH(7u) FA_LAUNCH(9u)
-        default:  // any wide key set: the generic variant (runtime mask)
-            if (wave_tiles) FA_LAUNCH_W(KS_ALL);
-            else hipLaunchKernelGGL((tile_kernel<MODE, KS_ALL>), g, b, 0, c->stream, a);
-            if (ev) (void)hipEventRecord(ev->e1, c->stream);
-            hipLaunchKernelGGL((deferred_kernel<MODE, KS_ALL>), ge, b, 0, dstream, a);
-            break;
+    if (p.wide_segments) HIPCHK(c, hipMemsetAsync(&c->d_ctr->wtb_min, 0xff, 2 * sizeof(unsigned int), c->stream));
+    auto launch = [&](auto variant) {
+        constexpr uint32_t KS = decltype(variant)::value;
+        if (!p.wave_tiles) {
+            hipLaunchKernelGGL((tile_kernel<MODE, KS>), dim3(p.grid), b, 0, c->stream, a);
+        } else if constexpr (MODE == MODE_INGEST && (KS & FA_KEYS_AS_PAIR) != 0u) {  // (no other variant has a wave-tile kernel compiled)
+            launch_wave_tiles<KS>(c, a, p);
         }
-    }
-#undef FA_LAUNCH
-#undef FA_LAUNCH_W
+        if (ev) (void)hipEventRecord(ev->e1, c->stream);
+        // (the second-chance kernel runs in line: on a side stream beside the aggregation it cost MORE - 66 vs 58 us for
+        // deferred + aggregation per launch, the cross-stream hand-over being slower than the 4.5 us kernel - and its atomic
+        // upserts would race with the region-owned plain stores of agg8_kernel / cms_agg_kernel)
+        hipLaunchKernelGGL((deferred_kernel<MODE, KS>), ge, b, 0, c->stream, a);
+    };
+    if constexpr (MODE == MODE_DECODE) launch(std::integral_constant<uint32_t, 1u>{});  // (the one decode kernel that is compiled)
+    else with_variant(p.variant, launch);
     // Behind the ingest and second-chance kernels two chains that share nothing run side by side in the candidates mode:
     //   ctx stream   [fold the sketch tuples: cms_agg_kernel] -> [candidates mode: the launch boundary] -> [(SrcAddr,DstPort,Proto) tuples]
     //   side stream  [flows_5m tuple aggregation: agg8_kernel / agg_kernel]
     // The boundary's two small kernels (52 us of BASELINE config 3's 1.03 ms) and the tails of the two big ones - each one LDS-filling
     // workgroup per CU - overlap: 1.017-1.034 -> 0.966-0.983 ms per launch, same box (profiles/r06_exp_agg_side_stream.jsonl).
     // (candidates mode only: in the exact mode the two big kernels gain nothing from each other - measured 0 .. +1 % - and stay in line)
-    const bool side = MODE == MODE_INGEST && wave_tiles && a.cseg && c->cand_stream && c->cand_state;
     hipStream_t agg_stream = c->stream;
-    if (side) {
+    if (p.side) {
         HIPCHK(c, hipEventRecord(c->cand_ev[0], c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->cand_stream, c->cand_ev[0], 0));
         agg_stream = c->cand_stream;
     }
-    if (MODE == MODE_INGEST && a.seg) {
+    if (p.wave_tiles) {
         const dim3 ga(1u << a.plog2);
-        if (t8) hipLaunchKernelGGL(agg8_kernel, ga, dim3(AGG_BLOCK), 0, agg_stream, a);
+        if (p.t8) hipLaunchKernelGGL(agg8_kernel, ga, dim3(AGG_BLOCK), 0, agg_stream, a);
         else hipLaunchKernelGGL(agg_kernel, ga, dim3(AGG_BLOCK), 0, agg_stream, a);
     }
     // Nothing returns between the fork and the join: the ctx stream's part is a lambda, whose early returns (HIPCHK) end that
     // part only - on every way out of this launch the ctx stream waits for the side stream.
-    const hipError_t side_done = side ? hipEventRecord(c->cand_ev[1], c->cand_stream) : hipSuccess;
+    const hipError_t side_done = p.side ? hipEventRecord(c->cand_ev[1], c->cand_stream) : hipSuccess;
     const int rc = [&]() -> int {
-        if (MODE == MODE_INGEST && wave_tiles && a.cseg) {  // fold the sketch tuples (Count-Min scatter sink)
+        if (p.cms_segments) {  // fold the sketch tuples (Count-Min scatter sink)
             const uint32_t set_mask = (c->cfg.key_sets >> 1) & 3u;
             const uint32_t nlog = CMS_NPART * (set_mask == 3u ? 2u : 1u);
             hipLaunchKernelGGL(cms_agg_kernel, dim3(std::min<uint32_t>((uint32_t)c->num_cus, nlog)), dim3(AGG_BLOCK), 0, c->stream, a, set_mask, c->cms_par);  // persistent: one per CU
@@ -118,8 +88,8 @@ static int launch_tiles(fa_ctx* c, KArgs& a, int grid, fa_ctx::LaunchEvents* ev 
         }
         // fold the (SrcAddr,DstPort,Proto) tuples: one workgroup per table region, plain loads and stores - behind every
         // dispatch of this launch that updates the wide table with atomics (wagg.cuh)
-        if (MODE == MODE_INGEST && wave_tiles && a.wseg) {
-            if (c->wlog_now) {  // log mode: the tuples stay where they are (the chunk is taken over behind the launch: wlog_record)
+        if (p.wide_segments) {
+            if (p.wlog) {  // log mode: the tuples stay where they are (the chunk is taken over behind the launch: wlog_record)
                 // (the time base and the tuples' bucket range, three words: Counters::tb_base, wtb_min, wtb_nmax)
                 HIPCHK(c, hipMemcpyAsync(c->wseg_counts + fa_ctx::wcounts_cap(c->wseg_counts), &c->d_ctr->tb_base, 3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
             } else {
@@ -129,7 +99,7 @@ static int launch_tiles(fa_ctx* c, KArgs& a, int grid, fa_ctx::LaunchEvents* ev 
         return FA_OK;
     }();
     // the join: everything behind this launch sees the aggregated table (on the host if the stream cannot wait for it)
-    if (side && (side_done != hipSuccess || hipStreamWaitEvent(c->stream, c->cand_ev[1], 0) != hipSuccess)) {
+    if (p.side && (side_done != hipSuccess || hipStreamWaitEvent(c->stream, c->cand_ev[1], 0) != hipSuccess)) {
         (void)hipStreamSynchronize(c->cand_stream);
         if (rc == FA_OK) return fail(c, FA_ERR_HIP, "joining the side stream failed");
     }
@@ -137,22 +107,6 @@ static int launch_tiles(fa_ctx* c, KArgs& a, int grid, fa_ctx::LaunchEvents* ev 
     if (ev) (void)hipEventRecord(ev->e2, c->stream);
     HIPCHK(c, hipGetLastError());
     return FA_OK;
-}
-
-template <int MODE>
-static int tile_grid(fa_ctx* c, uint32_t n, uint32_t tile_recs) {
-    if constexpr (MODE == MODE_DECODE) return grid_for(c, tile_kernel<MODE_DECODE, 1u>, n, tile_recs);
-    switch (c->cfg.key_sets) {
-    case 1u: return grid_for(c, tile_kernel<MODE_INGEST, 1u>, n, tile_recs);
-    case 2u: return grid_for(c, tile_kernel<MODE_INGEST, 2u>, n, tile_recs);
-    case 3u: return grid_for(c, tile_kernel<MODE_INGEST, 3u>, n, tile_recs);
-    case 4u: return grid_for(c, tile_kernel<MODE_INGEST, 4u>, n, tile_recs);
-    case 5u: return grid_for(c, tile_kernel<MODE_INGEST, 5u>, n, tile_recs);
-    case 6u: return grid_for(c, tile_kernel<MODE_INGEST, 6u>, n, tile_recs);
-    case 7u: return grid_for(c, tile_kernel<MODE_INGEST, 7u>, n, tile_recs);
-    case 9u: return grid_for(c, tile_kernel<MODE_INGEST, 9u>, n, tile_recs);
-    default: return grid_for(c, tile_kernel<MODE_INGEST, KS_ALL>, n, tile_recs);
-    }
 }
 
 // deferral lists for n records: exotic [0,cap) and retry [cap,2cap)
@@ -164,11 +118,13 @@ static int ensure_exotic(fa_ctx* c, size_t n) {
     return FA_OK;
 }
 
-// Tuple segments for a batch of n records processed by nwg workgroups: capacity per (partition,
+// Tuple segments for a batch of n records processed by p.grid workgroups: capacity per (partition,
 // workgroup) = 2x the mean + 32 (a Poisson mean of m never reaches 2m+32; skewed batches overflow into
 // the direct path), in whole 128-byte lines (8 wide / 16 compact tuples).  The region stride gets a skew of
 // three lines so that consecutive partitions do not alias in L2.
-static int ensure_segments(fa_ctx* c, size_t n, uint32_t nwg, bool t8, KArgs& a) {
+static int ensure_segments(fa_ctx* c, size_t n, const LaunchPlan& p, KArgs& a) {
+    const uint32_t nwg = (uint32_t)p.grid;
+    const bool t8 = p.t8;
     const size_t NPART = (size_t)1 << c->plog2;
     const size_t avg = n / ((size_t)nwg * NPART);
     const uint32_t tpl = (t8 ? 2u : 1u) * bin_line(c->cfg.key_sets);  // tuples per store unit (a 128-byte line; flows_5m alone: half a line)
@@ -193,17 +149,18 @@ static int ensure_segments(fa_ctx* c, size_t n, uint32_t nwg, bool t8, KArgs& a)
     a.capb = std::min<uint32_t>(std::max<uint32_t>(2 * tpl, (capq / 4) & ~(tpl - 1)), 0xff00u - tpl);  // back part: single tuples, bin leftovers
     a.capb = std::min(a.capb, capq - tpl);
     a.capf = std::min<uint32_t>(capq - a.capb, 0xff00u * tpl);                                           // front part: full lines
-    a.nwg = nwg;
+    a.nwg = nwg;  // (of every scatter sink's segments: the sketch and wide sinks exist only beside this one)
     a.region = region;
     a.plog2 = c->plog2;
     c->last_nwg = nwg;
     return FA_OK;
 }
 
-// Segments of the Count-Min scatter sink for a batch of n records processed by nwg workgroups: per (sketch partition,
+// Segments of the Count-Min scatter sink for a batch of n records processed by p.grid workgroups: per (sketch partition,
 // workgroup) 3x the mean + 32 tuples of 16 bytes (a heavy hitter adds up to one tuple per wave-tile to its partition after
 // the wave-level fold: about as much again as the partition's mean; what still overflows is added with atomics).
-static int ensure_csegments(fa_ctx* c, size_t n, uint32_t nwg, KArgs& a) {
+static int ensure_csegments(fa_ctx* c, size_t n, const LaunchPlan& p, KArgs& a) {
+    const uint32_t nwg = (uint32_t)p.grid;
     const size_t nparts = (size_t)CMS_SETS * CMS_NPART;
     const size_t mean = n / ((size_t)CMS_NPART * nwg);
     uint32_t capq = (uint32_t)((3 * mean + 32 + 3) & ~(size_t)3);
@@ -246,9 +203,10 @@ static int ensure_csegments(fa_ctx* c, size_t n, uint32_t nwg, KArgs& a) {
     return FA_OK;
 }
 
-// Segments of the wide scatter sink for a batch of n records processed by nwg workgroups: per (table region, workgroup)
+// Segments of the wide scatter sink for a batch of n records processed by p.grid workgroups: per (table region, workgroup)
 // 2x the mean + 32 tuples of 32 bytes (what overflows - a heavy key's region - takes the atomic path).
-static int ensure_wsegments(fa_ctx* c, size_t n, uint32_t nwg, KArgs& a) {
+static int ensure_wsegments(fa_ctx* c, size_t n, const LaunchPlan& p, KArgs& a) {
+    const uint32_t nwg = (uint32_t)p.grid;
     const size_t nparts = (size_t)1 << a.wplog2;
     const size_t mean = n / (nparts * nwg);
     uint32_t capq = (uint32_t)(2 * mean + 32);
@@ -290,7 +248,6 @@ static int ensure_wsegments(fa_ctx* c, size_t n, uint32_t nwg, KArgs& a) {
     a.wseg_counts = c->wseg_counts;
     a.wcapq = capq;
     a.wregion = region;
-    a.nwg = nwg;
     return FA_OK;
 }
 
@@ -430,6 +387,20 @@ static int ingest_device_any(fa_ctx* c, const void* d_buf, size_t len, const voi
     return talk_fold_records(c, d_buf, len, (const uint32_t*)d_off, n);
 }
 
+// Room for one more launch's three events in a pool that settle hands back whole: afterwards pool[used] exists and the launch
+// takes it with used++ (a settle in between starts the pool over; the launch then takes its first triple).  A pool at its
+// limit is settled instead of grown; no event is destroyed before the ctx goes.
+static int acquire_events(fa_ctx* c, std::vector<fa_ctx::LaunchEvents>& pool, const size_t& used, size_t limit) {
+    if (used < pool.size()) return FA_OK;
+    if (pool.size() >= limit) return settle(c);  // bound the pool: fold what is pending
+    fa_ctx::LaunchEvents e{};
+    HIPCHK(c, hipEventCreate(&e.e0));
+    HIPCHK(c, hipEventCreate(&e.e1));
+    HIPCHK(c, hipEventCreate(&e.e2));
+    pool.push_back(e);
+    return FA_OK;
+}
+
 // the launch arguments that name a table (settle / rebuild_* replace them)
 static bool table_args_stale(const fa_ctx* c, const KArgs& a) {
     return a.tab != c->tab || a.mask != (1u << c->cap_log2) - 1 || a.wtab != c->wtab || a.wmask != (1u << c->wcap_log2) - 1;
@@ -473,13 +444,14 @@ static int ingest_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
             return FA_OK;
         }
     }
+    LaunchPlan p;
+    p.variant = ks_variant(c->cfg.key_sets);
     // small batches are not worth a second pass: they go straight to the device-wide table
-    const bool scatter = (c->cfg.key_sets & FA_KEYS_AS_PAIR) && (c->sink_mode == 2 || (c->sink_mode == 0 && n >= (1u << 15)));
-    c->use_wave_tiles = scatter;
+    p.wave_tiles = (c->cfg.key_sets & FA_KEYS_AS_PAIR) && (c->sink_mode == 2 || (c->sink_mode == 0 && n >= (1u << 15)));
     // tuple format of this launch (table.cuh): compact 8-byte tuples on the wave-tile kernel with 256 partitions,
     // unless recent launches showed that this stream's records do not fit them
-    c->use_t8 = c->use_wave_tiles && c->plog2 == 8 && c->t8_mode != 2 && (c->t8_mode == 1 || c->stats.batches >= c->t8_wide_until);
-    if (n > AGG_MAX_BATCH && !c->use_t8) {  // the packed LDS sums of the wide-tuple aggregation hold 2^24 records per launch
+    p.t8 = p.wave_tiles && c->plog2 == 8 && c->t8_mode != 2 && (c->t8_mode == 1 || c->stats.batches >= c->t8_wide_until);
+    if (n > AGG_MAX_BATCH && !p.t8) {  // the packed LDS sums of the wide-tuple aggregation hold 2^24 records per launch
         const size_t h = n / 2;
         int rc1 = ingest_device_records(c, d_buf, len, bytes / 2, d_off, h);
         if (rc1) return rc1;
@@ -489,77 +461,51 @@ static int ingest_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
     if (rc) return rc;
     rc = ensure_exotic(c, n);
     if (rc) return rc;
-    if (c->ev_used == c->ev_pool.size()) {
-        if (c->ev_pool.size() >= 4096) {  // bound the pool: fold what is pending
-            rc = settle(c);
-            if (rc) return rc;
-        } else {
-            fa_ctx::LaunchEvents e{};
-            HIPCHK(c, hipEventCreate(&e.e0));
-            HIPCHK(c, hipEventCreate(&e.e1));
-            HIPCHK(c, hipEventCreate(&e.e2));
-            c->ev_pool.push_back(e);
-        }
-    }
+    rc = acquire_events(c, c->ev_pool, c->ev_used, 4096);
+    if (rc) return rc;
     KArgs a = make_args(c);
     a.buf = (const uint8_t*)d_buf;
     a.off = (const uint32_t*)d_off;
     a.n = (uint32_t)n;
     a.len = (uint32_t)len;
-    a.tile_recs = tile_recs_for(bytes, n);
-    int grid = tile_grid<MODE_INGEST>(c, a.n, a.tile_recs);
-    if (c->use_wave_tiles) {  // wave-private tiles: <= 64 records per wave, WBLOCK / 64 waves per workgroup, WT_WG_PER_CU workgroups per CU
-        const double avg = (double)bytes / (double)n;
-        // Tiles are sized by RECORDS: 64 (one per lane) whenever the mean record allows, otherwise as many as fit the
-        // buffer with about two sigma of byte headroom (sigma of a tile ~ 12 B x sqrt(records): a mix of 60- and 84-byte
-        // records).  A tile whose bytes still exceed the buffer is not lost to the slow path any more: the wave takes
-        // its rest as one more part (ingest.cuh) - about 1 tile in 80 on BASELINE config 2, where this fills all 64
-        // lanes instead of 61.
-        // (the kernel variants that serve a sketch run one 16-wave workgroup per CU instead of two 12-wave ones, with
-        // slightly shorter tile buffers: wtile_block, wtile_stride)
-        const bool big_wg = !wt_lean(c->cfg.key_sets);
-        const uint32_t ks = c->cfg.key_sets;
-        auto recs_for = [&](double cap) {
-            double r = cap / avg;
-            r = (cap - 2.0 * 12.0 * std::sqrt(std::min(r, (double)WT_RECS))) / avg;
-            return r >= (double)WT_RECS ? (uint32_t)WT_RECS : r < 1.0 ? 1u : (uint32_t)r;
-        };
-        const double cap = (double)wt_stride((ks >= 1u && ks <= 7u) || ks == 9u ? ks : KS_ALL) - 16.0 - 15.0;  // (the instantiation launch_tiles picks)
-        a.tile_recs = recs_for(cap);
-        const uint32_t wtiles = (a.n + a.tile_recs - 1) / a.tile_recs;
-        const uint32_t waves = (uint32_t)(big_wg ? WBLOCK_CMS : WBLOCK) / 64u;
-        const uint32_t wgs = (wtiles + waves - 1) / waves;
-        grid = (int)std::max(1u, std::min<uint32_t>(wgs, (uint32_t)c->num_cus * (uint32_t)(big_wg ? 1 : WT_WG_PER_CU)));
-    }
-    if (scatter) {
-        rc = ensure_segments(c, n, (uint32_t)grid, c->use_t8, a);
-        if (rc) return rc;
-    }
-    if (c->use_wave_tiles && (c->cfg.key_sets & (FA_KEYS_SRCADDR_CMS | FA_KEYS_DSTADDR_CMS)) && !c->cms_atomic && c->cms_scatter_ok) {
-        rc = ensure_csegments(c, n, (uint32_t)grid, a);
-        if (rc) return rc;
-    }
-    if (c->use_wave_tiles && c->wtab && (c->cfg.key_sets & FA_KEYS_ADDR_PORT_PROTO) && grid <= WAGG_MAX_NWG &&
-        (c->wide_mode == 2 || c->wide_mode == 3 || (c->wide_mode == 0 && c->wide_scatter))) {
-        // (a segment-buffer pair that cannot be had folds the oldest log chunk - and that fold may settle, grow or rebuild a
-        // table: the launch arguments built above would then point at freed memory.  Rebuilt, and the segments sized again
-        // for the new region count, until nothing moved.)
-        for (int guard = 0;; guard++) {
-            rc = ensure_wsegments(c, n, (uint32_t)grid, a);
-            if (rc) return rc;
-            if (!table_args_stale(c, a)) break;
-            if (guard >= 4) return fail(c, FA_ERR_HIP, "internal: tables keep moving while a launch is prepared");
-            refresh_table_args(c, a);
-        }
-        c->wlog_now = c->wide_mode == 3 || (c->wide_mode == 0 && c->wide_defer);
+    if (p.wave_tiles) {  // wave-private tiles, sized by RECORDS
+        p.tile_recs = wtile_recs_for(bytes, n, p.variant);
+        p.grid = wtile_grid(a.n, p.tile_recs, p.variant, (uint32_t)c->num_cus);
     } else {
-        c->wlog_now = false;
+        p.tile_recs = tile_recs_for(bytes, n);
+        p.grid = with_variant(p.variant, [&](auto v) { return grid_for(c, tile_kernel<MODE_INGEST, decltype(v)::value>, a.n, p.tile_recs); });
     }
-    fa_ctx::LaunchEvents* evp = &c->ev_pool[c->ev_used++];
+    a.tile_recs = p.tile_recs;
+    p.cms_segments = p.wave_tiles && (c->cfg.key_sets & (FA_KEYS_SRCADDR_CMS | FA_KEYS_DSTADDR_CMS)) && !c->cms_atomic && c->cms_scatter_ok;
+    p.wide_segments = p.wave_tiles && c->wtab && (c->cfg.key_sets & FA_KEYS_ADDR_PORT_PROTO) && p.grid <= WAGG_MAX_NWG &&
+                      (c->wide_mode == 2 || c->wide_mode == 3 || (c->wide_mode == 0 && c->wide_scatter));
+    if (p.wave_tiles) {
+        rc = ensure_segments(c, n, p, a);
+        if (rc) return rc;
+    }
+    if (p.cms_segments) {
+        rc = ensure_csegments(c, n, p, a);
+        if (rc) return rc;
+    }
+    // (a segment-buffer pair that cannot be had folds the oldest log chunk - and that fold may settle, grow or rebuild a
+    // table: the launch arguments built above would then point at freed memory.  Rebuilt, and the segments sized again
+    // for the new region count, until nothing moved.)
+    for (int guard = 0; p.wide_segments; guard++) {
+        rc = ensure_wsegments(c, n, p, a);
+        if (rc) return rc;
+        if (!table_args_stale(c, a)) break;
+        if (guard >= 4) return fail(c, FA_ERR_HIP, "internal: tables keep moving while a launch is prepared");
+        refresh_table_args(c, a);
+    }
+    // (what the feedback rules say NOW: a settle inside the preparations above may have moved them)
+    p.wlog = p.wide_segments && (c->wide_mode == 3 || (c->wide_mode == 0 && c->wide_defer));
+    // most records of the last launches needed the order-free parser: the kernel that learns a field order per wave
+    p.seq_variant = p.wave_tiles && c->cfg.key_sets == FA_KEYS_AS_PAIR && c->seq_mode != 2 && (c->seq_mode == 1 || c->stats.batches < c->seq_until);
+    p.side = p.cms_segments && c->cand_stream && c->cand_state;
     if (c->wtab) c->wpot_total += (uint64_t)n * c->wide_per_record;  // (rows this launch may open in the wide table: wide_rows_bound)
-    rc = launch_tiles<MODE_INGEST>(c, a, grid, evp);
+    rc = launch_tiles<MODE_INGEST>(c, a, p, &c->ev_pool[c->ev_used++]);
     if (rc) return rc;
-    if (c->wlog_now && a.wseg) {
+    if (p.wlog) {
         rc = wlog_record(c, a, n);
         if (rc) return rc;
     } else if (c->wide_mode == 0 && !c->wide_defer && !c->wlog.empty()) {

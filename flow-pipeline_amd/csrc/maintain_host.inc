@@ -100,7 +100,7 @@ static int settle_wide(fa_ctx* c, Counters& h) {
 
 static int cms_fold(fa_ctx* c);
 
-// tuple-format feedback (fa_ctx::use_t8): h = counters at least as new as the last look
+// tuple-format feedback (what the next LaunchPlan::t8 is decided from): h = counters at least as new as the last look
 static void format_feedback(fa_ctx* c, const Counters& h) {
     const uint64_t d_mis = h.misfit8 - c->seen_misfit8, d_ok = h.ok - c->seen_ok;
     if (d_ok && d_mis * 16 > d_ok) c->t8_wide_until = c->stats.batches + 64;

@@ -45,7 +45,7 @@ static_assert(WBLOCK % 64 == 0 && WBLOCK >= 256 && WBLOCK <= 1024 && WT_STRIDE %
 // A bin = one store unit of tuples per key partition, in uint4 (16-byte) words: a whole 128-byte line (8) in every kernel
 // variant that serves a sketch or a wide key set (16 waves per workgroup; half-line bins measured -6 % there), half a
 // line (4 = 8 compact tuples) in the flows_5m-only variant (24 waves per CU, see FA_WBLOCK above).  One function for
-// the kernel templates and the host (segment geometry): what launch_tiles dispatches on is the key-set mask.
+// the kernel templates and the host (segment geometry): what the host dispatches on is ks_variant(mask) (launch_plan.h).
 static_assert(FA_BIN_BYTES == 128 || FA_BIN_BYTES == 64, "bin = one or half a cache line");
 // (wt_lean: the variants without a sketch - 12-wave workgroups, two per CU: flows_5m alone, and config 5's pair
 // flows_5m + (SrcAddr,DstPort,Proto); every other mask runs the 16-wave geometry, WBLOCK_CMS / WT_STRIDE_CMS)
@@ -74,7 +74,7 @@ constexpr uint32_t AGG8_MAX_BATCH = (1u << 25) - 1u;  // compact tuples (Packets
 static_assert(TILE_STRIDE % 16 == 0, "LDS tile buffers must stay 16-byte aligned");
 
 enum { MODE_INGEST = 0, MODE_DECODE = 1 };
-// Kernel variants are compiled for the key-set masks 1..7 (rollup and/or sketches); every other
+// Kernel variants are compiled for the key-set masks ks_variant (launch_plan.h) maps to themselves; every other
 // combination runs the KS_ALL variant, which parses the union of the columns and tests the runtime mask.
 constexpr uint32_t KS_ALL = 0xFFu;
 constexpr uint32_t FA_KEYS_WIDE = FA_KEYS_ADDR_PORT_PROTO | FA_KEYS_PORT_HIST | FA_KEYS_MINUTE_SERIES;

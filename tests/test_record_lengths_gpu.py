@@ -43,7 +43,7 @@ def _kind(ks):
     return "aspairs" if ks == 1 else "zipf"
 
 
-# ---- what the host computes (ingest_host.inc: recs_for; flowagg.hip: tile_recs_for), restated ------------------------
+# ---- what the host computes (launch_plan.h: wtile_recs_for, tile_recs_for), restated; test_launch_plan_cpu.py compares ----
 def _wt_tile_recs(nbytes, n, stride):
     avg = nbytes / n
     cap = stride - 16.0 - 15.0
