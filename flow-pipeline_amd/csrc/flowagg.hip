@@ -179,7 +179,6 @@ struct fa_ctx {
     DevBuf<> fs_scratch;      // device-side framing (framing.cuh): block starts, exits, counts, bases, error / trust flags, sub-block entries, counters
     DevBuf<> fs_off;          // ... the offsets it produces
     DevBuf<> wl_scratch;      // window reads of log chunks: per-segment counts, their scan, hipcub storage
-    void* read_clk = nullptr;        // FA_VERBOSE: the ReadClock of the read in progress (collect's own phases report into it)
     DevBuf<> part_buf;        // fa_rows_partition_device: the rows grouped by destination rank
     DevBuf<unsigned int> part_cnt;  // [3][RPART_MAX_WORLD]: counts, starts, cursors
     // fa_group_*: the buffer the group's exchange writes into (peer copies from the other members), owned by the ctx so that it

@@ -5,15 +5,28 @@
 // result out".  The same two steps are exported (fa_rows_device, fa_rows_merge_device) so that a multi-GPU window
 // close exchanges device buffers over RCCL and merges them without a host sort (flow-pipeline_amd/dist.py).
 
-static size_t row_bytes_of(int kind) {
+// The RowOps<K> a row kind runs - THE statement of that mapping: both port kinds share one instantiation, both top-k kinds
+// another.  f(std::integral_constant<int, K>{}); false for a kind that is none.
+template <class F>
+static bool with_row_kind(int kind, F&& f) {
     switch (kind) {
-    case RK_5M: return sizeof(Row5m);
-    case RK_APP: return sizeof(RowApp);
-    case RK_PORT_SRC: case RK_PORT_DST: case RK_MINUTE: return sizeof(RowW);
-    case RK_TOPK_SRC: case RK_TOPK_DST: return sizeof(TopkRow);
-    default: return 0;
+    case RK_5M: f(std::integral_constant<int, RK_5M>{}); return true;
+    case RK_APP: f(std::integral_constant<int, RK_APP>{}); return true;
+    case RK_PORT_SRC: case RK_PORT_DST: f(std::integral_constant<int, RK_PORT_SRC>{}); return true;
+    case RK_MINUTE: f(std::integral_constant<int, RK_MINUTE>{}); return true;
+    case RK_TOPK_SRC: case RK_TOPK_DST: f(std::integral_constant<int, RK_TOPK_SRC>{}); return true;
+    default: return false;
     }
 }
+static size_t row_bytes_of(int kind) {
+    size_t bytes = 0;
+    (void)with_row_kind(kind, [&](auto rk) { bytes = sizeof(typename RowOps<decltype(rk)::value>::Row); });
+    return bytes;
+}
+static_assert(sizeof(RowOps<RK_5M>::Row) == sizeof(Row5m) && sizeof(Row5m) == 48, "row layout");
+static_assert(sizeof(RowOps<RK_APP>::Row) == sizeof(RowApp) && sizeof(RowApp) == 56, "row layout");
+static_assert(sizeof(RowOps<RK_PORT_SRC>::Row) == sizeof(RowW) && sizeof(RowOps<RK_MINUTE>::Row) == sizeof(RowW) && sizeof(RowW) == 24, "row layout");
+static_assert(sizeof(RowOps<RK_TOPK_SRC>::Row) == sizeof(TopkRow) && sizeof(TopkRow) == 24, "row layout");
 extern "C" size_t fa_row_bytes(int kind) { return row_bytes_of(kind); }
 
 static int ensure_dev(fa_ctx* c, DevBuf<>& b, size_t bytes, const char* what) {
@@ -21,37 +34,99 @@ static int ensure_dev(fa_ctx* c, DevBuf<>& b, size_t bytes, const char* what) {
     c->err = std::string("hipMalloc(") + what + ") failed";
     return FA_ERR_NOMEM;
 }
+// ---- the small steps every read is made of --------------------------------------------------------------------------
+// one device word: zeroed in stream order / read back (copy, then synchronise).  Callers wrap them in HIPCHK.
+static hipError_t zero_word(unsigned int* d_word, hipStream_t s) { return hipMemsetAsync(d_word, 0, sizeof(unsigned int), s); }
+static hipError_t read_word(const unsigned int* d_word, unsigned int& v, hipStream_t s) {
+    const hipError_t e = hipMemcpyAsync(&v, d_word, sizeof v, hipMemcpyDeviceToHost, s);
+    return e != hipSuccess ? e : hipStreamSynchronize(s);
+}
+// does p point into buf?
+template <class B>
+static bool inside(const B& buf, const void* p) {
+    const uint8_t *b = (const uint8_t*)buf.get(), *q = (const uint8_t*)p;
+    return b && q >= b && q < b + buf.bytes();
+}
+static size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// hipcub's temporary storage for an exclusive scan of n words
+static size_t scan_tmp_bytes(fa_ctx* c, size_t n) {
+    size_t bytes = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, c->stream);
+    return bytes;
+}
+static dim3 grid_n(size_t n) { return dim3((unsigned)std::min<size_t>(2048, std::max<size_t>(1, (n + 255) / 256))); }
+// The buckets a read of `timeslot` covers and the timeslot its rows fold to: the sub-buckets of a sliding window sum into one
+// row per key (0xFFFFFFFF: no fold - tumbling windows, every timeslot).  false: not a bucket boundary - no rows.
+struct Window { uint32_t lo = 0, hi = 0, fold = 0xFFFFFFFFu; };
+static bool window_of(const fa_ctx* c, uint32_t timeslot, Window& w) {
+    w = Window{};
+    if (!bucket_range(c, timeslot, w.lo, w.hi)) return false;
+    if (timeslot != 0xFFFFFFFFu && c->gran != c->cfg.window_secs) w.fold = timeslot;
+    return true;
+}
 
-// ---- collect: rows of the device state, public format, unsorted, in c->rc_buf ----------------------------------------
-static int collect_5m(fa_ctx* c, uint32_t tb_lo, uint32_t tb_hi, size_t& n) {
+// ---- phase times of a read (FA_VERBOSE): collect / key bits / sort / heads + scan / reduce / emit order / copy out ----------
+// A read makes one and hands it by reference to everything that works for it; off, a mark is one branch.
+struct ReadClock {
+    hipStream_t stream;  // what a mark waits for (unless it names another)
+    bool on;
+    double t_last;
+    size_t n_in = 0;
+    std::string line;
+    static double now() {
+        timespec ts;
+        clock_gettime(CLOCK_MONOTONIC, &ts);
+        return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
+    }
+    explicit ReadClock(fa_ctx* c, bool enable = true) : stream(c->stream), on(enable && getenv("FA_VERBOSE") != nullptr), t_last(0) {
+        if (on) {
+            (void)hipStreamSynchronize(stream);
+            t_last = now();
+        }
+    }
+    void mark(const char* what, hipStream_t s = nullptr) {  // (the syncs cost a few us each: verbose runs only)
+        if (!on) return;
+        (void)hipStreamSynchronize(s ? s : stream);
+        const double t = now();
+        char buf[64];
+        snprintf(buf, sizeof buf, " %s %.2f", what, t - t_last);
+        line += buf;
+        t_last = t;
+    }
+    void done(const char* tag, size_t n_in, size_t n_out) {  // (no phase marked - a timeslot off the grid: nothing to say)
+        if (on && !line.empty()) fprintf(stderr, "[flowagg read] %s: %zu rows in, %zu out; ms:%s\n", tag, n_in, n_out, line.c_str());
+        line.clear();
+    }
+};
+
+// ---- collect: rows of the device state, public format, unsorted, in a buffer of the ctx (`in`, `n`) -------------------
+static int collect_5m(fa_ctx* c, ReadClock&, uint32_t tb_lo, uint32_t tb_hi, const void*& in, size_t& n) {
     int rc = settle(c);
     if (rc) return rc;
     const size_t need = std::max<uint64_t>(c->stats.table_used, 1024);
     rc = ensure_dev(c, c->rc_buf, need * sizeof(Row5m), "rows");
     if (rc) return rc;
-    HIPCHK(c, hipMemsetAsync(&c->d_ctr->rows_count, 0, sizeof(unsigned int), c->stream));
+    HIPCHK(c, zero_word(&c->d_ctr->rows_count, c->stream));
     hipLaunchKernelGGL(extract_kernel, dim3(1024), dim3(256), 0, c->stream, c->tab, 1u << c->cap_log2, c->gran, tb_lo, tb_hi,
                        (Row5m*)c->rc_buf, (uint32_t)need, c->d_ctr);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    in = c->rc_buf;
     n = c->h_ctr->rows_count;
     if (n > need) return fail(c, FA_ERR_HIP, "internal: row buffer too small");
     return FA_OK;
 }
+// The scratch collect_wide_raw wants for a window that lives in pending chunks: the tuple count (256 bytes), then per chunk
+// the live tuples of each of its nseg segments and their exclusive scan (wl_arr bytes each), then hipcub's temporary storage
+static size_t wl_arr(uint32_t nseg) { return align256((size_t)nseg * 4); }
+static size_t wl_scratch_bytes(size_t arrays_end, size_t tmp_scan) { return arrays_end + tmp_scan + 256; }
 // selected rows of the wide table (packed keys) into c->rc_buf
-static void read_mark(fa_ctx* c, const char* what);  // (FA_VERBOSE: a phase of the read in progress; below, with ReadClock)
-// the scratch collect_wide_raw wants for a window that lives in `chunks` pending chunks of nseg segments each
-static size_t wl_scratch_bytes(fa_ctx* c, uint32_t nseg, size_t chunks) {
-    size_t tmp_scan = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)nseg, c->stream);
-    return 256 + chunks * 2 * (((size_t)nseg * 4 + 255) & ~(size_t)255) + tmp_scan + 256;
-}
-static int collect_wide_raw(fa_ctx* c, uint32_t kind_mask, uint32_t tb_lo, uint32_t tb_hi, size_t& n, size_t extra_rows = 0) {
+static int collect_wide_raw(fa_ctx* c, ReadClock& clk, uint32_t kind_mask, uint32_t tb_lo, uint32_t tb_hi, size_t& n) {
     if (!c->wtab) return fail(c, FA_ERR_ARG, "key set not enabled");
     int rc = settle(c);
     if (rc) return rc;
-    read_mark(c, "settle");
+    clk.mark("settle");
     const size_t need = std::max<uint64_t>(c->stats.wide_used, 1024);
     // log mode: the pending chunks' tuples are rows of this key set as well (one per record; the merge behind this sums them).
     // Kafka partitions are close to time-ordered, so a window lives in one or two chunks: the others are not even scanned
@@ -69,27 +144,24 @@ static int collect_wide_raw(fa_ctx* c, uint32_t kind_mask, uint32_t tb_lo, uint3
         size_t sel_at, pos_at;  // byte offsets into wl_scratch
     };
     std::vector<Sel> sel;
+    size_t at = 256, tmp_max = 0;
     if ((kind_mask & (1u << WK_APP)) && !c->wlog.empty()) {
         rc = wlog_bucket_ranges(c);
         if (rc) return rc;
-        read_mark(c, "chunk ranges");
-        size_t at = 256, tmp_max = 0;  // (the first 256 bytes: the tuple count)
+        clk.mark("chunk ranges");
         for (const auto& k : c->wlog) {
             if (!chunk_in_range(k)) continue;
             const uint32_t nseg = (1u << k.wplog2) * k.nwg;
-            const size_t arr = ((size_t)nseg * 4 + 255) & ~(size_t)255;
-            size_t tmp_scan = 0;
-            (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)nseg, c->stream);
-            tmp_max = std::max(tmp_max, tmp_scan);
-            sel.push_back(Sel{&k, nseg, at, at + arr});
-            at += 2 * arr;
+            sel.push_back(Sel{&k, nseg, at, at + wl_arr(nseg)});
+            at += 2 * wl_arr(nseg);
+            tmp_max = std::max(tmp_max, scan_tmp_bytes(c, nseg));
         }
         if (!sel.empty()) {
-            rc = ensure_dev(c, c->wl_scratch, at + tmp_max + 256, "log row scratch");
+            rc = ensure_dev(c, c->wl_scratch, wl_scratch_bytes(at, tmp_max), "log row scratch");
             if (rc) return rc;
             uint8_t* sb = (uint8_t*)c->wl_scratch;
             unsigned int* total = (unsigned int*)sb;
-            HIPCHK(c, hipMemsetAsync(total, 0, sizeof(unsigned int), c->stream));
+            HIPCHK(c, zero_word(total, c->stream));
             for (const Sel& q : sel) {
                 uint32_t* seg_sel = (uint32_t*)(sb + q.sel_at);
                 uint32_t* seg_pos = (uint32_t*)(sb + q.pos_at);
@@ -100,16 +172,15 @@ static int collect_wide_raw(fa_ctx* c, uint32_t kind_mask, uint32_t tb_lo, uint3
             }
             HIPCHK(c, hipGetLastError());
             unsigned int h_total = 0;
-            HIPCHK(c, hipMemcpyAsync(&h_total, total, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, read_word(total, h_total, c->stream));
             pending = h_total;
-            read_mark(c, "count");
+            clk.mark("count");
         }
     }
-    if (need + pending + extra_rows >= (1ull << 32)) return fail(c, FA_ERR_CAPACITY, "too many wide rows for one read");
-    rc = ensure_dev(c, c->rc_buf, (need + pending + extra_rows) * sizeof(WRow), "wide rows");
+    if (need + pending >= (1ull << 32)) return fail(c, FA_ERR_CAPACITY, "too many wide rows for one read");
+    rc = ensure_dev(c, c->rc_buf, (need + pending) * sizeof(WRow), "wide rows");
     if (rc) return rc;
-    HIPCHK(c, hipMemsetAsync(&c->d_ctr->wrows_count, 0, sizeof(unsigned int), c->stream));
+    HIPCHK(c, zero_word(&c->d_ctr->wrows_count, c->stream));
     hipLaunchKernelGGL(wextract_kernel, dim3(512), dim3(WX_BLOCK), 0, c->stream, c->wtab, 1u << c->wcap_log2, kind_mask, tb_lo, tb_hi,
                        (WRow*)c->rc_buf, (uint32_t)need, c->d_ctr);
     for (const Sel& q : sel) {  // the selected tuples behind the table's rows, every segment at its place (no atomics, no holes)
@@ -125,47 +196,10 @@ static int collect_wide_raw(fa_ctx* c, uint32_t kind_mask, uint32_t tb_lo, uint3
     HIPCHK(c, hipStreamSynchronize(c->stream));
     n = c->h_ctr->wrows_count;
     if (n > need + pending) return fail(c, FA_ERR_HIP, "internal: wide row buffer too small");
-    read_mark(c, "extract");
+    clk.mark("extract");
     return FA_OK;
 }
 static int ensure_pinned(fa_ctx* c, size_t result_bytes);
-static dim3 grid_n(size_t n) { return dim3((unsigned)std::min<size_t>(2048, std::max<size_t>(1, (n + 255) / 256))); }
-
-// ---- phase times of a read (FA_VERBOSE): collect / key bits / sort / heads + scan / reduce / emit order / copy out ----------
-struct ReadClock {
-    fa_ctx* c;
-    bool on;
-    double t_last;
-    size_t n_in = 0;
-    std::string line;
-    static double now() {
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
-    }
-    explicit ReadClock(fa_ctx* ctx) : c(ctx), on(getenv("FA_VERBOSE") != nullptr), t_last(0) {
-        if (on) {
-            (void)hipStreamSynchronize(c->stream);
-            t_last = now();
-        }
-    }
-    void mark(const char* what) {  // (the syncs cost a few us each: verbose runs only)
-        if (!on) return;
-        (void)hipStreamSynchronize(c->stream);
-        const double t = now();
-        char buf[64];
-        snprintf(buf, sizeof buf, " %s %.2f", what, t - t_last);
-        line += buf;
-        t_last = t;
-    }
-    void done(const char* tag, size_t n_in, size_t n_out) {
-        if (on) fprintf(stderr, "[flowagg read] %s: %zu rows in, %zu out; ms:%s\n", tag, n_in, n_out, line.c_str());
-        line.clear();
-    }
-};
-static void read_mark(fa_ctx* c, const char* what) {
-    if (c->read_clk) ((ReadClock*)c->read_clk)->mark(what);
-}
 
 // ---- merge: sort, sum equal keys, emit order; result in c->m_out[*] (or the pinned host buffer) -------------------
 struct SortScratch {
@@ -177,17 +211,17 @@ struct SortScratch {
 };
 // the permutation that puts n rows into the kind's merge order (EMIT: emit order): varying bits only (merge.cuh, RowPlan)
 template <int KIND, bool EMIT>
-static int rows_sort_order(fa_ctx* c, const typename RowOps<KIND>::Row* rows, uint32_t n, uint32_t fold, const SortScratch& s, uint32_t** perm, uint32_t* bits_sorted) {
+static int rows_sort_order(fa_ctx* c, hipStream_t stream, const typename RowOps<KIND>::Row* rows, uint32_t n, uint32_t fold, const SortScratch& s, uint32_t** perm, uint32_t* bits_sorted) {
     typedef RowOps<KIND> Ops;
     constexpr int NW = EMIT ? Ops::NK2 : Ops::NK;
     static_assert(NW >= 1 && NW <= RP_MAX_WORDS, "key words");
     const dim3 g = grid_n(n), b(256);
-    HIPCHK(c, hipMemsetAsync(s.bits, 0, NW * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(s.bits + NW, 0xff, NW * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL((row_bits_kernel<KIND, EMIT>), g, b, 0, c->stream, rows, n, fold, s.bits);
+    HIPCHK(c, hipMemsetAsync(s.bits, 0, NW * sizeof(unsigned long long), stream));
+    HIPCHK(c, hipMemsetAsync(s.bits + NW, 0xff, NW * sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL((row_bits_kernel<KIND, EMIT>), g, b, 0, stream, rows, n, fold, s.bits);
     unsigned long long h[2 * RP_MAX_WORDS];
-    HIPCHK(c, hipMemcpyAsync(h, s.bits, 2 * NW * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(h, s.bits, 2 * NW * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
     int wbits[RP_MAX_WORDS];
     for (int w = 0; w < NW; w++) {
         if constexpr (EMIT) wbits[w] = Ops::bits2(w);
@@ -200,15 +234,15 @@ static int rows_sort_order(fa_ctx* c, const typename RowOps<KIND>::Row* rows, ui
     for (uint32_t p = 0; p < plan.nwords; p++) {
         uint32_t* src = cur ? cur : s.ia;  // (identity is written into ia by the first pass)
         uint32_t* dst = src == s.ia ? s.ib : s.ia;
-        hipLaunchKernelGGL((row_pack_kernel<KIND, EMIT>), g, b, 0, c->stream, rows, (const uint32_t*)cur, n, fold, plan, p, s.ka, s.ia);
+        hipLaunchKernelGGL((row_pack_kernel<KIND, EMIT>), g, b, 0, stream, rows, (const uint32_t*)cur, n, fold, plan, p, s.ka, s.ia);
         size_t tb = s.tmp_bytes;
-        if (hipcub::DeviceRadixSort::SortPairs(s.tmp, tb, s.ka, s.kb, src, dst, (int)n, 0, (int)plan.bits[p], c->stream) != hipSuccess)
+        if (hipcub::DeviceRadixSort::SortPairs(s.tmp, tb, s.ka, s.kb, src, dst, (int)n, 0, (int)plan.bits[p], stream) != hipSuccess)
             return fail(c, FA_ERR_HIP, "radix sort failed");
         cur = dst;
         *bits_sorted += plan.bits[p];
     }
     if (!cur) {  // every key equal (or one row): any order is the order
-        hipLaunchKernelGGL(iota_kernel, g, b, 0, c->stream, s.ia, n);
+        hipLaunchKernelGGL(iota_kernel, g, b, 0, stream, s.ia, n);
         cur = s.ia;
     }
     HIPCHK(c, hipGetLastError());
@@ -218,13 +252,12 @@ static int rows_sort_order(fa_ctx* c, const typename RowOps<KIND>::Row* rows, ui
 
 // the sort / scan scratch of a merge of n rows: 2 key arrays, 4 index arrays, hipcub's temporary storage, the key-bit words
 static size_t merge_scratch_bytes(fa_ctx* c, uint32_t n, size_t& karr, size_t& iarr, size_t& tmp_bytes) {
-    size_t tmp_sort = 0, tmp_scan = 0;
+    size_t tmp_sort = 0;
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
                                              (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 64, c->stream);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, c->stream);
-    tmp_bytes = (std::max(tmp_sort, tmp_scan) + 255) & ~(size_t)255;
-    karr = ((size_t)n * 8 + 255) & ~(size_t)255;
-    iarr = ((size_t)n * 4 + 255) & ~(size_t)255;
+    tmp_bytes = align256(std::max(tmp_sort, scan_tmp_bytes(c, n)));
+    karr = align256((size_t)n * 8);
+    iarr = align256((size_t)n * 4);
     return 2 * karr + 4 * iarr + tmp_bytes + 256;
 }
 // The buffers a window read of `rows` (SrcAddr,DstPort,Proto) rows will want - collected rows, sort scratch, merged rows, the
@@ -238,7 +271,7 @@ static void reserve_window_read(fa_ctx* c, uint64_t rows, uint32_t nseg) {
     if (c->group_members > 1) rows = std::min<uint64_t>(rows + rows / 8, (1ull << 31) - 2048);
     const std::string keep = c->err;
     // (a window lives in one or two chunks; three when a close lags)
-    if (nseg) (void)ensure_dev(c, c->wl_scratch, wl_scratch_bytes(c, nseg, 3), "log row scratch");
+    if (nseg) (void)ensure_dev(c, c->wl_scratch, wl_scratch_bytes(256 + 3 * 2 * wl_arr(nseg), scan_tmp_bytes(c, nseg)), "log row scratch");
     size_t karr, iarr, tmp_bytes;
     const size_t scratch_bytes = merge_scratch_bytes(c, (uint32_t)rows, karr, iarr, tmp_bytes);
     const bool grow = c->rc_buf.bytes() < rows * sizeof(WRow) || c->m_scratch.bytes() < scratch_bytes || c->m_out[0].bytes() < rows * sizeof(RowApp);
@@ -266,8 +299,8 @@ static void reserve_window_read(fa_ctx* c, uint64_t rows, uint32_t nseg) {
     c->err = keep;
 }
 template <int KIND>
-static int rows_merge_t(fa_ctx* c, const void* d_rows, size_t n_in, uint32_t fold, size_t k, const void** out, size_t* n_out,
-                        bool to_host = false, bool* in_host = nullptr, ReadClock* clk = nullptr) {
+static int rows_merge_t(fa_ctx* c, hipStream_t stream, ReadClock& clk, const void* d_rows, size_t n_in, uint32_t fold, size_t k, const void** out, size_t* n_out,
+                        bool to_host = false, bool* in_host = nullptr) {
     typedef typename RowOps<KIND>::Row Row;
     typedef RowOps<KIND> Ops;
     if (in_host) *in_host = false;
@@ -279,9 +312,7 @@ static int rows_merge_t(fa_ctx* c, const void* d_rows, size_t n_in, uint32_t fol
     const Row* rows = (const Row*)d_rows;
     // (the caller's rows may be this ctx's own result of an earlier call - one rank feeding fa_rows_device's pointer back
     // in: the buffers below are about to be reused)
-    for (int q = 0; q < 2; q++)
-        if (c->m_out[q] && (const uint8_t*)d_rows >= (const uint8_t*)c->m_out[q] && (const uint8_t*)d_rows < (const uint8_t*)c->m_out[q] + c->m_out[q].bytes())
-            return fail(c, FA_ERR_ARG, "rows to merge alias the ctx's result buffer (copy them first)");
+    if (inside(c->m_out[0], d_rows) || inside(c->m_out[1], d_rows)) return fail(c, FA_ERR_ARG, "rows to merge alias the ctx's result buffer (copy them first)");
     size_t karr, iarr, tmp_bytes;
     const size_t scratch_bytes = merge_scratch_bytes(c, n, karr, iarr, tmp_bytes);
     int rc = ensure_dev(c, c->m_scratch, scratch_bytes, "merge scratch");
@@ -301,23 +332,23 @@ static int rows_merge_t(fa_ctx* c, const void* d_rows, size_t n_in, uint32_t fol
     const dim3 g = grid_n(n), b(256);
     uint32_t* cur = nullptr;
     uint32_t sorted_bits = 0;
-    rc = rows_sort_order<KIND, false>(c, rows, n, fold, ss, &cur, &sorted_bits);
+    rc = rows_sort_order<KIND, false>(c, stream, rows, n, fold, ss, &cur, &sorted_bits);
     if (rc) return rc;
-    if (clk) {
+    if (clk.on) {
         char what[32];
         snprintf(what, sizeof what, "sort(%u bits)", sorted_bits);
-        clk->mark(what);
+        clk.mark(what, stream);
     }
-    hipLaunchKernelGGL((row_heads_kernel<KIND>), g, b, 0, c->stream, rows, (const uint32_t*)cur, n, fold, flags);
+    hipLaunchKernelGGL((row_heads_kernel<KIND>), g, b, 0, stream, rows, (const uint32_t*)cur, n, fold, flags);
     {
         size_t tb = tmp_bytes;
-        if (hipcub::DeviceScan::ExclusiveSum(tmp, tb, flags, pos, (int)n, c->stream) != hipSuccess) return fail(c, FA_ERR_HIP, "scan failed");
+        if (hipcub::DeviceScan::ExclusiveSum(tmp, tb, flags, pos, (int)n, stream) != hipSuccess) return fail(c, FA_ERR_HIP, "scan failed");
     }
     uint32_t last[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(&last[0], flags + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&last[1], pos + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (clk) clk->mark("heads+scan");
+    HIPCHK(c, hipMemcpyAsync(&last[0], flags + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipMemcpyAsync(&last[1], pos + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
+    clk.mark("heads+scan", stream);
     const uint32_t m = last[0] + last[1];  // groups
     const size_t m_emit = (k && k < m) ? k : m;
     const bool host = to_host && c->h_rows && m_emit * sizeof(Row) <= c->h_rows.bytes();
@@ -326,74 +357,55 @@ static int rows_merge_t(fa_ctx* c, const void* d_rows, size_t n_in, uint32_t fol
     // the groups' rows: heads sum the first RUN_SERIAL rows of their run; longer runs (only a caller's degenerate input has
     // them) are finished with atomics by a second kernel, which needs the rows in device memory
     unsigned int* long_runs = &c->d_ctr->rows_count;
-    HIPCHK(c, hipMemsetAsync(long_runs, 0, sizeof(unsigned int), c->stream));
+    HIPCHK(c, zero_word(long_runs, stream));
     auto reduce_into = [&](Row* dst) -> int {
-        hipLaunchKernelGGL((row_reduce_kernel<KIND>), g, b, 0, c->stream, rows, (const uint32_t*)cur, (const uint32_t*)flags, (const uint32_t*)pos, n, fold, dst, long_runs);
+        hipLaunchKernelGGL((row_reduce_kernel<KIND>), g, b, 0, stream, rows, (const uint32_t*)cur, (const uint32_t*)flags, (const uint32_t*)pos, n, fold, dst, long_runs);
         HIPCHK(c, hipGetLastError());
         return FA_OK;
     };
     auto finish_long_runs = [&](Row* dst) -> int {  // dst: device memory
         unsigned int lr = 0;
-        HIPCHK(c, hipMemcpyAsync(&lr, long_runs, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, read_word(long_runs, lr, stream));
         if (lr) {
-            hipLaunchKernelGGL((row_tail_kernel<KIND>), g, b, 0, c->stream, rows, (const uint32_t*)cur, (const uint32_t*)flags, (const uint32_t*)pos, n, dst);
+            hipLaunchKernelGGL((row_tail_kernel<KIND>), g, b, 0, stream, rows, (const uint32_t*)cur, (const uint32_t*)flags, (const uint32_t*)pos, n, dst);
             HIPCHK(c, hipGetLastError());
         }
         return FA_OK;
     };
     const bool may_be_long = n > m && (uint64_t)n >= (uint64_t)RUN_SERIAL;  // (a run of RUN_SERIAL rows needs at least that many rows)
-    if (Ops::NK2 == 0) {
-        // straight into the pinned host buffer only when no run can be long (the atomics of row_tail_kernel want device memory)
-        Row* dst = (host && m_emit == m && !may_be_long) ? (Row*)c->h_rows : (Row*)c->m_out[0];
-        rc = reduce_into(dst);
+    // a kind without an emit order is done with the reduce: straight into the pinned host buffer when no run can be long (the
+    // atomics of row_tail_kernel want device memory)
+    Row* red = (Ops::NK2 == 0 && host && m_emit == m && !may_be_long) ? (Row*)c->h_rows : (Row*)c->m_out[0];
+    rc = reduce_into(red);
+    if (rc) return rc;
+    if (may_be_long) {
+        rc = finish_long_runs(red);
         if (rc) return rc;
-        if (may_be_long) {
-            rc = finish_long_runs(dst);
-            if (rc) return rc;
-        }
-        if (clk) clk->mark("reduce");
-        if (in_host) *in_host = dst == (Row*)c->h_rows;
-        *out = dst;
-        *n_out = m_emit;
-        return FA_OK;
     }
-    if constexpr (Ops::NK2 > 0) {
-        Row* red = (Row*)c->m_out[0];
-        rc = reduce_into(red);
-        if (rc) return rc;
-        if (may_be_long) {
-            rc = finish_long_runs(red);
-            if (rc) return rc;
-        }
-        if (clk) clk->mark("reduce");
-        // emit order: a second sort over the groups
+    clk.mark("reduce", stream);
+    Row* dst = red;
+    if constexpr (Ops::NK2 > 0) {  // emit order: a second sort over the groups
         uint32_t* cur2 = nullptr;
-        rc = rows_sort_order<KIND, true>(c, (const Row*)red, m, fold, ss, &cur2, &sorted_bits);
+        rc = rows_sort_order<KIND, true>(c, stream, (const Row*)red, m, fold, ss, &cur2, &sorted_bits);
         if (rc) return rc;
         rc = ensure_dev(c, c->m_out[1], m_emit * sizeof(Row), "ordered rows");
         if (rc) return rc;
-        Row* dst = host ? (Row*)c->h_rows : (Row*)c->m_out[1];
-        hipLaunchKernelGGL((row_gather_kernel<Row>), grid_n(m_emit), b, 0, c->stream, (const Row*)red, (const uint32_t*)cur2, (uint32_t)m_emit, dst);
+        dst = host ? (Row*)c->h_rows : (Row*)c->m_out[1];
+        hipLaunchKernelGGL((row_gather_kernel<Row>), grid_n(m_emit), b, 0, stream, (const Row*)red, (const uint32_t*)cur2, (uint32_t)m_emit, dst);
         HIPCHK(c, hipGetLastError());
-        if (clk) clk->mark("emit order");
-        if (in_host) *in_host = host;
-        *out = dst;
-        *n_out = m_emit;
+        clk.mark("emit order", stream);
     }
+    if (in_host) *in_host = dst == (Row*)c->h_rows;
+    *out = dst;
+    *n_out = m_emit;
     return FA_OK;
 }
 
-static int rows_merge(fa_ctx* c, int kind, const void* d_rows, size_t n, uint32_t fold, size_t k, const void** out, size_t* n_out,
-                      bool to_host = false, bool* in_host = nullptr, ReadClock* clk = nullptr) {
-    switch (kind) {
-    case RK_5M: return rows_merge_t<RK_5M>(c, d_rows, n, fold, k, out, n_out, to_host, in_host, clk);
-    case RK_APP: return rows_merge_t<RK_APP>(c, d_rows, n, fold, k, out, n_out, to_host, in_host, clk);
-    case RK_PORT_SRC: case RK_PORT_DST: return rows_merge_t<RK_PORT_SRC>(c, d_rows, n, fold, k, out, n_out, to_host, in_host, clk);
-    case RK_MINUTE: return rows_merge_t<RK_MINUTE>(c, d_rows, n, fold, k, out, n_out, to_host, in_host, clk);
-    case RK_TOPK_SRC: case RK_TOPK_DST: return rows_merge_t<RK_TOPK_SRC>(c, d_rows, n, fold, k, out, n_out, to_host, in_host, clk);
-    default: return fail(c, FA_ERR_ARG, "unknown row kind");
-    }
+static int rows_merge(fa_ctx* c, hipStream_t stream, ReadClock& clk, int kind, const void* d_rows, size_t n, uint32_t fold, size_t k, const void** out, size_t* n_out,
+                      bool to_host = false, bool* in_host = nullptr) {
+    int rc = FA_OK;
+    const bool known = with_row_kind(kind, [&](auto rk) { rc = rows_merge_t<decltype(rk)::value>(c, stream, clk, d_rows, n, fold, k, out, n_out, to_host, in_host); });
+    return known ? rc : fail(c, FA_ERR_ARG, "unknown row kind");
 }
 
 static int kind_enabled(fa_ctx* c, int kind) {
@@ -408,198 +420,188 @@ static int kind_enabled(fa_ctx* c, int kind) {
     }
 }
 
-// The ctx's own result for (kind, timeslot): what the matching read call returns, left in HBM (or, to_host, written
-// straight into the pinned host buffer when it fits).  lo/hi: the bucket range that was read (window kinds).
 static const char* const ROW_KIND_NAMES[RK_COUNT] = {"flows_5m", "(SrcAddr,DstPort,Proto)", "SrcPort", "DstPort", "minutes", "top-k SrcAddr", "top-k DstAddr"};
-static int rows_local(fa_ctx* c, int kind, uint32_t timeslot, size_t k, const void** out, size_t* n_out, uint32_t& lo, uint32_t& hi,
-                      bool to_host = false, bool* in_host = nullptr, ReadClock* clk = nullptr) {
+static const char* row_kind_name(int kind) { return ROW_KIND_NAMES[kind < 0 || kind >= RK_COUNT ? 0 : kind]; }
+
+// (SrcAddr,DstPort,Proto) rows of the buckets [lo, hi): the wide table's (and the pending chunks') rows, unpacked in place
+static int collect_app(fa_ctx* c, ReadClock& clk, uint32_t lo, uint32_t hi, const void*& in, size_t& n) {
+    int rc = collect_wide_raw(c, clk, 1u << WK_APP, lo, hi, n);
+    if (rc) return rc;
+    if (n) hipLaunchKernelGGL(wrows_to_app_kernel, grid_n(n), dim3(256), 0, c->stream, (WRow*)c->rc_buf, (uint32_t)n, c->gran);
+    in = c->rc_buf;
+    return FA_OK;
+}
+// GROUP BY port / the minute series: the wide table's rows as RowW in c->rw_buf, the dense ports' rows behind them
+static int collect_w(fa_ctx* c, ReadClock& clk, int kind, const void*& in, size_t& n) {
+    const bool port = kind != RK_MINUTE;
+    const int dst = kind == RK_PORT_DST;
+    int rc = collect_wide_raw(c, clk, 1u << (kind == RK_MINUTE ? WK_MINUTE : dst ? WK_DSTPORT : WK_SRCPORT), 0, 0, n);
+    if (rc) return rc;
+    const size_t cap_rows = n + (port ? PORT_DENSE : 0) + 16;
+    rc = ensure_dev(c, c->rw_buf, cap_rows * sizeof(RowW), "port / minute rows");
+    if (rc) return rc;
+    if (n) hipLaunchKernelGGL(wrows_to_w_kernel, grid_n(n), dim3(256), 0, c->stream, (const WRow*)c->rc_buf, (uint32_t)n, port ? 1u : 60u, (RowW*)c->rw_buf);
+    if (port) {
+        HIPCHK(c, zero_word(&c->d_ctr->rows_count, c->stream));
+        hipLaunchKernelGGL(port_dense_rows_kernel, dim3(64), dim3(256), 0, c->stream, c->port_hist + (size_t)dst * PORT_DENSE, (uint32_t)PORT_DENSE,
+                           (RowW*)c->rw_buf + n, &c->d_ctr->rows_count);
+        unsigned int nd = 0;
+        HIPCHK(c, read_word(&c->d_ctr->rows_count, nd, c->stream));
+        n += nd;
+    }
+    in = c->rw_buf;
+    return FA_OK;
+}
+
+// ---- fa_topk's collection: k rows out of millions - only the rows that can be among the first k leave the set ----------
+struct TopkSet {  // one direction's distinct-address set and the sketch its estimates come from
+    KeySlot* ks;
+    const unsigned long long* cms;
+    uint32_t nslots;
+};
+// ONE scan of the whole set: the rows whose estimate reaches lb_bin (0: every row) into c->rc_buf, room for cap_rows of them
+// (almost every key stops at its row-0 counter) -> how many there were (more than cap_rows: the caller's call)
+static int topk_scan_rows(fa_ctx* c, const TopkSet& t, uint32_t lb_bin, size_t cap_rows, unsigned int& nr) {
+    int rc = ensure_dev(c, c->rc_buf, cap_rows * sizeof(TopkRow), "top-k rows");
+    if (rc) return rc;
+    HIPCHK(c, zero_word(&c->d_ctr->ks_rows, c->stream));
+    hipLaunchKernelGGL(topk_scan_kernel<TK_ONE>, dim3(1024), dim3(256), 0, c->stream, t.ks, t.nslots, t.cms, c->cfg.cms_depth, c->cfg.cms_width_log2, c->cfg.cms_seed, lb_bin,
+                       (unsigned int*)nullptr, (unsigned short*)nullptr, (TopkRow*)c->rc_buf, (uint32_t)cap_rows, c->d_ctr);
+    HIPCHK(c, read_word(&c->d_ctr->ks_rows, nr, c->stream));
+    return FA_OK;
+}
+// histogram of the estimates' bins over the first ns slots (grid workgroups), then the bin that holds rank sel_k:
+// sel[0] that bin, sel[1] the rows in the bins >= it, sel[2] the rows held; the chunks' largest bins are left in c->rw_buf
+static int topk_threshold(fa_ctx* c, const TopkSet& t, uint32_t ns, unsigned grid, size_t sel_k, unsigned int (&sel)[3], const unsigned short** chunkmax) {
+    const size_t cm_bytes = align256((size_t)(ns >> 6) * sizeof(unsigned short));
+    int rc = ensure_dev(c, c->rw_buf, (TK_BINS + 4) * sizeof(unsigned int) + cm_bytes, "top-k histogram");
+    if (rc) return rc;
+    unsigned int* hist = (unsigned int*)c->rw_buf;
+    unsigned short* cmax = (unsigned short*)(hist + TK_BINS + 4);
+    HIPCHK(c, hipMemsetAsync(hist, 0, (TK_BINS + 4) * sizeof(unsigned int), c->stream));
+    hipLaunchKernelGGL(topk_scan_kernel<TK_HIST>, dim3(grid), dim3(256), 0, c->stream, t.ks, ns, t.cms, c->cfg.cms_depth, c->cfg.cms_width_log2, c->cfg.cms_seed, 0u, hist, cmax,
+                       (TopkRow*)nullptr, 0u, c->d_ctr);
+    hipLaunchKernelGGL(topk_thresh_kernel, dim3(1), dim3(256), 0, c->stream, (const unsigned int*)hist, (uint32_t)sel_k, hist + TK_BINS);
+    HIPCHK(c, hipMemcpyAsync(sel, hist + TK_BINS, sizeof sel, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *chunkmax = cmax;
+    return FA_OK;
+}
+// The rows that can be among the first sel_k (k: what the caller asked for; sel_k > k: a retry, see rows_local), tried in
+// this order - each arm that does not settle it falls through to the next:
+//  1. a bin the k-th estimate is known to reach (the k-th row of an earlier read of this sketch and view: estimates and sets
+//     only grow): ONE scan;
+//  2. no such bin (a first read, a new view, a larger k) and a set of 2^18 slots or more: the k-th estimate of a SAMPLE is a
+//     lower bound of the k-th estimate of the set - the first 1 / 64 of the slots hold a hash-uniform 1 / 64 of the keys - and
+//     one scan of the whole set with that bin replaces the full-depth scan (40 M random sketch reads on BASELINE config 3's sets);
+//  3. histogram of the estimates' bins -> the bin that holds rank k -> the rows of that bin and above, found through the
+//     chunks' largest bins;
+//  4. every row (k = 0, k >= the slots).
+// partial: rows were left behind.
+static int collect_topk(fa_ctx* c, ReadClock& clk, int kind, size_t k, size_t sel_k, bool& partial, const void*& in, size_t& n) {
+    const int d = kind == RK_TOPK_DST;
+    int rc = settle(c);
+    if (rc) return rc;
+    if (c->h_ctr->ks_overflow) return fail(c, FA_ERR_TABLE_FULL, "fa_topk: distinct-address set overflowed (raise topk_capacity_log2)");
+    const TopkSet t{d ? c->ks_dst : c->ks_src, cms_of(c, d ? FA_KEYS_DSTADDR_CMS : FA_KEYS_SRCADDR_CMS), 1u << c->ks_log2};
+    const bool merged_now = c->merged_valid && (d ? c->cms_dst_m : c->cms_src_m) != nullptr;
+    const bool lb_ok = c->tk_lb_k[d] != 0 && sel_k != 0 && sel_k <= c->tk_lb_k[d] && c->tk_lb_merged[d] == merged_now && sel_k == k;
+    partial = false;
+    unsigned int nr = 0, sel[3] = {0, 0, 0};
+    const unsigned short* chunkmax = nullptr;
+    bool done = false;
+    if (lb_ok) {
+        const size_t cap_rows = std::max<size_t>(8 * sel_k, 1u << 16);
+        rc = topk_scan_rows(c, t, c->tk_lb_bin[d], cap_rows, nr);
+        if (rc) return rc;
+        done = nr <= cap_rows && nr >= sel_k;  // (more rows than room, or fewer than k - a reset nobody told us about: the long way)
+        partial = true;
+        if (!done) c->tk_lb_k[d] = 0;
+        clk.mark("one pass");
+    }
+    if (!done && sel_k && sel_k == k && sel_k <= 4096 && t.nslots >= (1u << 18)) {
+        rc = topk_threshold(c, t, t.nslots >> 6, 256, sel_k, sel, &chunkmax);
+        if (rc) return rc;
+        clk.mark("sample");
+        if (sel[2] >= sel_k && sel[0] > 0) {
+            const size_t cap_rows = std::max<size_t>(256 * sel_k, 1u << 16);
+            rc = topk_scan_rows(c, t, sel[0], cap_rows, nr);
+            if (rc) return rc;
+            done = nr <= cap_rows;  // (a stream whose estimates crowd one bin: the histogram of the whole set decides)
+            partial = true;
+            clk.mark("one pass");
+        }
+    }
+    if (!done && sel_k && sel_k < t.nslots) {
+        rc = topk_threshold(c, t, t.nslots, 1024, sel_k, sel, &chunkmax);
+        if (rc) return rc;
+        clk.mark("estimates");
+        const size_t cap_rows = std::max<size_t>(sel[1], 1);
+        partial = sel[1] < sel[2];
+        rc = ensure_dev(c, c->rc_buf, cap_rows * sizeof(TopkRow), "top-k rows");
+        if (rc) return rc;
+        HIPCHK(c, zero_word(&c->d_ctr->ks_rows, c->stream));
+        hipLaunchKernelGGL(topk_pick_kernel, dim3(256), dim3(256), 0, c->stream, (const KeySlot*)t.ks, t.nslots, chunkmax, sel[0], (TopkRow*)c->rc_buf, (uint32_t)cap_rows, c->d_ctr);
+        HIPCHK(c, read_word(&c->d_ctr->ks_rows, nr, c->stream));
+        if (nr > cap_rows) return fail(c, FA_ERR_HIP, "internal: top-k row buffer too small");
+        done = true;
+    }
+    if (!done) {  // every row
+        rc = topk_scan_rows(c, t, 0u, t.nslots, nr);
+        if (rc) return rc;
+    }
+    in = c->rc_buf;
+    n = nr;
+    return FA_OK;
+}
+
+// The ctx's own result for (kind, timeslot): what the matching read call returns, left in HBM (or, to_host, written
+// straight into the pinned host buffer when it fits): the window, then collect, then merge.
+static int rows_local(fa_ctx* c, ReadClock& clk, int kind, uint32_t timeslot, size_t k, const void** out, size_t* n_out, bool to_host = false, bool* in_host = nullptr) {
     *out = nullptr;
     *n_out = 0;
-    lo = hi = 0;
     if (in_host) *in_host = false;
     int rc = kind_enabled(c, kind);
     if (rc) return rc;
-    ReadClock own(c);
-    if (!clk) clk = &own;
-    struct ClockScope {  // collect_*'s own phases report into this read's clock
-        fa_ctx* c;
-        void* prev;
-        ClockScope(fa_ctx* ctx, ReadClock* k) : c(ctx), prev(ctx->read_clk) { c->read_clk = k->on ? k : nullptr; }
-        ~ClockScope() { c->read_clk = prev; }
-    } clock_scope(c, clk);
-    size_t n = 0;
-    const bool windowed = kind == RK_5M || kind == RK_APP;
-    uint32_t fold = 0xFFFFFFFFu;
-    if (windowed) {
-        if (!bucket_range(c, timeslot, lo, hi)) {
-            lo = hi = 0;
-            return FA_OK;  // not a bucket boundary: no rows
-        }
-        if (timeslot != 0xFFFFFFFFu && c->gran != c->cfg.window_secs) fold = timeslot;
-    }
+    Window w;
+    if ((kind == RK_5M || kind == RK_APP) && !window_of(c, timeslot, w)) return FA_OK;  // not a bucket boundary: no rows
+    const bool topk = kind == RK_TOPK_SRC || kind == RK_TOPK_DST;
+    const int d = kind == RK_TOPK_DST;
     const void* in = nullptr;
-    size_t sel_k = k;        // top-k kinds: rows the collection has to keep (grows when duplicate keys ate into the first k)
-    bool sel_partial = false;  // ... and whether it left rows behind
-again:
-    switch (kind) {
-    case RK_5M:
-        rc = collect_5m(c, lo, hi, n);
-        in = c->rc_buf;
-        break;
-    case RK_APP:
-        rc = collect_wide_raw(c, 1u << WK_APP, lo, hi, n);
-        if (!rc && n) hipLaunchKernelGGL(wrows_to_app_kernel, grid_n(n), dim3(256), 0, c->stream, (WRow*)c->rc_buf, (uint32_t)n, c->gran);
-        in = c->rc_buf;
-        break;
-    case RK_PORT_SRC: case RK_PORT_DST: case RK_MINUTE: {
-        const bool port = kind != RK_MINUTE;
-        const int dst = kind == RK_PORT_DST;
-        rc = collect_wide_raw(c, 1u << (kind == RK_MINUTE ? WK_MINUTE : dst ? WK_DSTPORT : WK_SRCPORT), 0, 0, n);
-        if (rc) break;
-        const size_t cap_rows = n + (port ? PORT_DENSE : 0) + 16;
-        rc = ensure_dev(c, c->rw_buf, cap_rows * sizeof(RowW), "port / minute rows");
-        if (rc) break;
-        if (n) hipLaunchKernelGGL(wrows_to_w_kernel, grid_n(n), dim3(256), 0, c->stream, (const WRow*)c->rc_buf, (uint32_t)n, port ? 1u : 60u, (RowW*)c->rw_buf);
-        if (port) {
-            HIPCHK(c, hipMemsetAsync(&c->d_ctr->rows_count, 0, sizeof(unsigned int), c->stream));
-            hipLaunchKernelGGL(port_dense_rows_kernel, dim3(64), dim3(256), 0, c->stream, c->port_hist + (size_t)dst * PORT_DENSE, (uint32_t)PORT_DENSE,
-                               (RowW*)c->rw_buf + n, &c->d_ctr->rows_count);
-            unsigned int nd = 0;
-            HIPCHK(c, hipMemcpyAsync(&nd, &c->d_ctr->rows_count, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            n += nd;
+    size_t n = 0;
+    // top-k kinds: sel_k rows the collection has to keep, and whether it left rows behind.  The distinct-address set may (rarely)
+    // hold a key twice (sinks.cuh, keyset_step): the merge keeps it once, and when that leaves fewer than k rows although the
+    // collection cut some off, it collects again with more room.
+    size_t sel_k = k;
+    bool sel_partial = false, again;
+    do {
+        switch (kind) {
+        case RK_5M: rc = collect_5m(c, clk, w.lo, w.hi, in, n); break;
+        case RK_APP: rc = collect_app(c, clk, w.lo, w.hi, in, n); break;
+        case RK_PORT_SRC: case RK_PORT_DST: case RK_MINUTE: rc = collect_w(c, clk, kind, in, n); break;
+        case RK_TOPK_SRC: case RK_TOPK_DST: rc = collect_topk(c, clk, kind, k, sel_k, sel_partial, in, n); break;
+        default: return fail(c, FA_ERR_ARG, "unknown row kind");
         }
-        in = c->rw_buf;
-        break;
-    }
-    case RK_TOPK_SRC: case RK_TOPK_DST: {
-        const uint32_t key_set = kind == RK_TOPK_SRC ? FA_KEYS_SRCADDR_CMS : FA_KEYS_DSTADDR_CMS;
-        unsigned long long* cms = cms_of(c, key_set);
-        KeySlot* ks = kind == RK_TOPK_SRC ? c->ks_src : c->ks_dst;
-        rc = settle(c);
-        if (rc) break;
-        if (c->h_ctr->ks_overflow) return fail(c, FA_ERR_TABLE_FULL, "fa_topk: distinct-address set overflowed (raise topk_capacity_log2)");
-        const uint32_t nslots = 1u << c->ks_log2;
-        const int d = kind == RK_TOPK_DST;
-        const bool merged_now = c->merged_valid && (d ? c->cms_dst_m : c->cms_src_m) != nullptr;
-        // k rows out of millions: only the rows that can be among the first k leave the set (maintenance.cuh).
-        //  * a bin the k-th estimate is known to reach (the k-th row of an earlier read of this sketch and view: estimates and
-        //    sets only grow): ONE scan, almost every key stops at its row-0 counter;
-        //  * otherwise: histogram of the estimates' bins -> the bin that holds rank k -> the rows of that bin and above, found
-        //    through the chunks' largest bins;   * k = 0: every row.
-        const bool lb_ok = c->tk_lb_k[d] != 0 && sel_k != 0 && sel_k <= c->tk_lb_k[d] && c->tk_lb_merged[d] == merged_now && sel_k == k;
-        sel_partial = false;
-        unsigned int nr = 0;
-        bool done = false;
-        if (lb_ok) {
-            const size_t cap_rows = std::max<size_t>(8 * sel_k, 1u << 16);
-            rc = ensure_dev(c, c->rc_buf, cap_rows * sizeof(TopkRow), "top-k rows");
-            if (rc) break;
-            HIPCHK(c, hipMemsetAsync(&c->d_ctr->ks_rows, 0, sizeof(unsigned int), c->stream));
-            hipLaunchKernelGGL(topk_scan_kernel<TK_ONE>, dim3(1024), dim3(256), 0, c->stream, ks, nslots, (const unsigned long long*)cms, c->cfg.cms_depth, c->cfg.cms_width_log2,
-                               c->cfg.cms_seed, c->tk_lb_bin[d], (unsigned int*)nullptr, (unsigned short*)nullptr, (TopkRow*)c->rc_buf, (uint32_t)cap_rows, c->d_ctr);
-            HIPCHK(c, hipMemcpyAsync(&nr, &c->d_ctr->ks_rows, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            done = nr <= cap_rows && nr >= sel_k;  // (more rows than room, or fewer than k - a reset nobody told us about: the long way)
-            sel_partial = true;
-            if (!done) c->tk_lb_k[d] = 0;
-            clk->mark("one pass");
+        if (rc) return rc;
+        HIPCHK(c, hipGetLastError());
+        clk.mark("collect");
+        rc = rows_merge(c, c->stream, clk, kind, in, n, w.fold, k, out, n_out, to_host, in_host);
+        again = !rc && topk && k && *n_out < k && sel_partial;
+        if (again) {
+            sel_k = std::max<size_t>(2 * sel_k, sel_k + 64);
+            c->tk_lb_k[d] = 0;
         }
-        if (!done && sel_k && sel_k == k && sel_k <= 4096 && nslots >= (1u << 18)) {
-            // no remembered bin (a first read, a new view, a larger k): the k-th estimate of a SAMPLE is a lower bound of the k-th
-            // estimate of the set - the first 1 / 64 of the slots hold a hash-uniform 1 / 64 of the keys - and one scan of the whole
-            // set with that bin (row-0 early-out) replaces the full-depth scan (40 M random sketch reads on BASELINE config 3's sets)
-            const uint32_t ns = nslots >> 6;
-            const size_t cm_bytes = ((size_t)(ns >> 6) * sizeof(unsigned short) + 255) & ~(size_t)255;
-            rc = ensure_dev(c, c->rw_buf, (TK_BINS + 4) * sizeof(unsigned int) + cm_bytes, "top-k histogram");
-            if (rc) break;
-            unsigned int* hist = (unsigned int*)c->rw_buf;
-            HIPCHK(c, hipMemsetAsync(hist, 0, (TK_BINS + 4) * sizeof(unsigned int), c->stream));
-            hipLaunchKernelGGL(topk_scan_kernel<TK_HIST>, dim3(256), dim3(256), 0, c->stream, ks, ns, (const unsigned long long*)cms, c->cfg.cms_depth, c->cfg.cms_width_log2,
-                               c->cfg.cms_seed, 0u, hist, (unsigned short*)(hist + TK_BINS + 4), (TopkRow*)nullptr, 0u, c->d_ctr);
-            hipLaunchKernelGGL(topk_thresh_kernel, dim3(1), dim3(256), 0, c->stream, (const unsigned int*)hist, (uint32_t)sel_k, hist + TK_BINS);
-            unsigned int sel[3] = {0, 0, 0};
-            HIPCHK(c, hipMemcpyAsync(sel, hist + TK_BINS, sizeof sel, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            clk->mark("sample");
-            if (sel[2] >= sel_k && sel[0] > 0) {
-                const size_t cap_rows = std::max<size_t>(256 * sel_k, 1u << 16);
-                rc = ensure_dev(c, c->rc_buf, cap_rows * sizeof(TopkRow), "top-k rows");
-                if (rc) break;
-                HIPCHK(c, hipMemsetAsync(&c->d_ctr->ks_rows, 0, sizeof(unsigned int), c->stream));
-                hipLaunchKernelGGL(topk_scan_kernel<TK_ONE>, dim3(1024), dim3(256), 0, c->stream, ks, nslots, (const unsigned long long*)cms, c->cfg.cms_depth,
-                                   c->cfg.cms_width_log2, c->cfg.cms_seed, sel[0], (unsigned int*)nullptr, (unsigned short*)nullptr, (TopkRow*)c->rc_buf, (uint32_t)cap_rows, c->d_ctr);
-                HIPCHK(c, hipMemcpyAsync(&nr, &c->d_ctr->ks_rows, 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                done = nr <= cap_rows;  // (a stream whose estimates crowd one bin: the histogram of the whole set decides)
-                sel_partial = true;
-                clk->mark("one pass");
-            }
-        }
-        if (!done && sel_k && sel_k < nslots) {
-            const size_t cm_bytes = ((size_t)(nslots >> 6) * sizeof(unsigned short) + 255) & ~(size_t)255;
-            rc = ensure_dev(c, c->rw_buf, (TK_BINS + 4) * sizeof(unsigned int) + cm_bytes, "top-k histogram");
-            if (rc) break;
-            unsigned int* hist = (unsigned int*)c->rw_buf;
-            unsigned short* chunkmax = (unsigned short*)(hist + TK_BINS + 4);
-            HIPCHK(c, hipMemsetAsync(hist, 0, (TK_BINS + 4) * sizeof(unsigned int), c->stream));
-            hipLaunchKernelGGL(topk_scan_kernel<TK_HIST>, dim3(1024), dim3(256), 0, c->stream, ks, nslots, (const unsigned long long*)cms, c->cfg.cms_depth, c->cfg.cms_width_log2,
-                               c->cfg.cms_seed, 0u, hist, chunkmax, (TopkRow*)nullptr, 0u, c->d_ctr);
-            hipLaunchKernelGGL(topk_thresh_kernel, dim3(1), dim3(256), 0, c->stream, (const unsigned int*)hist, (uint32_t)sel_k, hist + TK_BINS);
-            unsigned int sel[3] = {0, 0, 0};
-            HIPCHK(c, hipMemcpyAsync(sel, hist + TK_BINS, sizeof sel, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            clk->mark("estimates");
-            const size_t cap_rows = std::max<size_t>(sel[1], 1);
-            sel_partial = sel[1] < sel[2];
-            rc = ensure_dev(c, c->rc_buf, cap_rows * sizeof(TopkRow), "top-k rows");
-            if (rc) break;
-            HIPCHK(c, hipMemsetAsync(&c->d_ctr->ks_rows, 0, sizeof(unsigned int), c->stream));
-            hipLaunchKernelGGL(topk_pick_kernel, dim3(256), dim3(256), 0, c->stream, (const KeySlot*)ks, nslots, (const unsigned short*)chunkmax, sel[0], (TopkRow*)c->rc_buf,
-                               (uint32_t)cap_rows, c->d_ctr);
-            HIPCHK(c, hipMemcpyAsync(&nr, &c->d_ctr->ks_rows, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (nr > cap_rows) return fail(c, FA_ERR_HIP, "internal: top-k row buffer too small");
-            done = true;
-        }
-        if (!done) {  // every row
-            rc = ensure_dev(c, c->rc_buf, (size_t)nslots * sizeof(TopkRow), "top-k rows");
-            if (rc) break;
-            HIPCHK(c, hipMemsetAsync(&c->d_ctr->ks_rows, 0, sizeof(unsigned int), c->stream));
-            hipLaunchKernelGGL(topk_scan_kernel<TK_ONE>, dim3(1024), dim3(256), 0, c->stream, ks, nslots, (const unsigned long long*)cms, c->cfg.cms_depth, c->cfg.cms_width_log2,
-                               c->cfg.cms_seed, 0u, (unsigned int*)nullptr, (unsigned short*)nullptr, (TopkRow*)c->rc_buf, nslots, c->d_ctr);
-            HIPCHK(c, hipMemcpyAsync(&nr, &c->d_ctr->ks_rows, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
-        n = nr;
-        in = c->rc_buf;
-        break;
-    }
-    default: return fail(c, FA_ERR_ARG, "unknown row kind");
-    }
-    if (rc) return rc;
-    HIPCHK(c, hipGetLastError());
-    clk->mark("collect");
-    rc = rows_merge(c, kind, in, n, fold, k, out, n_out, to_host, in_host, clk);
-    // the distinct-address set may (rarely) hold a key twice (sinks.cuh, keyset_step): the merge keeps it once, and when that
-    // leaves fewer than k rows although the collection cut some off, it collects again with more room
-    if (!rc && (kind == RK_TOPK_SRC || kind == RK_TOPK_DST) && k && *n_out < k && sel_partial) {
-        sel_k = std::max<size_t>(2 * sel_k, sel_k + 64);
-        c->tk_lb_k[kind == RK_TOPK_DST] = 0;
-        goto again;
-    }
-    if (!rc && (kind == RK_TOPK_SRC || kind == RK_TOPK_DST) && k && *n_out == k) {
+    } while (again);
+    if (!rc && topk && k && *n_out == k) {
         // the k-th row's estimate: a bin every later read of this sketch and view (for k' <= k) knows its k'-th estimate reaches
-        const int d = kind == RK_TOPK_DST;
-        unsigned long long w = 0;
-        HIPCHK(c, hipMemcpyAsync(&w, (const uint8_t*)*out + (k - 1) * sizeof(TopkRow) + offsetof(TopkRow, weight), sizeof w, hipMemcpyDefault, c->stream));
+        unsigned long long weight = 0;
+        HIPCHK(c, hipMemcpyAsync(&weight, (const uint8_t*)*out + (k - 1) * sizeof(TopkRow) + offsetof(TopkRow, weight), sizeof weight, hipMemcpyDefault, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->tk_lb_bin[d] = topk_bin(w);
+        c->tk_lb_bin[d] = topk_bin(weight);
         c->tk_lb_k[d] = k;
         c->tk_lb_merged[d] = c->merged_valid && (d ? c->cms_dst_m : c->cms_src_m) != nullptr;
     }
-    if (clk == &own) clk->done(ROW_KIND_NAMES[kind], n, *n_out);
-    else clk->n_in = n;
+    clk.n_in = n;
     return rc;
 }
 
@@ -693,12 +695,12 @@ static int rows_copy_out(fa_ctx* c, const void* d, size_t n, size_t row_bytes, b
     }
     return copy_out_pipelined(c, out, d, n * row_bytes);
 }
-static int rows_read(fa_ctx* c, int kind, uint32_t timeslot, size_t k, void* out, size_t cap, size_t* n_out, uint32_t& lo, uint32_t& hi) {
+static int rows_read(fa_ctx* c, int kind, uint32_t timeslot, size_t k, void* out, size_t cap, size_t* n_out) {
     const void* d = nullptr;
     size_t n = 0;
     bool in_host = false;
     ReadClock clk(c);
-    int rc = rows_local(c, kind, timeslot, k, &d, &n, lo, hi, true, &in_host, &clk);
+    int rc = rows_local(c, clk, kind, timeslot, k, &d, &n, true, &in_host);
     if (rc) return rc;
     if (n > cap) {  // (the caller asks again with room for *n_out rows; nothing was removed)
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -711,7 +713,7 @@ static int rows_read(fa_ctx* c, int kind, uint32_t timeslot, size_t k, void* out
     }
     rc = rows_copy_out(c, d, n, row_bytes_of(kind), in_host, out, cap, n_out);
     clk.mark("copy out");
-    clk.done(ROW_KIND_NAMES[kind], clk.n_in, n);
+    clk.done(row_kind_name(kind), clk.n_in, n);
     return rc;
 }
 
@@ -757,8 +759,7 @@ static int rows_read_app48_split(fa_ctx* c, size_t n, uint32_t fold, void* out, 
     hipLaunchKernelGGL(app_cut_kernel, dim3(1024), dim3(APP_CUT_BLOCK), 0, c->stream, rows, (uint32_t)n, pivot, (RowApp*)c->cut_buf, d_cnt);
     HIPCHK(c, hipGetLastError());
     unsigned int na = 0;
-    HIPCHK(c, hipMemcpyAsync(&na, d_cnt, sizeof na, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, read_word(d_cnt, na, c->stream));
     clk.mark("cut");
     rc = ensure_dev(c, c->m_out[1], n * sizeof(RowApp48), "packed rows");  // (at most n rows come out)
     if (rc) return rc;
@@ -769,24 +770,16 @@ static int rows_read_app48_split(fa_ctx* c, size_t n, uint32_t fold, void* out, 
     // The copies stay on the ctx's own stream (its copy engine knows the caller's pages: on a second stream the first window's copy
     // took 3 ms longer); the SECOND half's kernels run on the other stream, behind the first half's (they share the merge scratch).
     hipStream_t const main_stream = c->stream;
-    struct StreamSwap {  // c->stream is what every merge step launches on
-        fa_ctx* c;
-        hipStream_t keep;
-        StreamSwap(fa_ctx* ctx, hipStream_t s) : c(ctx), keep(ctx->stream) { c->stream = s; }
-        ~StreamSwap() { c->stream = keep; }
-    };
     for (int h = 0; h < 2; h++) {
         if (!part_n[h]) continue;
         const void* d = nullptr;
         size_t m = 0;
-        {
-            StreamSwap on(c, h ? c->copy_stream : main_stream);
-            if (h) HIPCHK(c, hipStreamWaitEvent(c->stream, c->copy_ev[0], 0));  // (behind the first half's pack; recorded below, or never: no first half)
-            rc = rows_merge_t<RK_APP>(c, (const RowApp*)c->cut_buf + (h ? na : 0), part_n[h], fold, 0, &d, &m, false, nullptr, &clk);
-            if (!rc && done + m <= cap) {
-                hipLaunchKernelGGL(row_app48_kernel, grid_n(m), dim3(256), 0, c->stream, (const RowApp*)d, (uint32_t)m, packed + done);
-                if (hipGetLastError() != hipSuccess || hipEventRecord(c->copy_ev[h], c->stream) != hipSuccess) rc = fail(c, FA_ERR_HIP, "pack of a half failed");
-            }
+        hipStream_t const on = h ? c->copy_stream : main_stream;
+        if (h) HIPCHK(c, hipStreamWaitEvent(on, c->copy_ev[0], 0));  // (behind the first half's pack; recorded below, or never: no first half)
+        rc = rows_merge(c, on, clk, RK_APP, (const RowApp*)c->cut_buf + (h ? na : 0), part_n[h], fold, 0, &d, &m);
+        if (!rc && done + m <= cap) {
+            hipLaunchKernelGGL(row_app48_kernel, grid_n(m), dim3(256), 0, on, (const RowApp*)d, (uint32_t)m, packed + done);
+            if (hipGetLastError() != hipSuccess || hipEventRecord(c->copy_ev[h], on) != hipSuccess) rc = fail(c, FA_ERR_HIP, "pack of a half failed");
         }
         if (rc) break;
         if (done + m > cap) {  // (what has left already is the front of the result; the caller asks again with room for every row)
@@ -812,19 +805,13 @@ static int rows_read_app48(fa_ctx* c, uint32_t timeslot, void* out, size_t cap, 
     if (rc) return rc;
     *n_out = 0;
     if (date_out) *date_out = timeslot / 86400u;
-    uint32_t lo, hi;
-    if (!bucket_range(c, timeslot, lo, hi)) return FA_OK;  // not a bucket boundary: no rows
-    const uint32_t fold = c->gran != c->cfg.window_secs ? timeslot : 0xFFFFFFFFu;
+    Window w;
+    if (!window_of(c, timeslot, w)) return FA_OK;  // not a bucket boundary: no rows
     ReadClock clk(c);
-    struct ClockScope {
-        fa_ctx* c;
-        ClockScope(fa_ctx* ctx, ReadClock* k) : c(ctx) { c->read_clk = k->on ? k : nullptr; }
-        ~ClockScope() { c->read_clk = nullptr; }
-    } clock_scope(c, &clk);
+    const void* in = nullptr;
     size_t n = 0;
-    rc = collect_wide_raw(c, 1u << WK_APP, lo, hi, n);
+    rc = collect_app(c, clk, w.lo, w.hi, in, n);
     if (rc) return rc;
-    if (n) hipLaunchKernelGGL(wrows_to_app_kernel, grid_n(n), dim3(256), 0, c->stream, (WRow*)c->rc_buf, (uint32_t)n, c->gran);
     HIPCHK(c, hipGetLastError());
     clk.mark("collect");
     clk.n_in = n;
@@ -832,13 +819,13 @@ static int rows_read_app48(fa_ctx* c, uint32_t timeslot, void* out, size_t cap, 
     size_t split_min = APP48_SPLIT_MIN;
     if (const char* e = getenv("FA_APP48_SPLIT")) split_min = !strcmp(e, "0") ? ~(size_t)0 : std::max<size_t>(4096, strtoull(e, nullptr, 0));
     if (n >= split_min && n < ((size_t)1 << 31) - 1024 && cap && host_pinned(out, cap * sizeof(RowApp48))) {
-        rc = rows_read_app48_split(c, n, fold, out, cap, n_out, clk);
+        rc = rows_read_app48_split(c, n, w.fold, out, cap, n_out, clk);
         clk.done("(SrcAddr,DstPort,Proto) 48-byte rows, in two halves", clk.n_in, *n_out);
         return rc;
     }
     const void* d = nullptr;
     size_t m = 0;
-    rc = rows_merge(c, RK_APP, c->rc_buf, n, fold, 0, &d, &m, false, nullptr, &clk);
+    rc = rows_merge(c, c->stream, clk, RK_APP, in, n, w.fold, 0, &d, &m);
     if (rc) return rc;
     *n_out = m;
     if (m > cap) {
@@ -857,17 +844,16 @@ extern "C" int fa_read_window(fa_ctx* c, uint32_t timeslot, fa_row5m* out, size_
     if (!c || !n_out || (!out && cap)) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;
     static_assert(sizeof(Row5m) == sizeof(fa_row5m), "row layout");
-    uint32_t lo, hi;
-    return rows_read(c, RK_5M, timeslot, 0, out, cap, n_out, lo, hi);
+    return rows_read(c, RK_5M, timeslot, 0, out, cap, n_out);
 }
 
 // what a close removes: everything for tumbling windows / close-all, only the oldest sub-bucket when windows slide
 static int drop_buckets(fa_ctx* c, int kind, uint32_t lo, uint32_t rm_hi, bool time_watermark);
 static int drop_window(fa_ctx* c, int kind, uint32_t timeslot) {
-    uint32_t lo, hi;
-    if (!bucket_range(c, timeslot, lo, hi) || lo == hi) return FA_OK;
-    const uint32_t rm_hi = (timeslot != 0xFFFFFFFFu && c->gran != c->cfg.window_secs) ? lo + 1 : hi;
-    return drop_buckets(c, kind, lo, rm_hi, timeslot != 0xFFFFFFFFu);
+    Window w;
+    if (!window_of(c, timeslot, w) || w.lo == w.hi) return FA_OK;
+    const uint32_t rm_hi = w.fold != 0xFFFFFFFFu ? w.lo + 1 : w.hi;  // (a sliding window's rows are folded: so is what its close removes)
+    return drop_buckets(c, kind, w.lo, rm_hi, timeslot != 0xFFFFFFFFu);
 }
 // removes the buckets [lo, rm_hi) of a windowed row kind
 static int drop_buckets(fa_ctx* c, int kind, uint32_t lo, uint32_t rm_hi, bool time_watermark) {
@@ -905,8 +891,7 @@ extern "C" int fa_close_window(fa_ctx* c, uint32_t timeslot, fa_row5m* out, size
     FA_ON_DEVICE(c);
     if (!c || !n_out || (!out && cap)) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;
-    uint32_t lo, hi;
-    int rc = rows_read(c, RK_5M, timeslot, 0, out, cap, n_out, lo, hi);
+    int rc = rows_read(c, RK_5M, timeslot, 0, out, cap, n_out);
     if (rc) return rc;
     return drop_window(c, RK_5M, timeslot);
 }
@@ -934,11 +919,22 @@ extern "C" int fa_rows_device(fa_ctx* c, int kind, uint32_t timeslot, size_t k, 
     FA_ON_DEVICE(c);
     if (!c || !d_rows || !n_out) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;
-    uint32_t lo, hi;
-    int rc = rows_local(c, kind, timeslot, k, d_rows, n_out, lo, hi);
+    ReadClock clk(c);
+    int rc = rows_local(c, clk, kind, timeslot, k, d_rows, n_out);
     if (rc) return rc;
+    clk.done(row_kind_name(kind), clk.n_in, *n_out);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FA_OK;
+}
+
+// rows from elsewhere: are all n timeslots on this ctx's bucket grid?  (`who`: the entry point, for the message)
+static int rows5m_on_grid(fa_ctx* c, const void* d_rows, size_t n, const char* who) {
+    HIPCHK(c, zero_word(&c->d_ctr->rows_count, c->stream));
+    hipLaunchKernelGGL(rows5m_check_kernel, grid_n(n), dim3(256), 0, c->stream, (const Row5m*)d_rows, (uint32_t)n, c->gran, &c->d_ctr->rows_count);
+    unsigned int bad = 0;
+    HIPCHK(c, read_word(&c->d_ctr->rows_count, bad, c->stream));
+    if (!bad) return FA_OK;
+    return fail(c, FA_ERR_ARG, (std::string(who) + ": timeslot not on this ctx's bucket grid").c_str());
 }
 
 extern "C" int fa_rows_merge_device(fa_ctx* c, int kind, const void* d_rows, size_t n, size_t k, const void** d_out, size_t* n_out) {
@@ -946,16 +942,14 @@ extern "C" int fa_rows_merge_device(fa_ctx* c, int kind, const void* d_rows, siz
     if (!c || !d_out || !n_out || (!d_rows && n)) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;
     if (kind < 0 || kind >= RK_COUNT) return fail(c, FA_ERR_ARG, "unknown row kind");
-    if (kind == RK_5M && n) {  // rows from elsewhere: on this ctx's bucket grid?
+    int rc = FA_OK;
+    if (kind == RK_5M && n) {
         if (n >= (1ull << 31)) return fail(c, FA_ERR_ARG, "too many rows");
-        HIPCHK(c, hipMemsetAsync(&c->d_ctr->rows_count, 0, sizeof(unsigned int), c->stream));
-        hipLaunchKernelGGL(rows5m_check_kernel, grid_n(n), dim3(256), 0, c->stream, (const Row5m*)d_rows, (uint32_t)n, c->gran, &c->d_ctr->rows_count);
-        unsigned int bad = 0;
-        HIPCHK(c, hipMemcpyAsync(&bad, &c->d_ctr->rows_count, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (bad) return fail(c, FA_ERR_ARG, "fa_rows_merge_device: timeslot not on this ctx's bucket grid");
+        rc = rows5m_on_grid(c, d_rows, n, "fa_rows_merge_device");
+        if (rc) return rc;
     }
-    int rc = rows_merge(c, kind, d_rows, n, 0xFFFFFFFFu, k, d_out, n_out);
+    ReadClock clk(c, false);
+    rc = rows_merge(c, c->stream, clk, kind, d_rows, n, 0xFFFFFFFFu, k, d_out, n_out);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FA_OK;
@@ -998,16 +992,8 @@ extern "C" int fa_rows_partition_device(fa_ctx* c, int kind, const void* d_rows,
     int rc = ensure_dev(c, c->part_buf, n * rb, "partitioned rows");
     if (rc) return rc;
     if (!c->part_cnt.grow(3 * RPART_MAX_WORLD * sizeof(unsigned int))) return fail(c, FA_ERR_NOMEM, "hipMalloc(partition counters) failed");
-    if ((const uint8_t*)d_rows >= (const uint8_t*)c->part_buf && (const uint8_t*)d_rows < (const uint8_t*)c->part_buf + c->part_buf.bytes())
-        return fail(c, FA_ERR_ARG, "rows to partition alias the ctx's partition buffer");
-    switch (kind) {
-    case RK_5M: rc = rows_partition_t<RK_5M>(c, d_rows, (uint32_t)n, world, counts); break;
-    case RK_APP: rc = rows_partition_t<RK_APP>(c, d_rows, (uint32_t)n, world, counts); break;
-    case RK_PORT_SRC: case RK_PORT_DST: rc = rows_partition_t<RK_PORT_SRC>(c, d_rows, (uint32_t)n, world, counts); break;
-    case RK_MINUTE: rc = rows_partition_t<RK_MINUTE>(c, d_rows, (uint32_t)n, world, counts); break;
-    case RK_TOPK_SRC: case RK_TOPK_DST: rc = rows_partition_t<RK_TOPK_SRC>(c, d_rows, (uint32_t)n, world, counts); break;
-    default: return fail(c, FA_ERR_ARG, "unknown row kind");
-    }
+    if (inside(c->part_buf, d_rows)) return fail(c, FA_ERR_ARG, "rows to partition alias the ctx's partition buffer");
+    (void)with_row_kind(kind, [&](auto rk) { rc = rows_partition_t<decltype(rk)::value>(c, d_rows, (uint32_t)n, world, counts); });  // (a known kind: it has a row size)
     if (rc) return rc;
     *d_out = c->part_buf;
     return FA_OK;
@@ -1026,11 +1012,11 @@ extern "C" int fa_rows_fetch(fa_ctx* c, int kind, const void* d_rows, size_t n, 
         size_t n;
         ~Done() {
             k.mark("copy out");
-            k.done(ROW_KIND_NAMES[kind < 0 || kind >= RK_COUNT ? 0 : kind], n, n);
+            k.done(row_kind_name(kind), n, n);
         }
     } done{clk, kind, n};
     if (n) {
-        if (c->h_rows && (const uint8_t*)d_rows >= (const uint8_t*)c->h_rows && (const uint8_t*)d_rows < (const uint8_t*)c->h_rows + c->h_rows.bytes()) {
+        if (inside(c->h_rows, d_rows)) {
             copy_threads(c, out, d_rows, n * rb);  // (host memory: a result the last kernel wrote into the pinned buffer)
             return FA_OK;
         }
@@ -1051,10 +1037,12 @@ extern "C" int fa_window_rows_device(fa_ctx* c, uint32_t timeslot, const void** 
     *n_out = 0;
     uint32_t lo, hi;
     if (!bucket_range(c, timeslot, lo, hi)) return FA_OK;
+    ReadClock clk(c, false);  // (not a read with phases to report)
+    const void* in = nullptr;
     size_t n = 0;
-    int rc = collect_5m(c, lo, hi, n);
+    int rc = collect_5m(c, clk, lo, hi, in, n);
     if (rc) return rc;
-    rc = rows_merge(c, RK_5M, c->rc_buf, n, 0xFFFFFFFFu, 0, d_rows, n_out);
+    rc = rows_merge(c, c->stream, clk, RK_5M, in, n, 0xFFFFFFFFu, 0, d_rows, n_out);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FA_OK;
@@ -1066,12 +1054,8 @@ extern "C" int fa_merge_rows_device(fa_ctx* c, const void* d_rows, size_t n) {
     if (c->sticky) return c->sticky;
     if (!n) return FA_OK;
     if (n >= (1ull << 31)) return fail(c, FA_ERR_ARG, "fa_merge_rows_device: too many rows");
-    HIPCHK(c, hipMemsetAsync(&c->d_ctr->rows_count, 0, sizeof(unsigned int), c->stream));
-    hipLaunchKernelGGL(rows5m_check_kernel, grid_n(n), dim3(256), 0, c->stream, (const Row5m*)d_rows, (uint32_t)n, c->gran, &c->d_ctr->rows_count);
-    unsigned int bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, &c->d_ctr->rows_count, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (bad) return fail(c, FA_ERR_ARG, "fa_merge_rows_device: timeslot not on this ctx's bucket grid");
+    int rc = rows5m_on_grid(c, d_rows, n, "fa_merge_rows_device");
+    if (rc) return rc;
     KArgs a = make_args(c);
     hipLaunchKernelGGL(merge_rows_kernel, dim3(1024), dim3(256), 0, c->stream, (const Row5m*)d_rows, (uint32_t)n, a);
     HIPCHK(c, hipGetLastError());
@@ -1118,11 +1102,13 @@ extern "C" int fa_open_timeslots(fa_ctx* c, uint32_t* out, size_t cap, size_t* n
         }
         // (buckets spread over more than 65 536 granules: the rows' own timeslots, below)
     }
+    ReadClock clk(c, false);
+    const void* in = nullptr;
     size_t nr = 0;
-    int rc = collect_5m(c, 0, 0xFFFFFFFFu, nr);
+    int rc = collect_5m(c, clk, 0, 0xFFFFFFFFu, in, nr);
     if (rc) return rc;
     std::vector<fa_row5m> rows(nr);
-    if (nr) HIPCHK(c, hipMemcpy(rows.data(), c->rc_buf, nr * sizeof(Row5m), hipMemcpyDeviceToHost));
+    if (nr) HIPCHK(c, hipMemcpy(rows.data(), in, nr * sizeof(Row5m), hipMemcpyDeviceToHost));
     std::vector<uint32_t> ts;
     ts.reserve(rows.size());
     for (auto& r : rows) ts.push_back(r.timeslot);
@@ -1161,16 +1147,14 @@ extern "C" int fa_read_window_app(fa_ctx* c, uint32_t timeslot, fa_row_app* out,
     if (!c || !n_out || (!out && cap)) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;
     static_assert(sizeof(RowApp) == sizeof(fa_row_app), "row layout");
-    uint32_t lo, hi;
-    return rows_read(c, RK_APP, timeslot, 0, out, cap, n_out, lo, hi);
+    return rows_read(c, RK_APP, timeslot, 0, out, cap, n_out);
 }
 
 extern "C" int fa_close_window_app(fa_ctx* c, uint32_t timeslot, fa_row_app* out, size_t cap, size_t* n_out) {
     FA_ON_DEVICE(c);
     if (!c || !n_out || (!out && cap)) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;
-    uint32_t lo, hi;
-    int rc = rows_read(c, RK_APP, timeslot, 0, out, cap, n_out, lo, hi);
+    int rc = rows_read(c, RK_APP, timeslot, 0, out, cap, n_out);
     if (rc) return rc;
     return drop_window(c, RK_APP, timeslot);
 }
@@ -1201,16 +1185,14 @@ extern "C" int fa_top_ports(fa_ctx* c, int dst, size_t k, fa_port_row* out, size
         *n_out = 0;
         return FA_OK;
     }
-    uint32_t lo, hi;
-    return rows_read(c, dst ? RK_PORT_DST : RK_PORT_SRC, 0, k, out, cap, n_out, lo, hi);
+    return rows_read(c, dst ? RK_PORT_DST : RK_PORT_SRC, 0, k, out, cap, n_out);
 }
 
 extern "C" int fa_minute_series(fa_ctx* c, fa_minute_row* out, size_t cap, size_t* n_out) {
     FA_ON_DEVICE(c);
     if (!c || !n_out || (!out && cap)) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;
-    uint32_t lo, hi;
-    return rows_read(c, RK_MINUTE, 0, 0, out, cap, n_out, lo, hi);
+    return rows_read(c, RK_MINUTE, 0, 0, out, cap, n_out);
 }
 
 extern "C" int fa_topk(fa_ctx* c, uint32_t key_set, size_t k, fa_topk_row* out, size_t cap, size_t* n_out) {
@@ -1223,6 +1205,5 @@ extern "C" int fa_topk(fa_ctx* c, uint32_t key_set, size_t k, fa_topk_row* out, 
         *n_out = 0;
         return FA_OK;
     }
-    uint32_t lo, hi;
-    return rows_read(c, key_set == FA_KEYS_SRCADDR_CMS ? RK_TOPK_SRC : RK_TOPK_DST, 0, k, out, cap, n_out, lo, hi);
+    return rows_read(c, key_set == FA_KEYS_SRCADDR_CMS ? RK_TOPK_SRC : RK_TOPK_DST, 0, k, out, cap, n_out);
 }
