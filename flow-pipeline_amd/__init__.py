@@ -131,7 +131,8 @@ assert TALKER_ROW_DTYPE.itemsize == 40
 TALK_BLOCK, TALK_LDS_ENTRIES, TALK_WG_PER_CU = 512, 512, 2
 assert ROW5M_DTYPE.itemsize == 48 and FLOW_ROW_DTYPE.itemsize == 120
 assert ROW_APP_DTYPE.itemsize == 56 and PORT_ROW_DTYPE.itemsize == 24 and MINUTE_ROW_DTYPE.itemsize == 24
-ROW_DTYPES = [ROW5M_DTYPE, ROW_APP_DTYPE, PORT_ROW_DTYPE, PORT_ROW_DTYPE, MINUTE_ROW_DTYPE, TOPK_DTYPE, TOPK_DTYPE]  # by row kind
+ROW_DTYPES = [ROW5M_DTYPE, ROW_APP_DTYPE, PORT_ROW_DTYPE, PORT_ROW_DTYPE, MINUTE_ROW_DTYPE, TOPK_DTYPE, TOPK_DTYPE,
+              None, TALKER_ROW_DTYPE, TALKER_ROW_DTYPE]  # by row kind (7 is none)
 
 # every symbol include/flowagg.h declares (checked by the CPU test-suite)
 EXPORTS = [
@@ -148,11 +149,13 @@ EXPORTS = [
     "fa_group_allreduce_sketches", "fa_group_topk", "fa_group_stats", "fa_read_window_app48", "fa_close_window_app48",
     "fa_reserve_ingest",
     "fa_talkers_enable", "fa_talkers_fold_columns_device", "fa_top_talkers", "fa_merge_talkers", "fa_talkers_reset", "fa_talkers_stats",
+    "fa_merge_talkers_device", "fa_group_top_talkers",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
 # row kinds of the device-resident window close (include/flowagg.h, ABI 5)
 ROWS_5M, ROWS_APP, ROWS_PORT_SRC, ROWS_PORT_DST, ROWS_MINUTE, ROWS_TOPK_SRC, ROWS_TOPK_DST = range(7)
+ROWS_TALKERS_SRC, ROWS_TALKERS_DST = 8, 9  # (ABI 8, addition; 7 is unassigned)
 
 _LIB = None
 
@@ -312,6 +315,8 @@ def lib():
     L.fa_merge_talkers.argtypes = [vp, C.c_int, vp, sz]
     L.fa_talkers_reset.argtypes = [vp]
     L.fa_talkers_stats.argtypes = [vp, C.POINTER(TalkersStats)]
+    L.fa_merge_talkers_device.argtypes = [vp, C.c_int, vp, sz]
+    L.fa_group_top_talkers.argtypes = [vp, C.c_int, sz, vp, sz, szp]
     _LIB = L
     return L
 
@@ -677,6 +682,10 @@ class FlowAgg:
         r = np.ascontiguousarray(rows, dtype=TALKER_ROW_DTYPE)
         self._chk(self._L.fa_merge_talkers(self._h, dst, r.ctypes.data, len(r)))
 
+    def merge_talkers_device(self, dst: int, d_rows_ptr: int, n: int):
+        """merge_talkers for n rows that sit in HBM (another ctx's rows_device(ROWS_TALKERS_*) result, an exchanged share)."""
+        self._chk(self._L.fa_merge_talkers_device(self._h, dst, d_rows_ptr, n))
+
     def talkers_reset(self):
         self._chk(self._L.fa_talkers_reset(self._h))
 
@@ -824,6 +833,12 @@ class FlowGroup:
         n = C.c_size_t()
         self._chk(self._L.fa_group_topk(self._h, key_set, int(k), out.ctypes.data, len(out), C.byref(n)))
         return out[:n.value].copy()
+
+    def top_talkers(self, dst: int, k: int = 0, cap=None) -> np.ndarray:
+        """FlowAgg.top_talkers of ONE ctx that folded every member's partition, byte for byte: exact, merged in HBM."""
+        kind = ROWS_TALKERS_DST if dst else ROWS_TALKERS_SRC
+        cap = cap if cap is not None else (max(int(k), 1) if k else 1 << 12)
+        return self._rows(lambda out, c, n: self._L.fa_group_top_talkers(self._h, dst, int(k), out.ctypes.data, c, C.byref(n)), kind, cap)
 
     def stats(self) -> dict:
         s = Stats()

@@ -481,6 +481,7 @@ static int group_args(fa_group* g, const void* out, size_t cap, const size_t* n_
 }
 
 extern "C" int fa_group_read_window(fa_group* g, int kind, uint32_t timeslot, size_t k, void* out, size_t cap, size_t* n_out) {
+    if (is_talker_kind(kind)) return fa_group_top_talkers(g, kind == RK_TALKERS_DST, k, (fa_talker_row*)out, cap, n_out);  // (no timeslot: the tables span the stream)
     int rc = group_args(g, out, cap, n_out);
     if (rc) return rc;
     if (kind == RK_TOPK_SRC || kind == RK_TOPK_DST) {
@@ -511,30 +512,30 @@ extern "C" int fa_group_topk(fa_group* g, uint32_t key_set, size_t k, fa_topk_ro
     return fa_group_read_window(g, key_set == FA_KEYS_SRCADDR_CMS ? RK_TOPK_SRC : RK_TOPK_DST, 0, k, out, cap, n_out);
 }
 
+// FA_VERBOSE: wall time of a close's steps (every step ends with its members synchronised)
+struct StepClock {
+    bool on = getenv("FA_VERBOSE") != nullptr;
+    double t = ReadClock::now();
+    std::string line;
+    void mark(const char* what) {
+        if (!on) return;
+        const double u = ReadClock::now();
+        char b[64];
+        snprintf(b, sizeof b, " %s %.2f", what, u - t);
+        line += b;
+        t = u;
+    }
+};
+
 // ---- rows: hash-partitioned (large sets) -----------------------------------------------------------------------------------
 // (SrcAddr,DstPort,Proto): a window of BASELINE config 5 is 16.6 M rows x 56 B PER MEMBER - gathered, one GPU would receive
 // and sort all of it.  Every member cuts its rows by owner (fa_rows_partition_device, owner = hash(key) scaled to the group),
 // member r pulls group r of every member (one peer copy per pair: every xGMI link carries 1 / n of a member's rows), merges
 // its share - 1 / n of the keys, complete - and the shares leave through the members' own PCIe links in parallel, back to
 // back in the caller's buffer: share 0 first, each in the kind's emit order, a key in exactly one share.
-static int group_rows_partitioned(fa_group* g, int kind, uint32_t timeslot, void* out, size_t cap, size_t* share_rows, size_t* n_out) {
+// The shares: member r's merged rows (res[r], m[r] of them, in r's HBM) of the keys it owns, cut after k rows (0: all).
+static int group_shares(fa_group* g, int kind, uint32_t timeslot, size_t k, StepClock& clk, std::vector<const void*>& res, std::vector<size_t>& m) {
     const size_t n = g->m.size(), rb = row_bytes_of(kind);
-    if (!rb) return gfail(g, FA_ERR_ARG, "unknown row kind");
-    *n_out = 0;
-    // FA_VERBOSE: wall time of the close's steps (every step ends with its members synchronised)
-    struct StepClock {
-        bool on = getenv("FA_VERBOSE") != nullptr;
-        double t = ReadClock::now();
-        std::string line;
-        void mark(const char* what) {
-            if (!on) return;
-            const double u = ReadClock::now();
-            char b[64];
-            snprintf(b, sizeof b, " %s %.2f", what, u - t);
-            line += b;
-            t = u;
-        }
-    } clk;
     std::vector<const void*> part(n, nullptr);
     std::vector<size_t> counts(n * n, 0);  // counts[p * n + r]: rows member p holds for member r
     int rc = group_each(g, "rows", [&](size_t i) {
@@ -566,9 +567,20 @@ static int group_rows_partitioned(fa_group* g, int kind, uint32_t timeslot, void
     rc = group_sync(g, "row exchange");
     if (rc) return rc;
     clk.mark("exchange");
-    std::vector<const void*> res(n, nullptr);
-    std::vector<size_t> m(n, 0);
-    rc = group_each(g, "merge", [&](size_t r) { return got[r] ? fa_rows_merge_device(g->m[r], kind, g->m[r]->xch_buf, got[r], 0, &res[r], &m[r]) : FA_OK; });
+    res.assign(n, nullptr);
+    m.assign(n, 0);
+    rc = group_each(g, "merge", [&](size_t r) { return got[r] ? fa_rows_merge_device(g->m[r], kind, g->m[r]->xch_buf, got[r], k, &res[r], &m[r]) : FA_OK; });
+    clk.mark("merge");
+    return rc;
+}
+static int group_rows_partitioned(fa_group* g, int kind, uint32_t timeslot, void* out, size_t cap, size_t* share_rows, size_t* n_out) {
+    const size_t n = g->m.size(), rb = row_bytes_of(kind);
+    if (!rb) return gfail(g, FA_ERR_ARG, "unknown row kind");
+    *n_out = 0;
+    StepClock clk;
+    std::vector<const void*> res;
+    std::vector<size_t> m;
+    int rc = group_shares(g, kind, timeslot, 0, clk, res, m);
     if (rc) return rc;
     size_t total = 0;
     std::vector<size_t> at(n, 0);
@@ -578,7 +590,6 @@ static int group_rows_partitioned(fa_group* g, int kind, uint32_t timeslot, void
         if (share_rows) share_rows[r] = m[r];
     }
     *n_out = total;
-    clk.mark("merge");
     if (total > cap) return gfail(g, FA_ERR_CAPACITY, "output buffer too small");
     rc = group_each(g, "fetch", [&](size_t r) { return m[r] ? fa_rows_fetch(g->m[r], kind, res[r], m[r], (uint8_t*)out + at[r] * rb, m[r]) : FA_OK; });
     clk.mark("fetch");
@@ -597,6 +608,66 @@ extern "C" int fa_group_close_window_partitioned(fa_group* g, int kind, uint32_t
     rc = group_rows_partitioned(g, kind, timeslot, out, cap, share_rows, n_out);
     if (rc) return rc;
     return group_drop(g, kind, timeslot);
+}
+
+// ---- exact top talkers over the members' tables -------------------------------------------------------------------------------
+// An exact top k over partitions cannot be built from each partition's top k (a key that is tenth everywhere can lead overall):
+// every member's WHOLE table leaves as rows, hash-partitioned.  Stage 1 is group_shares with the merge cut at k: member r holds
+// the first k rows of the keys it owns - each key in exactly one share, with its complete sums, so under the total order (weight
+// DESC, key bytes, etype) the global first k are among the shares' first k.  Stage 2 gathers those n x k rows on one root and
+// merges them with the same cut.  The result is fa_top_talkers of ONE ctx that folded every partition, byte for byte.
+extern "C" int fa_group_top_talkers(fa_group* g, int dst, size_t k, fa_talker_row* out, size_t cap, size_t* n_out) {
+    int rc = group_args(g, out, cap, n_out);
+    if (rc) return rc;
+    if (dst != 0 && dst != 1) return gfail(g, FA_ERR_ARG, "fa_group_top_talkers: bad argument");
+    const int kind = dst ? RK_TALKERS_DST : RK_TALKERS_SRC;
+    const size_t n = g->m.size(), rb = sizeof(TalkRow);
+    *n_out = 0;
+    for (size_t i = 0; i < n; i++)  // (before anything is collected or exchanged)
+        if (!g->m[i]->talk) {
+            rc = gfail_member(g, i, kind_enabled(g->m[i], kind), "top talkers");
+            g->m[i]->err = "group: " + g->err;
+            return rc;
+        }
+    StepClock clk;
+    size_t root = 0, m = 0;
+    fa_ctx* c = g->m[0];
+    const void* d = nullptr;
+    if (n == 1) {
+        rc = fa_rows_device(c, kind, 0, k, &d, &m);
+        if (rc) return gfail_member(g, 0, rc, "rows");
+        clk.mark("rows");
+    } else {
+        std::vector<const void*> res;
+        std::vector<size_t> cnt;
+        rc = group_shares(g, kind, 0, k, clk, res, cnt);
+        if (rc) return rc;
+        size_t total = 0;
+        for (size_t r = 0; r < n; r++) total += cnt[r];
+        if (!total) return FA_OK;
+        root = g->next_root++ % n;
+        c = g->m[root];
+        // (the root's exchange buffer held the input of its own share's merge: dead, its result sits in the merge's buffers)
+        rc = group_recv(g, root, total * rb);
+        if (rc) return gfail_member(g, root, rc, "rows");
+        size_t at = 0;
+        for (size_t p = 0; p < n; p++) {
+            if (group_copy(g, root, (uint8_t*)c->xch_buf + at * rb, p, res[p], cnt[p] * rb) != hipSuccess) return gfail(g, FA_ERR_HIP, "share gather copy failed");
+            at += cnt[p];
+        }
+        (void)hipSetDevice(c->cfg.device);
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return gfail(g, FA_ERR_HIP, "share gather failed");
+        clk.mark("gather");
+        rc = fa_rows_merge_device(c, kind, c->xch_buf, total, k, &d, &m);
+        if (rc) return gfail_member(g, root, rc, "merge");
+        clk.mark("merge of the shares");
+    }
+    *n_out = m;
+    if (m > cap) return gfail(g, FA_ERR_CAPACITY, "output buffer too small");
+    rc = fa_rows_fetch(c, kind, d, m, out, cap);
+    clk.mark("fetch");
+    if (clk.on) fprintf(stderr, "[flowagg group] top talkers (%s), %zu members, k %zu, %zu rows out; ms:%s\n", dst ? "DstAddr" : "SrcAddr", n, k, m, clk.line.c_str());
+    return rc ? gfail_member(g, root, rc, "fetch") : FA_OK;
 }
 
 // ---- what a consumer asks before a flush, and at exit ----------------------------------------------------------------------

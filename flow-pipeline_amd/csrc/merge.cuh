@@ -13,10 +13,12 @@
 
 #include "maintenance.cuh"
 #include "rowplan.cuh"
+#include "talkers.cuh"
 
 namespace fa {
 
-enum { RK_5M = 0, RK_APP = 1, RK_PORT_SRC = 2, RK_PORT_DST = 3, RK_MINUTE = 4, RK_TOPK_SRC = 5, RK_TOPK_DST = 6, RK_COUNT = 7 };
+// (7 is no kind: the numbers are not dense - "is this a kind" is with_row_kind / row_bytes_of in rows_host.inc)
+enum { RK_5M = 0, RK_APP = 1, RK_PORT_SRC = 2, RK_PORT_DST = 3, RK_MINUTE = 4, RK_TOPK_SRC = 5, RK_TOPK_DST = 6, RK_TALKERS_SRC = 8, RK_TALKERS_DST = 9 };
 
 struct RowApp {  // == fa_row_app
     uint32_t date, timeslot;
@@ -158,6 +160,33 @@ template <>
 struct RowOps<RK_TOPK_SRC> : RowOpsTopk {};
 template <>
 struct RowOps<RK_TOPK_DST> : RowOpsTopk {};
+
+// exact top talkers (talkers.cuh): one row per (16 canonical key bytes, family), weight and count summed mod 2^64,
+// ORDER BY weight DESC, key bytes, etype - the four words of talker_sortkey_kernel's passes, so a merged result is
+// byte for byte what fa_top_talkers returns for a ctx that folded every record.  Rows are canonical (etype 0 / 0x800:
+// 12 bits; fa_rows_merge_device refuses anything else before it merges).
+struct RowOpsTalk {
+    typedef TalkRow Row;
+    static constexpr int NK = 3, NK2 = 4;
+    __device__ static unsigned long long key(const Row& r, int w, uint32_t) { return w == 0 ? (unsigned long long)r.etype : w == 1 ? bytes_order(r.key[1]) : bytes_order(r.key[0]); }
+    __host__ __device__ static int bits(int w) { return w == 0 ? 12 : 64; }
+    __device__ static unsigned long long key2(const Row& r, int w) { return w < 3 ? key(r, w, 0xffffffffu) : ~r.weight; }
+    __host__ __device__ static int bits2(int w) { return w == 0 ? 12 : 64; }
+    __device__ static bool same(const Row& a, const Row& b, uint32_t) { return a.key[0] == b.key[0] && a.key[1] == b.key[1] && a.etype == b.etype; }
+    __device__ static void add(Row& a, const Row& b) {
+        a.weight += b.weight;
+        a.count += b.count;
+    }
+    __device__ static void add_atomic(Row& a, const Row& b) {
+        atomicAdd(&a.weight, b.weight);
+        atomicAdd(&a.count, b.count);
+    }
+    __device__ static void finish(Row& r, uint32_t) { r.pad = 0; }
+};
+template <>
+struct RowOps<RK_TALKERS_SRC> : RowOpsTalk {};
+template <>
+struct RowOps<RK_TALKERS_DST> : RowOpsTalk {};
 
 // ---- sort keys: only the bits that differ ----------------------------------------------------------------------------
 // A row kind's order is up to four 64-bit words (224 bits for (SrcAddr,DstPort,Proto) rows) - but inside ONE row set most of
@@ -361,6 +390,16 @@ __global__ void port_dense_rows_kernel(const ulonglong2* hist, uint32_t nports, 
 __global__ void rows5m_check_kernel(const Row5m* rows, uint32_t n, uint32_t gran, unsigned int* bad) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
         if (rows[i].timeslot % gran) atomicAdd(bad, 1u);
+}
+
+// talker rows from elsewhere (fa_rows_merge_device, fa_merge_talkers_device): a row that is not canonical - etype other than
+// 0 / 0x800, or non-zero bytes 4..15 under 0x800 - would become a group no fold can produce
+__global__ void talker_rows_check_kernel(const TalkRow* rows, uint64_t n, unsigned int* bad) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const TalkRow r = rows[i];
+        const bool ok = r.etype == 0u || (r.etype == TALK_FAMILY_V4 && (r.key[0] >> 32) == 0ull && r.key[1] == 0ull);
+        if (!ok) atomicAdd(bad, 1u);
+    }
 }
 
 // fa_read_window_app48: the rows of ONE window share date and timeslot - they leave without them (a seventh of the bytes of the

@@ -6,7 +6,7 @@
 // close exchanges device buffers over RCCL and merges them without a host sort (flow-pipeline_amd/dist.py).
 
 // The RowOps<K> a row kind runs - THE statement of that mapping: both port kinds share one instantiation, both top-k kinds
-// another.  f(std::integral_constant<int, K>{}); false for a kind that is none.
+// another, both talker kinds a third.  f(std::integral_constant<int, K>{}); false for a kind that is none (7 is none).
 template <class F>
 static bool with_row_kind(int kind, F&& f) {
     switch (kind) {
@@ -15,6 +15,7 @@ static bool with_row_kind(int kind, F&& f) {
     case RK_PORT_SRC: case RK_PORT_DST: f(std::integral_constant<int, RK_PORT_SRC>{}); return true;
     case RK_MINUTE: f(std::integral_constant<int, RK_MINUTE>{}); return true;
     case RK_TOPK_SRC: case RK_TOPK_DST: f(std::integral_constant<int, RK_TOPK_SRC>{}); return true;
+    case RK_TALKERS_SRC: case RK_TALKERS_DST: f(std::integral_constant<int, RK_TALKERS_SRC>{}); return true;
     default: return false;
     }
 }
@@ -27,6 +28,8 @@ static_assert(sizeof(RowOps<RK_5M>::Row) == sizeof(Row5m) && sizeof(Row5m) == 48
 static_assert(sizeof(RowOps<RK_APP>::Row) == sizeof(RowApp) && sizeof(RowApp) == 56, "row layout");
 static_assert(sizeof(RowOps<RK_PORT_SRC>::Row) == sizeof(RowW) && sizeof(RowOps<RK_MINUTE>::Row) == sizeof(RowW) && sizeof(RowW) == 24, "row layout");
 static_assert(sizeof(RowOps<RK_TOPK_SRC>::Row) == sizeof(TopkRow) && sizeof(TopkRow) == 24, "row layout");
+static_assert(sizeof(RowOps<RK_TALKERS_SRC>::Row) == sizeof(TalkRow) && sizeof(TalkRow) == sizeof(fa_talker_row) && sizeof(TalkRow) == 40, "row layout");
+static_assert(RowOps<RK_TALKERS_SRC>::NK2 <= RP_MAX_WORDS, "emit words");
 extern "C" size_t fa_row_bytes(int kind) { return row_bytes_of(kind); }
 
 static int ensure_dev(fa_ctx* c, DevBuf<>& b, size_t bytes, const char* what) {
@@ -408,6 +411,13 @@ static int rows_merge(fa_ctx* c, hipStream_t stream, ReadClock& clk, int kind, c
     return known ? rc : fail(c, FA_ERR_ARG, "unknown row kind");
 }
 
+// the talker kinds live in talkers_host.inc (TalkState): is the state there, its collector, and its row buffer
+static bool is_talker_kind(int kind) { return kind == RK_TALKERS_SRC || kind == RK_TALKERS_DST; }
+static const char TALK_OFF[] = "top talkers are not enabled on this ctx (fa_talkers_enable)";
+static const char TALK_NOT_CANONICAL[] = "fa_merge_talkers: a row is not canonical (etype 0 or 0x800; bytes 4..15 zero under 0x800)";
+static int collect_talkers(fa_ctx* c, ReadClock& clk, int kind, const void*& in, size_t& n);
+static bool talk_rows_hold(const fa_ctx* c, const void* p);
+
 static int kind_enabled(fa_ctx* c, int kind) {
     switch (kind) {
     case RK_5M: return FA_OK;
@@ -416,12 +426,25 @@ static int kind_enabled(fa_ctx* c, int kind) {
     case RK_MINUTE: return (c->cfg.key_sets & FA_KEYS_MINUTE_SERIES) ? FA_OK : fail(c, FA_ERR_ARG, "FA_KEYS_MINUTE_SERIES not enabled");
     case RK_TOPK_SRC: return c->ks_src ? FA_OK : fail(c, FA_ERR_ARG, "fa_topk: key set not enabled");
     case RK_TOPK_DST: return c->ks_dst ? FA_OK : fail(c, FA_ERR_ARG, "fa_topk: key set not enabled");
+    case RK_TALKERS_SRC: case RK_TALKERS_DST: return c->talk ? FA_OK : fail(c, FA_ERR_UNSUPPORTED, TALK_OFF);
     default: return fail(c, FA_ERR_ARG, "unknown row kind");
     }
 }
 
-static const char* const ROW_KIND_NAMES[RK_COUNT] = {"flows_5m", "(SrcAddr,DstPort,Proto)", "SrcPort", "DstPort", "minutes", "top-k SrcAddr", "top-k DstAddr"};
-static const char* row_kind_name(int kind) { return ROW_KIND_NAMES[kind < 0 || kind >= RK_COUNT ? 0 : kind]; }
+static const char* row_kind_name(int kind) {
+    switch (kind) {
+    case RK_5M: return "flows_5m";
+    case RK_APP: return "(SrcAddr,DstPort,Proto)";
+    case RK_PORT_SRC: return "SrcPort";
+    case RK_PORT_DST: return "DstPort";
+    case RK_MINUTE: return "minutes";
+    case RK_TOPK_SRC: return "top-k SrcAddr";
+    case RK_TOPK_DST: return "top-k DstAddr";
+    case RK_TALKERS_SRC: return "talkers SrcAddr";
+    case RK_TALKERS_DST: return "talkers DstAddr";
+    default: return "unknown";
+    }
+}
 
 // (SrcAddr,DstPort,Proto) rows of the buckets [lo, hi): the wide table's (and the pending chunks') rows, unpacked in place
 static int collect_app(fa_ctx* c, ReadClock& clk, uint32_t lo, uint32_t hi, const void*& in, size_t& n) {
@@ -580,6 +603,7 @@ static int rows_local(fa_ctx* c, ReadClock& clk, int kind, uint32_t timeslot, si
         case RK_APP: rc = collect_app(c, clk, w.lo, w.hi, in, n); break;
         case RK_PORT_SRC: case RK_PORT_DST: case RK_MINUTE: rc = collect_w(c, clk, kind, in, n); break;
         case RK_TOPK_SRC: case RK_TOPK_DST: rc = collect_topk(c, clk, kind, k, sel_k, sel_partial, in, n); break;
+        case RK_TALKERS_SRC: case RK_TALKERS_DST: rc = collect_talkers(c, clk, kind, in, n); break;  // (a table holds a key once: k only cuts)
         default: return fail(c, FA_ERR_ARG, "unknown row kind");
         }
         if (rc) return rc;
@@ -937,15 +961,32 @@ static int rows5m_on_grid(fa_ctx* c, const void* d_rows, size_t n, const char* w
     return fail(c, FA_ERR_ARG, (std::string(who) + ": timeslot not on this ctx's bucket grid").c_str());
 }
 
+// talker rows from elsewhere: all n are looked at before the first is merged
+static int talker_rows_canonical(fa_ctx* c, const void* d_rows, size_t n) {
+    if (!n) return FA_OK;
+    HIPCHK(c, zero_word(&c->d_ctr->rows_count, c->stream));
+    hipLaunchKernelGGL(talker_rows_check_kernel, grid_n(n), dim3(256), 0, c->stream, (const TalkRow*)d_rows, (uint64_t)n, &c->d_ctr->rows_count);
+    unsigned int bad = 0;
+    HIPCHK(c, read_word(&c->d_ctr->rows_count, bad, c->stream));
+    return bad ? fail(c, FA_ERR_ARG, TALK_NOT_CANONICAL) : FA_OK;
+}
+
 extern "C" int fa_rows_merge_device(fa_ctx* c, int kind, const void* d_rows, size_t n, size_t k, const void** d_out, size_t* n_out) {
     FA_ON_DEVICE(c);
     if (!c || !d_out || !n_out || (!d_rows && n)) return FA_ERR_ARG;
     if (c->sticky) return c->sticky;
-    if (kind < 0 || kind >= RK_COUNT) return fail(c, FA_ERR_ARG, "unknown row kind");
+    if (!row_bytes_of(kind)) return fail(c, FA_ERR_ARG, "unknown row kind");
     int rc = FA_OK;
     if (kind == RK_5M && n) {
         if (n >= (1ull << 31)) return fail(c, FA_ERR_ARG, "too many rows");
         rc = rows5m_on_grid(c, d_rows, n, "fa_rows_merge_device");
+        if (rc) return rc;
+    }
+    if (is_talker_kind(kind)) {
+        rc = kind_enabled(c, kind);
+        if (rc) return rc;
+        if (talk_rows_hold(c, d_rows)) return fail(c, FA_ERR_ARG, "rows to merge alias the ctx's result buffer (copy them first)");
+        rc = talker_rows_canonical(c, d_rows, n);
         if (rc) return rc;
     }
     ReadClock clk(c, false);
@@ -985,6 +1026,7 @@ extern "C" int fa_rows_partition_device(fa_ctx* c, int kind, const void* d_rows,
     if (c->sticky) return c->sticky;
     const size_t rb = row_bytes_of(kind);
     if (!rb) return fail(c, FA_ERR_ARG, "unknown row kind");
+    if (is_talker_kind(kind) && !c->talk) return kind_enabled(c, kind);
     if (n >= (1ull << 31) - 1024) return fail(c, FA_ERR_ARG, "too many rows for one partition (2^31)");
     *d_out = nullptr;
     for (uint32_t d = 0; d < world; d++) counts[d] = 0;
@@ -1004,6 +1046,7 @@ extern "C" int fa_rows_fetch(fa_ctx* c, int kind, const void* d_rows, size_t n, 
     if (!c || (!d_rows && n) || (!out && n)) return FA_ERR_ARG;
     const size_t rb = row_bytes_of(kind);
     if (!rb) return fail(c, FA_ERR_ARG, "unknown row kind");
+    if (is_talker_kind(kind) && !c->talk) return kind_enabled(c, kind);
     if (n > cap) return fail(c, FA_ERR_CAPACITY, "output buffer too small");
     ReadClock clk(c);
     struct Done {

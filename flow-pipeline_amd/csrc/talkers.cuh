@@ -294,6 +294,75 @@ __global__ __launch_bounds__(256) void talker_collect_kernel(const TSlot* tab, u
         rows[j] = r;
     }
 }
+// The occupied slots as rows for the device-resident close (rows_host.inc, collect_talkers), unordered.  Shaped like
+// wextract_kernel (maintenance.cuh): a workgroup of 16 waves looks at TR_U x 1024 slots per round - every lane its own 64-byte
+// slot, three 16-byte loads, so a wave reads 64 whole lines - ballot and popcount give each row its place among the wave's,
+// and the workgroup takes the places of the round's rows with ONE returning atomic (talker_collect_kernel above: one per row,
+// all on one word).  cap = the table's own count of occupied slots; *cursor ends at the rows there were.
+constexpr int TR_U = 4;
+constexpr int TR_BLOCK = 1024;
+__global__ __launch_bounds__(TR_BLOCK) void talker_rows_kernel(const TSlot* tab, uint32_t nslots, TalkRow* rows, uint32_t cap, unsigned int* cursor) {
+    __shared__ uint32_t wave_total[TR_BLOCK / 64];
+    __shared__ uint32_t wg_rows;
+    const uint32_t nthr = gridDim.x * blockDim.x, lane = __lane_id(), wave = threadIdx.x >> 6;
+    for (uint32_t b0 = blockIdx.x * blockDim.x; b0 < nslots; b0 += TR_U * nthr) {  // (the trip count is the workgroup's: barriers inside)
+        const uint32_t i0 = b0 + threadIdx.x;
+        ulonglong2 q[TR_U][3];  // {w0, w1}, {w2, -}, {weight, count}
+        bool sel[TR_U];
+        unsigned long long m[TR_U];
+        uint32_t total = 0;
+#pragma unroll
+        for (int u = 0; u < TR_U; u++) {
+            // (i0 + u * nthr < 2^32: nslots <= 2^30 and a round overshoots by less than TR_U * nthr <= 2^21)
+            const ulonglong2* p = reinterpret_cast<const ulonglong2*>(&tab[min(i0 + (uint32_t)u * nthr, nslots - 1u)]);
+            q[u][0] = p[0];
+            q[u][1] = p[1];
+            q[u][2] = p[2];
+        }
+#pragma unroll
+        for (int u = 0; u < TR_U; u++) {
+            sel[u] = i0 + (uint32_t)u * nthr < nslots && q[u][0].x != 0ull;
+            m[u] = __builtin_amdgcn_ballot_w64(sel[u]);
+            total += (uint32_t)__builtin_popcountll(m[u]);
+        }
+        if (lane == 0) wave_total[wave] = total;
+        __syncthreads();
+        if (threadIdx.x < 64) {  // wave 0: the workgroup's rows of this round, one atomic
+            const uint32_t t = lane < TR_BLOCK / 64 ? wave_total[lane] : 0u;
+            uint32_t incl = t;
+#pragma unroll
+            for (int o = 1; o < TR_BLOCK / 64; o <<= 1) {
+                const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
+                if (lane >= (uint32_t)o) incl += up;
+            }
+            const uint32_t wg_total = (uint32_t)__builtin_amdgcn_readlane((int)incl, TR_BLOCK / 64 - 1);
+            uint32_t base = 0;
+            if (lane == 0 && wg_total != 0u) base = atomicAdd(cursor, wg_total);
+            base = (uint32_t)__builtin_amdgcn_readlane((int)base, 0);
+            if (lane < TR_BLOCK / 64) wave_total[lane] = base + incl - t;  // (exclusive: where this wave's rows start)
+            if (lane == 0) wg_rows = wg_total;
+        }
+        __syncthreads();
+        if (wg_rows != 0u && total != 0u) {  // (wave-uniform)
+            unsigned int base = wave_total[wave];
+#pragma unroll
+            for (int u = 0; u < TR_U; u++) {
+                const unsigned int j = base + (unsigned int)__builtin_popcountll(m[u] & ((1ull << lane) - 1ull));
+                base += (unsigned int)__builtin_popcountll(m[u]);
+                if (sel[u] && j < cap) {  // (j < cap always: cap counts the same slots)
+                    const unsigned long long w[3] = {q[u][0].x, q[u][0].y, q[u][1].x};
+                    TalkRow r;
+                    tkey_unpack(w, r.key[0], r.key[1], r.etype);
+                    r.pad = 0;
+                    r.weight = q[u][2].x;
+                    r.count = q[u][2].y;
+                    rows[j] = r;
+                }
+            }
+        }
+        __syncthreads();  // (wave_total and wg_rows are rewritten by the next round)
+    }
+}
 __device__ __forceinline__ unsigned long long talk_bswap64(unsigned long long v) { return __builtin_bswap64(v); }
 // Sort key of pass p over the rows in their current order (perm == nullptr: the identity, which is written to perm_out).
 // Emit order = weight DESC, key bytes ascending (memcmp), etype ascending - least significant criterion first, stable passes:

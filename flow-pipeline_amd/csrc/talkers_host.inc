@@ -20,6 +20,7 @@ struct TalkState {
     std::vector<Ev> ev;   // one pair per fold launch that has not been read yet
     size_t ev_used = 0;
     DevBuf<> scratch;  // fa_top_talkers: rows, ordered rows, sort keys, permutations, hipcub storage
+    DevBuf<> rows;     // collect_talkers: a table's rows on their way into the device-resident close (rows_host.inc)
 };
 
 static void talk_destroy(fa_ctx* c) {
@@ -37,7 +38,7 @@ static void talk_destroy(fa_ctx* c) {
     FA_ON_DEVICE(c);                                                                                   \
     if (!(c)) return FA_ERR_ARG;                                                                       \
     if ((c)->sticky) return (c)->sticky;                                                               \
-    if (!(c)->talk) return fail((c), FA_ERR_UNSUPPORTED, "top talkers are not enabled on this ctx (fa_talkers_enable)")
+    if (!(c)->talk) return fail((c), FA_ERR_UNSUPPORTED, TALK_OFF)
 
 extern "C" int fa_talkers_enable(fa_ctx* c, uint32_t capacity_log2) {
     FA_ON_DEVICE(c);
@@ -223,7 +224,7 @@ extern "C" int fa_merge_talkers(fa_ctx* c, int dst, const fa_talker_row* rows, s
         bool ok = rows[i].etype == 0 || rows[i].etype == TALK_FAMILY_V4;
         if (ok && rows[i].etype == TALK_FAMILY_V4)
             for (int b = 4; b < 16; b++) ok = ok && rows[i].key[b] == 0;
-        if (!ok) return fail(c, FA_ERR_ARG, "fa_merge_talkers: a row is not canonical (etype 0 or 0x800; bytes 4..15 zero under 0x800)");
+        if (!ok) return fail(c, FA_ERR_ARG, TALK_NOT_CANONICAL);
     }
     TalkState* t = c->talk;
     for (size_t i = 0; i < n;) {
@@ -249,6 +250,60 @@ extern "C" int fa_merge_talkers(fa_ctx* c, int dst, const fa_talker_row* rows, s
         t->used_ub[dst] += m;
         i += m;
     }
+    return FA_OK;
+}
+
+// fa_merge_talkers for rows that sit in HBM already (another ctx's fa_rows_device result, a share an exchange delivered): the
+// merge kernel reads the caller's rows where they are.
+extern "C" int fa_merge_talkers_device(fa_ctx* c, int dst, const void* d_rows, size_t n) {
+    TALK_ENTER(c);
+    if ((!d_rows && n) || (dst != 0 && dst != 1)) return fail(c, FA_ERR_ARG, "fa_merge_talkers_device: bad argument");
+    int rc = talker_rows_canonical(c, d_rows, n);
+    if (rc) return rc;
+    TalkState* t = c->talk;
+    for (size_t i = 0; i < n;) {
+        const size_t m = std::min(n - i, talk_chunk_cap(c));
+        rc = talk_reserve(c, dst, m);
+        if (rc) return rc;
+        hipLaunchKernelGGL(talker_merge_kernel, dim3((unsigned)std::min<size_t>((m + 255) / 256, 1024)), dim3(256), 0, c->stream, (const TalkRow*)d_rows + i, (uint32_t)m,
+                           t->tab[dst].get(), (uint32_t)((1ull << t->log2[dst]) - 1), t->d_ctr.get(), dst);
+        HIPCHK(c, hipGetLastError());
+        t->used_ub[dst] += m;
+        i += m;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the caller's rows are not referenced after the call)
+    return FA_OK;
+}
+
+// ---- the talker row kinds of the device-resident close (rows_host.inc: rows_local, fa_rows_merge_device) ---------------------
+static bool talk_rows_hold(const fa_ctx* c, const void* p) { return c->talk && inside(c->talk->rows, p); }
+// Table d's occupied slots as fa_talker_row, unordered, in the state's row buffer: the exact count first (it sizes the buffer
+// and reports lost updates), then one scan of the table.
+static int collect_talkers(fa_ctx* c, ReadClock& clk, int kind, const void*& in, size_t& n) {
+    TalkState* t = c->talk;
+    const int d = kind == RK_TALKERS_DST;
+    TalkCounters h;
+    int rc = talk_settle(c, h);
+    if (rc) return rc;
+    t->used_ub[0] = h.used[0];
+    t->used_ub[1] = h.used[1];
+    clk.mark("settle");
+    const size_t used = (size_t)h.used[d];  // (<= 2^29: the load is at most 1/2)
+    rc = ensure_dev(c, t->rows, std::max<size_t>(used, 1) * sizeof(TalkRow), "talker rows");
+    if (rc) return rc;
+    in = t->rows;
+    n = 0;
+    if (!used) return FA_OK;
+    unsigned int* cursor = &c->d_ctr->rows_count;
+    HIPCHK(c, zero_word(cursor, c->stream));
+    const uint32_t slots = 1u << t->log2[d];
+    const unsigned grid = (unsigned)std::min<uint32_t>(512, (slots + TR_BLOCK * TR_U - 1) / (TR_BLOCK * TR_U));
+    hipLaunchKernelGGL(talker_rows_kernel, dim3(grid), dim3(TR_BLOCK), 0, c->stream, (const TSlot*)t->tab[d], slots, (TalkRow*)t->rows.get(), (uint32_t)used, cursor);
+    HIPCHK(c, hipGetLastError());
+    unsigned int got = 0;
+    HIPCHK(c, read_word(cursor, got, c->stream));
+    if (got != used) return fail(c, FA_ERR_HIP, "internal: the talker table's rows and its count differ");
+    n = got;
     return FA_OK;
 }
 

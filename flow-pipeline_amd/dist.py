@@ -37,6 +37,7 @@ ROW_APP_DTYPE = np.dtype([
 ])
 PORT_ROW_DTYPE = np.dtype([("port", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
 MINUTE_ROW_DTYPE = np.dtype([("minute", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
+TALKER_ROW_DTYPE = np.dtype([("key", "u1", 16), ("etype", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
 
 
 def partitions_of(rank: int, world: int, n_partitions: int):
@@ -115,6 +116,22 @@ def merge_minutes_host(parts) -> np.ndarray:
     return _merge_sorted_groups(rows[np.argsort(rows["minute"], kind="stable")], ("minute",), ("weight", "count"))
 
 
+def merge_talkers_host(parts) -> np.ndarray:
+    """Partial exact top-talker row sets -> one row per (key, etype), weight and count summed mod 2^64, _pad zeroed,
+    ORDER BY weight DESC, key bytes, etype (fa_top_talkers' order; merge.cuh RowOpsTalk restated)."""
+    parts = [np.ascontiguousarray(p, dtype=TALKER_ROW_DTYPE) for p in parts if len(p)]
+    if not parts:
+        return np.zeros(0, dtype=TALKER_ROW_DTYPE)
+    rows = np.concatenate(parts)
+    key = np.ascontiguousarray(rows["key"])
+    hi, lo = key[:, :8].copy().view(">u8").reshape(-1), key[:, 8:].copy().view(">u8").reshape(-1)
+    rows = _merge_sorted_groups(rows[np.lexsort((rows["etype"], lo, hi))], ("key", "etype"), ("weight", "count"))
+    rows["_pad"] = 0
+    key = np.ascontiguousarray(rows["key"])
+    hi, lo = key[:, :8].copy().view(">u8").reshape(-1), key[:, 8:].copy().view(">u8").reshape(-1)
+    return rows[np.lexsort((rows["etype"], lo, hi, np.uint64(0xFFFFFFFFFFFFFFFF) - rows["weight"]))]
+
+
 def allgather_struct(rows: np.ndarray, dtype, group=None, device=None):
     """All ranks receive every rank's rows of `dtype` (list indexed by rank)."""
     rows = np.ascontiguousarray(rows, dtype=dtype)
@@ -161,7 +178,7 @@ def _mix64(z: np.ndarray) -> np.ndarray:
 
 def _key_words(rows: np.ndarray, kind: int):
     """The merge-order key words of a row kind, least significant first (merge.cuh, RowOps<KIND>::key)."""
-    from . import ROWS_5M, ROWS_APP, ROWS_MINUTE, ROWS_PORT_DST, ROWS_PORT_SRC
+    from . import ROWS_5M, ROWS_APP, ROWS_MINUTE, ROWS_PORT_DST, ROWS_PORT_SRC, ROWS_TALKERS_DST, ROWS_TALKERS_SRC, ROWS_TOPK_DST, ROWS_TOPK_SRC
     u64 = np.uint64
     if kind == ROWS_5M:
         return [(rows["dst_as"].astype(u64) << u64(32)) | rows["etype"].astype(u64),
@@ -175,8 +192,13 @@ def _key_words(rows: np.ndarray, kind: int):
         return [rows["port"].astype(u64)]
     if kind == ROWS_MINUTE:
         return [rows["minute"].astype(u64)]
-    key = np.ascontiguousarray(rows["key"])  # top-k rows
-    return [key[:, 8:].copy().view(">u8").reshape(-1).astype(u64), key[:, :8].copy().view(">u8").reshape(-1).astype(u64)]
+    key = np.ascontiguousarray(rows["key"])
+    words = [key[:, 8:].copy().view(">u8").reshape(-1).astype(u64), key[:, :8].copy().view(">u8").reshape(-1).astype(u64)]
+    if kind in (ROWS_TALKERS_SRC, ROWS_TALKERS_DST):
+        return [rows["etype"].astype(u64)] + words
+    if kind in (ROWS_TOPK_SRC, ROWS_TOPK_DST):
+        return words
+    raise ValueError("unknown row kind %r" % (kind,))
 
 
 def partition_rows_host(rows: np.ndarray, kind: int, world: int) -> np.ndarray:
@@ -385,6 +407,48 @@ def top_ports_merged(agg, dst, k=None, group=None, device=None) -> np.ndarray:
 def minute_series_merged(agg, group=None, device=None) -> np.ndarray:
     from . import ROWS_MINUTE
     return rows_merged(agg, ROWS_MINUTE, group=group)
+
+
+def top_talkers_merged(agg, dst, k=0, group=None) -> np.ndarray:
+    """Exact top talkers across ranks, identical on every rank and equal to FlowAgg.top_talkers of one ctx that folded every
+    rank's records.  A rank's top k says nothing about the global one (a key that is tenth everywhere can lead overall), so the
+    WHOLE table travels, hash-partitioned: rows_device(k = 0) -> fa_rows_partition_device -> one all-to-all -> rows_merge_device
+    cut at k (this rank's share: its keys, complete - the global first k are among the shares' first k) -> all-gather of the
+    shares' k rows -> rows_merge_device cut at k.  k = 0: every group."""
+    import torch.distributed as dist
+    from . import ROW_DTYPES, ROWS_TALKERS_DST, ROWS_TALKERS_SRC, FlowAggError
+    kind = ROWS_TALKERS_DST if dst else ROWS_TALKERS_SRC
+    world, rb = dist.get_world_size(group), ROW_DTYPES[kind].itemsize
+    err = None
+    try:
+        ptr, n = agg.rows_device(kind, k=0)
+        pptr, counts = agg.rows_partition_device(kind, ptr, n, world)
+    except FlowAggError as e:  # (the others must not wait for this rank in the collective: it takes part with counts of -1)
+        err, pptr, counts = e, 0, [-1] * world
+    try:
+        buf, total = alltoall_device_rows(pptr, counts, rb, group=group)
+    except RankFailed:
+        if err is not None:
+            raise err
+        raise
+    try:
+        sptr, m = agg.rows_merge_device(kind, buf.data_ptr(), total, k)
+    except FlowAggError as e:
+        err, sptr, m = e, 0, -1
+    try:
+        buf, total = allgather_device_rows(sptr, m, rb, group=group)
+    except RankFailed:
+        if err is not None:
+            raise err
+        raise
+    rows = None
+    try:
+        mptr, m = agg.rows_merge_device(kind, buf.data_ptr(), total, k)
+        rows = agg.rows_fetch(kind, mptr, m)
+    except FlowAggError as e:
+        err = e
+    _all_ok(err is None, "the merge of the shares' rows", group=group, own_error=err)
+    return rows
 
 
 def allgather_rows(rows: np.ndarray, group=None, device=None):

@@ -289,13 +289,21 @@ int fa_merge_rows_device(fa_ctx*, const void* d_rows, size_t n);
  *   FA_ROWS_PORT_SRC / _DST  fa_port_row   ORDER BY weight DESC, port                       (fa_top_ports; viz-ch.json:358,604)
  *   FA_ROWS_MINUTE    fa_minute_row ORDER BY minute                                         (fa_minute_series; viz-ch.json:74)
  *   FA_ROWS_TOPK_SRC / _DST  fa_topk_row   ORDER BY weight DESC, key bytes                  (fa_topk; viz-ch.json:233,479)
+ *   FA_ROWS_TALKERS_SRC / _DST  fa_talker_row  ORDER BY weight DESC, key bytes, etype       (fa_top_talkers; ABI 8, addition)
+ * Kind 7 is unassigned and stays unknown to every call.  The talker kinds need fa_talkers_enable on the ctx that is
+ * called (FA_ERR_UNSUPPORTED otherwise, from fa_rows_device / _merge_device / _partition_device / _fetch alike); they are
+ * not windowed - timeslot is ignored - and fa_rows_merge_device refuses rows that are not canonical (fa_merge_talkers' rule:
+ * FA_ERR_ARG, nothing merged, the outputs untouched).  An exact top k over partitions needs every partition's WHOLE table
+ * (fa_rows_device with k = 0), hash-partitioned: fa_group_top_talkers / dist.top_talkers_merged.
  * Multi-GPU window close (one ctx per GPU / Kafka partition, inserter.go:176): every rank calls fa_rows_device,
  * the ranks all-gather the device buffers over RCCL (counts first, no padding), every rank calls
  * fa_rows_merge_device on the concatenation - sum is a commutative monoid, so the result equals the single-ctx
  * result bit for bit (SummingMergeTree collapse, create.sh:70-90) - and fa_drop_window removes what was closed. */
 enum {
     FA_ROWS_5M = 0, FA_ROWS_APP = 1, FA_ROWS_PORT_SRC = 2, FA_ROWS_PORT_DST = 3, FA_ROWS_MINUTE = 4,
-    FA_ROWS_TOPK_SRC = 5, FA_ROWS_TOPK_DST = 6
+    FA_ROWS_TOPK_SRC = 5, FA_ROWS_TOPK_DST = 6,
+    /* 7: unassigned */
+    FA_ROWS_TALKERS_SRC = 8, FA_ROWS_TALKERS_DST = 9
 };
 size_t fa_row_bytes(int kind); /* bytes of one row of the kind; 0 for an unknown kind */
 /* This ctx's result for (kind, timeslot) exactly as the matching read call would return it - the sub-buckets of a
@@ -424,6 +432,10 @@ int fa_top_talkers(fa_ctx*, int dst, size_t k, fa_talker_row* out, size_t cap, s
 /* Adds rows produced by another ctx / rank (sums commute: two partitions merged equal one ctx over both, bit for bit).
  * A row that is not canonical (etype not 0 / 0x800, non-zero bytes 4..15 under 0x800) -> FA_ERR_ARG, nothing is merged. */
 int fa_merge_talkers(fa_ctx*, int dst, const fa_talker_row* rows, size_t n);
+/* fa_merge_talkers for n rows that already sit in HBM (d_rows: DEVICE pointer - another ctx's fa_rows_device(FA_ROWS_TALKERS_*)
+ * result, a share an exchange delivered): checked on the device by the same rule, merged where they are, no staging copy.
+ * Synchronous: d_rows is not referenced after the call. */
+int fa_merge_talkers_device(fa_ctx*, int dst, const void* d_rows, size_t n);
 /* Empties both tables (they keep their size); the counters of fa_talkers_stats go on counting. */
 int fa_talkers_reset(fa_ctx*);
 int fa_talkers_stats(fa_ctx*, fa_talkers_stats_t* out);
@@ -543,6 +555,13 @@ int fa_group_close_window_partitioned(fa_group*, int kind, uint32_t timeslot, vo
 int fa_group_allreduce_sketches(fa_group*);
 /* fa_topk over the whole topic (= fa_group_read_window(FA_ROWS_TOPK_SRC / _DST, 0, k, ...)). */
 int fa_group_topk(fa_group*, uint32_t key_set, size_t k, fa_topk_row* out, size_t cap, size_t* n_out);
+/* fa_top_talkers over the whole topic, exact (= fa_group_read_window(FA_ROWS_TALKERS_SRC / _DST, any timeslot, k, ...)): every
+ * member's table leaves as rows regrouped by owner, member r merges group r of every member and keeps its first k rows (a key
+ * lives in exactly one share, with its complete sums), the shares' k rows are gathered on one member and merged with the same
+ * cut - all in HBM, k rows cross PCIe.  k = 0: every group.  The result is what fa_top_talkers returns for ONE ctx that folded
+ * every partition, byte for byte.  A member without fa_talkers_enable -> FA_ERR_UNSUPPORTED before anything is exchanged (the
+ * group's and every member's last error name it).  FA_ERR_CAPACITY: *n_out = rows needed. */
+int fa_group_top_talkers(fa_group*, int dst, size_t k, fa_talker_row* out, size_t cap, size_t* n_out);
 /* fa_stats summed over the members (kernel_ns: the slowest member's last launch). */
 int fa_group_stats(fa_group*, fa_stats_t* out);
 
