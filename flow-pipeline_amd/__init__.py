@@ -415,6 +415,20 @@ def rowbinary_to_rows_fast(blob) -> np.ndarray:
     return out
 
 
+def _rows_with_room(call, chk, dtype, cap, fresh=np.empty):
+    """call(out, cap, n) -> rc fills a fresh array of `dtype` with room for `cap` rows and leaves the row count in n; on
+    FA_ERR_CAPACITY (-6) n holds the rows needed and the call is made again with that much room.  -> the rows written."""
+    n = C.c_size_t()
+    while True:
+        out = fresh(cap, dtype=dtype)
+        rc = call(out, cap, n)
+        if rc == -6:
+            cap = n.value
+            continue
+        chk(rc)
+        return out[:n.value]
+
+
 class FlowAgg:
     """One aggregation context = one (Kafka partition, GPU) pair."""
 
@@ -487,19 +501,11 @@ class FlowAgg:
 
     # -- window close ---------------------------------------------------------------
     def _rows_call(self, fn, timeslot, dtype=ROW5M_DTYPE):
-        n = C.c_size_t()
         # one call in the common case: the table's group count bounds the rows of any window (a too small buffer
         # would make the library extract and sort the window a second time)
         st = self.stats()
         cap = max(1 << 12, int(st["table_used"] if dtype is ROW5M_DTYPE else st["wide_used"]))
-        while True:
-            out = np.empty(cap, dtype=dtype)
-            rc = fn(self._h, timeslot, out.ctypes.data, cap, C.byref(n))
-            if rc == -6:  # FA_ERR_CAPACITY: n holds the required size
-                cap = n.value
-                continue
-            self._chk(rc)
-            return out[:n.value]
+        return _rows_with_room(lambda out, cap, n: fn(self._h, timeslot, out.ctypes.data, cap, C.byref(n)), self._chk, dtype, cap)
 
     def read_window(self, timeslot=ALL_TIMESLOTS) -> np.ndarray:
         return self._rows_call(self._L.fa_read_window, timeslot)
@@ -565,16 +571,7 @@ class FlowAgg:
         self._chk(self._L.fa_drop_range(self._h, kind, timeslot_lo, timeslot_hi))
 
     def open_timeslots(self) -> np.ndarray:
-        n = C.c_size_t()
-        cap = 1 << 10
-        while True:
-            out = np.zeros(cap, dtype=np.uint32)
-            rc = self._L.fa_open_timeslots(self._h, out.ctypes.data, cap, C.byref(n))
-            if rc == -6:
-                cap = n.value
-                continue
-            self._chk(rc)
-            return out[:n.value].copy()
+        return _rows_with_room(lambda out, cap, n: self._L.fa_open_timeslots(self._h, out.ctypes.data, cap, C.byref(n)), self._chk, np.uint32, 1 << 10, np.zeros).copy()
 
     def merge_rows(self, rows: np.ndarray):
         r = np.ascontiguousarray(rows, dtype=ROW5M_DTYPE)
@@ -601,7 +598,7 @@ class FlowAgg:
         fn = self._L.fa_close_window_app48 if close else self._L.fa_read_window_app48
         n, date = C.c_size_t(), C.c_uint32()
         cap = len(out) if out is not None else 1 << 12
-        while True:
+        while True:  # (its own ask-again loop: a caller's buffer is reused when it has room, and the date is a second result)
             if out is None or len(out) < cap or out.dtype != ROW_APP48_DTYPE:
                 out = np.empty(cap, dtype=ROW_APP48_DTYPE)
             rc = fn(self._h, timeslot, out.ctypes.data, len(out), C.byref(n), C.byref(date))
@@ -619,32 +616,15 @@ class FlowAgg:
     # -- dashboard read side -------------------------------------------------------------
     def top_ports(self, dst: int, k=1 << 32) -> np.ndarray:
         """GROUP BY SrcPort (dst=0) / DstPort (dst=1) ORDER BY sum(Bytes*SamplingRate) DESC, first k rows."""
-        n = C.c_size_t()
-        cap = 1 << 12
-        while True:
-            out = np.zeros(cap, dtype=PORT_ROW_DTYPE)
-            rc = self._L.fa_top_ports(self._h, dst, min(int(k), 1 << 40), out.ctypes.data, cap, C.byref(n))
-            if rc == -6:
-                cap = n.value
-                continue
-            self._chk(rc)
-            return out[:n.value].copy()
+        return _rows_with_room(lambda out, cap, n: self._L.fa_top_ports(self._h, dst, min(int(k), 1 << 40), out.ctypes.data, cap, C.byref(n)),
+                               self._chk, PORT_ROW_DTYPE, 1 << 12, np.zeros).copy()
 
     def merge_ports(self, dst: int, rows: np.ndarray):
         r = np.ascontiguousarray(rows, dtype=PORT_ROW_DTYPE)
         self._chk(self._L.fa_merge_ports(self._h, dst, r.ctypes.data, len(r)))
 
     def minute_series(self) -> np.ndarray:
-        n = C.c_size_t()
-        cap = 1 << 10
-        while True:
-            out = np.zeros(cap, dtype=MINUTE_ROW_DTYPE)
-            rc = self._L.fa_minute_series(self._h, out.ctypes.data, cap, C.byref(n))
-            if rc == -6:
-                cap = n.value
-                continue
-            self._chk(rc)
-            return out[:n.value].copy()
+        return _rows_with_room(lambda out, cap, n: self._L.fa_minute_series(self._h, out.ctypes.data, cap, C.byref(n)), self._chk, MINUTE_ROW_DTYPE, 1 << 10, np.zeros).copy()
 
     def merge_minutes(self, rows: np.ndarray):
         r = np.ascontiguousarray(rows, dtype=MINUTE_ROW_DTYPE)
@@ -667,16 +647,8 @@ class FlowAgg:
     def top_talkers(self, dst: int, k: int = 0) -> np.ndarray:
         """GROUP BY the rendered SrcAddr (dst=0) / DstAddr (dst=1) ORDER BY sum(Bytes*SamplingRate) DESC, key bytes, etype:
         every group (k=0) or the first k.  format_addr(row["key"], row["etype"]) is the string the panel shows."""
-        n = C.c_size_t()
-        cap = max(int(k), 1) if k else 1 << 12
-        while True:
-            out = np.zeros(cap, dtype=TALKER_ROW_DTYPE)
-            rc = self._L.fa_top_talkers(self._h, dst, int(k), out.ctypes.data, cap, C.byref(n))
-            if rc == -6:
-                cap = n.value
-                continue
-            self._chk(rc)
-            return out[:n.value].copy()
+        return _rows_with_room(lambda out, cap, n: self._L.fa_top_talkers(self._h, dst, int(k), out.ctypes.data, cap, C.byref(n)),
+                               self._chk, TALKER_ROW_DTYPE, max(int(k), 1) if k else 1 << 12, np.zeros).copy()
 
     def merge_talkers(self, dst: int, rows: np.ndarray):
         r = np.ascontiguousarray(rows, dtype=TALKER_ROW_DTYPE)
@@ -785,27 +757,10 @@ class FlowGroup:
         return self._L.fa_group_transport(self._h)
 
     def _rows(self, call, kind, cap=1 << 12):
-        n = C.c_size_t()
-        while True:
-            out = np.empty(cap, dtype=ROW_DTYPES[kind])
-            rc = call(out, cap, n)
-            if rc == -6:
-                cap = n.value
-                continue
-            self._chk(rc)
-            return out[:n.value]
+        return _rows_with_room(call, self._chk, ROW_DTYPES[kind], cap)
 
     def open_timeslots(self) -> np.ndarray:
-        n = C.c_size_t()
-        cap = 1 << 10
-        while True:
-            out = np.zeros(cap, dtype=np.uint32)
-            rc = self._L.fa_group_open_timeslots(self._h, out.ctypes.data, cap, C.byref(n))
-            if rc == -6:
-                cap = n.value
-                continue
-            self._chk(rc)
-            return out[:n.value].copy()
+        return _rows_with_room(lambda out, cap, n: self._L.fa_group_open_timeslots(self._h, out.ctypes.data, cap, C.byref(n)), self._chk, np.uint32, 1 << 10, np.zeros).copy()
 
     def read_window(self, kind=ROWS_5M, timeslot=ALL_TIMESLOTS, k=0, cap=1 << 12) -> np.ndarray:
         return self._rows(lambda out, c, n: self._L.fa_group_read_window(self._h, kind, timeslot, k, out.ctypes.data, c, C.byref(n)), kind, cap)

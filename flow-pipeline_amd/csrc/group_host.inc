@@ -202,17 +202,27 @@ static hipError_t group_copy(fa_group* g, size_t r, void* dst, size_t p, const v
     if (cr->cfg.device == cp->cfg.device) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, cr->stream);
     return hipMemcpyPeerAsync(dst, cr->cfg.device, src, cp->cfg.device, bytes, cr->stream);
 }
+// waits for what is queued on member i's stream
+static int member_sync(fa_group* g, size_t i, const char* what) {
+    (void)hipSetDevice(g->m[i]->cfg.device);
+    const hipError_t e = hipStreamSynchronize(g->m[i]->stream);
+    if (e == hipSuccess) return FA_OK;
+    g->m[i]->err = std::string(what) + ": " + hipGetErrorString(e);
+    return gfail_member(g, i, FA_ERR_HIP, what);
+}
 static int group_sync(fa_group* g, const char* what) {
-    for (size_t i = 0; i < g->m.size(); i++) {
-        (void)hipSetDevice(g->m[i]->cfg.device);
-        const hipError_t e = hipStreamSynchronize(g->m[i]->stream);
-        if (e != hipSuccess) {
-            g->m[i]->err = std::string(what) + ": " + hipGetErrorString(e);
-            return gfail_member(g, i, FA_ERR_HIP, what);
-        }
-    }
+    for (size_t i = 0; i < g->m.size(); i++)
+        if (int rc = member_sync(g, i, what)) return rc;
     return FA_OK;
 }
+// what a call that works with the members' state refuses up front
+static int group_sticky(fa_group* g) {
+    for (fa_ctx* c : g->m)
+        if (c->sticky) return gfail(g, c->sticky, "a member context holds a sticky error");
+    return FA_OK;
+}
+// words of a sketch one member sums in the peer all-reduce (even: 16-byte loads); fa_group_create reserves what it receives
+static size_t sketch_slice_words(size_t words, size_t n) { return ((words + n - 1) / n + 1) & ~(size_t)1; }
 
 extern "C" int fa_group_create(fa_ctx* const* ctxs, size_t n, uint32_t flags, fa_group** out) {
     if (!ctxs || !out || n == 0 || n > RPART_MAX_WORLD || (flags & ~1u)) {
@@ -252,10 +262,12 @@ extern "C" int fa_group_create(fa_ctx* const* ctxs, size_t n, uint32_t flags, fa
     }
     std::unique_ptr<fa_group> g(new fa_group());
     g->m.assign(ctxs, ctxs + n);
+    std::vector<int> dev(n);  // the members' devices
+    for (size_t i = 0; i < n; i++) dev[i] = ctxs[i]->cfg.device;
     // peers that can reach each other exchange over xGMI without a bounce through host memory
     for (size_t i = 0; i < n; i++)
         for (size_t j = 0; j < n; j++) {
-            const int di = ctxs[i]->cfg.device, dj = ctxs[j]->cfg.device;
+            const int di = dev[i], dj = dev[j];
             int can = 0;
             if (di == dj || hipDeviceCanAccessPeer(&can, di, dj) != hipSuccess || !can) continue;
             (void)hipSetDevice(di);
@@ -265,12 +277,9 @@ extern "C" int fa_group_create(fa_ctx* const* ctxs, size_t n, uint32_t flags, fa
     if (flags & FA_GROUP_RCCL) {
         // one communicator per member, made in one call (ncclCommInitAll): needs a GPU per member
         const RcclApi* api = rccl_api();
-        std::vector<int> devs(n);
         bool distinct = true;
-        for (size_t i = 0; i < n; i++) {
-            devs[i] = ctxs[i]->cfg.device;
-            for (size_t j = 0; j < i; j++) distinct = distinct && devs[j] != devs[i];
-        }
+        for (size_t i = 0; i < n; i++)
+            for (size_t j = 0; j < i; j++) distinct = distinct && dev[j] != dev[i];
         if (!api || !api->CommInitAll || !api->CommDestroy || !api->GroupStart || !api->GroupEnd) {
             g_group_error = "fa_group_create: FA_GROUP_RCCL, but librccl.so could not be loaded";
             return FA_ERR_UNSUPPORTED;
@@ -280,15 +289,13 @@ extern "C" int fa_group_create(fa_ctx* const* ctxs, size_t n, uint32_t flags, fa
             return FA_ERR_UNSUPPORTED;
         }
         g->comms.assign(n, nullptr);
-        if (api->CommInitAll(g->comms.data(), (int)n, devs.data()) != 0) {
+        if (api->CommInitAll(g->comms.data(), (int)n, dev.data()) != 0) {
             g_group_error = "fa_group_create: ncclCommInitAll failed";
             return FA_ERR_HIP;
         }
         g->transport = FA_GROUP_RCCL;
     }
     if (n > 1) {
-        std::vector<int> dev(n);
-        for (size_t i = 0; i < n; i++) dev[i] = ctxs[i]->cfg.device;
         g->pool.reset(new GroupPool());
         g->pool->start(n - 1, dev);
     }
@@ -303,10 +310,7 @@ extern "C" int fa_group_create(fa_ctx* const* ctxs, size_t n, uint32_t flags, fa
         const std::string keep = c->err;
         if ((c->cms_src || c->cms_dst) && n > 1) {
             (void)ensure_merged_view(c);
-            if (g->transport == FA_GROUP_PEER) {
-                const size_t slice = ((c->cms_words + n - 1) / n + 1) & ~(size_t)1;
-                (void)ensure_dev(c, c->xch_buf, (n - 1) * slice * 8, "group exchange buffer");
-            }
+            if (g->transport == FA_GROUP_PEER) (void)ensure_dev(c, c->xch_buf, (n - 1) * sketch_slice_words(c->cms_words, n) * 8, "group exchange buffer");
         }
         if (n > 1 && c->wtab && (c->cfg.key_sets & FA_KEYS_ADDR_PORT_PROTO)) {
             uint64_t rows = c->stats.wide_used;
@@ -388,7 +392,7 @@ static int group_allreduce(fa_group* g) {
         rc = group_sync(g, "sketch all-reduce");
         if (rc) return rc;
     } else {
-        const size_t slice = ((words + n - 1) / n + 1) & ~(size_t)1;  // words per member (even: 16-byte loads)
+        const size_t slice = sketch_slice_words(words, n);
         for (size_t r = 0; r < n; r++) {
             rc = group_recv(g, r, (n - 1) * slice * 8);
             if (rc) return gfail_member(g, r, rc, "sketch all-reduce");
@@ -426,58 +430,104 @@ static int group_allreduce(fa_group* g) {
 }
 extern "C" int fa_group_allreduce_sketches(fa_group* g) {
     if (!g) return FA_ERR_ARG;
-    for (fa_ctx* c : g->m)
-        if (c->sticky) return gfail(g, c->sticky, "a member context holds a sticky error");
-    return group_allreduce(g);
+    int rc = group_sticky(g);
+    return rc ? rc : group_allreduce(g);
 }
 
-// ---- rows: gathered (small sets) -------------------------------------------------------------------------------------------
-// every member's own result (fa_rows_device: collected, sub-buckets folded, sorted, cut at k_local) -> peer copies into ONE
-// member's exchange buffer -> fa_rows_merge_device there -> the caller's buffer.  The result is what a single ctx that had
+// ---- rows ------------------------------------------------------------------------------------------------------------------
+// Every read is three steps: the members leave rows in their HBM (fa_rows_device; group_shares), an exchange - a gather on one
+// root (group_gather_merge) or a hash-partitioned all-to-all (inside group_shares) -, and the receiver merges and fetches
+// (group_emit; a partitioned read fetches every share through its own member).  The result is what a single ctx that had
 // ingested every partition returns (sum is a commutative monoid; SummingMergeTree collapse, create.sh:70-90).
-static int group_rows_merged(fa_group* g, int kind, uint32_t timeslot, size_t k_local, size_t k, void* out, size_t cap, size_t* n_out) {
+// FA_VERBOSE: wall time of a close's steps (every step ends with its members synchronised)
+struct StepClock {
+    bool on = getenv("FA_VERBOSE") != nullptr;
+    double t = ReadClock::now();
+    std::string head, line;  // head: which call, set by the caller when `on`
+    void mark(const char* what) {
+        if (!on) return;
+        const double u = ReadClock::now();
+        char b[64];
+        snprintf(b, sizeof b, " %s %.2f", what, u - t);
+        line += b;
+        t = u;
+    }
+    void done(size_t rows) const {
+        if (on) fprintf(stderr, "[flowagg group] %s %zu rows out; ms:%s\n", head.c_str(), rows, line.c_str());
+    }
+};
+static void mark(StepClock* clk, const char* what) {
+    if (clk) clk->mark(what);
+}
+
+struct RootRows {  // m rows at d, in member `root`'s HBM
+    size_t root = 0, m = 0;
+    const void* d = nullptr;
+};
+// rows[p] / cnt[p] in member p's HBM -> peer copies into ONE member's exchange buffer -> fa_rows_merge_device there, cut after k
+// rows (0: all).  The root rotates, one step per call that gathers: a group of one has nothing to gather (its rows, cut, are the
+// result), and neither have members without a single row (m = 0).  (A root's exchange buffer may have held the input of its own
+// share's merge: dead, that result sits in the merge's buffers.)
+static int group_gather_merge(fa_group* g, int kind, const std::vector<const void*>& rows, const std::vector<size_t>& cnt, size_t k, StepClock* clk, RootRows& res) {
     const size_t n = g->m.size(), rb = row_bytes_of(kind);
-    if (!rb) return gfail(g, FA_ERR_ARG, "unknown row kind");
+    size_t total = 0;
+    for (size_t p = 0; p < n; p++) total += cnt[p];
+    res = RootRows();
+    if (n == 1) res.d = rows[0], res.m = k && total > k ? k : total;
+    if (n == 1 || !total) return FA_OK;
+    const size_t root = res.root = g->next_root++ % n;
+    fa_ctx* c = g->m[root];
+    int rc = group_recv(g, root, total * rb);
+    if (rc) return gfail_member(g, root, rc, "rows");
+    size_t at = 0;
+    for (size_t p = 0; p < n; p++) {
+        if (group_copy(g, root, (uint8_t*)c->xch_buf + at * rb, p, rows[p], cnt[p] * rb) != hipSuccess) return gfail(g, FA_ERR_HIP, "group_gather_merge: copy failed");
+        at += cnt[p];
+    }
+    rc = member_sync(g, root, "group_gather_merge");
+    if (rc) return rc;
+    mark(clk, "gather");
+    rc = fa_rows_merge_device(c, kind, c->xch_buf, total, k, &res.d, &res.m);
+    if (rc) return gfail_member(g, root, rc, "merge");
+    mark(clk, "merge of the shares");
+    return FA_OK;
+}
+// -> the caller's buffer (FA_ERR_CAPACITY: *n_out says what is needed, nothing was fetched); a clocked read's line ends here
+static int group_emit(fa_group* g, int kind, const RootRows& res, void* out, size_t cap, size_t* n_out, StepClock* clk) {
+    *n_out = res.m;
+    if (res.m > cap) return gfail(g, FA_ERR_CAPACITY, "output buffer too small");
+    const int rc = fa_rows_fetch(g->m[res.root], kind, res.d, res.m, out, cap);
+    mark(clk, "fetch");
+    if (clk) clk->done(res.m);
+    return rc ? gfail_member(g, res.root, rc, "fetch") : FA_OK;
+}
+// gathered (small sets): every member's own result (collected, sub-buckets folded, sorted, cut at k_local) -> one root -> the
+// caller's buffer.  An empty result returns with *n_out = 0 and no fetch - unless the read is clocked (the talkers of a group of
+// one), whose line has always reported the fetch of no rows too.
+static int group_rows_merged(fa_group* g, int kind, uint32_t timeslot, size_t k_local, size_t k, void* out, size_t cap, size_t* n_out, StepClock* clk = nullptr) {
+    const size_t n = g->m.size();
+    if (!row_bytes_of(kind)) return gfail(g, FA_ERR_ARG, "unknown row kind");
     *n_out = 0;
     std::vector<const void*> ptr(n, nullptr);
     std::vector<size_t> cnt(n, 0);
     int rc = group_each(g, "rows", [&](size_t i) { return fa_rows_device(g->m[i], kind, timeslot, k_local, &ptr[i], &cnt[i]); });
     if (rc) return rc;
-    size_t total = 0;
-    for (size_t i = 0; i < n; i++) total += cnt[i];
-    if (!total) return FA_OK;
-    const size_t root = n == 1 ? 0 : (g->next_root++ % n);
-    fa_ctx* c = g->m[root];
-    const void* d = ptr[root];
-    size_t m = cnt[root];
-    if (n > 1) {
-        rc = group_recv(g, root, total * rb);
-        if (rc) return gfail_member(g, root, rc, "rows");
-        size_t at = 0;
-        for (size_t p = 0; p < n; p++) {
-            if (group_copy(g, root, (uint8_t*)g->m[root]->xch_buf + at * rb, p, ptr[p], cnt[p] * rb) != hipSuccess) return gfail(g, FA_ERR_HIP, "row gather copy failed");
-            at += cnt[p];
-        }
-        (void)hipSetDevice(c->cfg.device);
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return gfail(g, FA_ERR_HIP, "row gather failed");
-        rc = fa_rows_merge_device(c, kind, g->m[root]->xch_buf, total, k, &d, &m);
-        if (rc) return gfail_member(g, root, rc, "merge");
-    } else if (k && m > k) {
-        m = k;
-    }
-    *n_out = m;
-    if (m > cap) return gfail(g, FA_ERR_CAPACITY, "output buffer too small");
-    rc = fa_rows_fetch(c, kind, d, m, out, cap);
-    return rc ? gfail_member(g, root, rc, "fetch") : FA_OK;
+    mark(clk, "rows");
+    RootRows res;
+    rc = group_gather_merge(g, kind, ptr, cnt, k, clk, res);
+    if (rc || (!res.m && !clk)) return rc;
+    return group_emit(g, kind, res, out, cap, n_out, clk);
 }
 static int group_drop(fa_group* g, int kind, uint32_t timeslot) {
     return group_each(g, "drop", [&](size_t i) { return fa_drop_window(g->m[i], kind, timeslot); });
 }
 static int group_args(fa_group* g, const void* out, size_t cap, const size_t* n_out) {
     if (!g || !n_out || (!out && cap)) return FA_ERR_ARG;
-    for (fa_ctx* c : g->m)
-        if (c->sticky) return gfail(g, c->sticky, "a member context holds a sticky error");
-    return FA_OK;
+    return group_sticky(g);
+}
+// the kinds a close removes a window of
+static int group_windowed(fa_group* g, int kind, const char* who) {
+    return kind == RK_5M || kind == RK_APP ? FA_OK : gfail(g, FA_ERR_ARG, std::string(who) + ": not a windowed row kind");
 }
 
 extern "C" int fa_group_read_window(fa_group* g, int kind, uint32_t timeslot, size_t k, void* out, size_t cap, size_t* n_out) {
@@ -497,11 +547,9 @@ extern "C" int fa_group_read_window(fa_group* g, int kind, uint32_t timeslot, si
 }
 extern "C" int fa_group_close_window(fa_group* g, int kind, uint32_t timeslot, void* out, size_t cap, size_t* n_out) {
     int rc = group_args(g, out, cap, n_out);
-    if (rc) return rc;
-    if (kind != RK_5M && kind != RK_APP) return gfail(g, FA_ERR_ARG, "fa_group_close_window: not a windowed row kind");
-    rc = group_rows_merged(g, kind, timeslot, 0, 0, out, cap, n_out);
-    if (rc) return rc;  // (FA_ERR_CAPACITY included: nothing is removed before the rows have left)
-    return group_drop(g, kind, timeslot);
+    if (!rc) rc = group_windowed(g, kind, "fa_group_close_window");
+    if (!rc) rc = group_rows_merged(g, kind, timeslot, 0, 0, out, cap, n_out);
+    return rc ? rc : group_drop(g, kind, timeslot);  // (FA_ERR_CAPACITY included: nothing is removed before the rows have left)
 }
 extern "C" int fa_group_topk(fa_group* g, uint32_t key_set, size_t k, fa_topk_row* out, size_t cap, size_t* n_out) {
     if (key_set != FA_KEYS_SRCADDR_CMS && key_set != FA_KEYS_DSTADDR_CMS) return g ? gfail(g, FA_ERR_ARG, "fa_group_topk: key set") : FA_ERR_ARG;
@@ -511,21 +559,6 @@ extern "C" int fa_group_topk(fa_group* g, uint32_t key_set, size_t k, fa_topk_ro
     }
     return fa_group_read_window(g, key_set == FA_KEYS_SRCADDR_CMS ? RK_TOPK_SRC : RK_TOPK_DST, 0, k, out, cap, n_out);
 }
-
-// FA_VERBOSE: wall time of a close's steps (every step ends with its members synchronised)
-struct StepClock {
-    bool on = getenv("FA_VERBOSE") != nullptr;
-    double t = ReadClock::now();
-    std::string line;
-    void mark(const char* what) {
-        if (!on) return;
-        const double u = ReadClock::now();
-        char b[64];
-        snprintf(b, sizeof b, " %s %.2f", what, u - t);
-        line += b;
-        t = u;
-    }
-};
 
 // ---- rows: hash-partitioned (large sets) -----------------------------------------------------------------------------------
 // (SrcAddr,DstPort,Proto): a window of BASELINE config 5 is 16.6 M rows x 56 B PER MEMBER - gathered, one GPU would receive
@@ -578,6 +611,7 @@ static int group_rows_partitioned(fa_group* g, int kind, uint32_t timeslot, void
     if (!rb) return gfail(g, FA_ERR_ARG, "unknown row kind");
     *n_out = 0;
     StepClock clk;
+    if (clk.on) clk.head = "partitioned read of kind " + std::to_string(kind) + ", " + std::to_string(n) + " members,";
     std::vector<const void*> res;
     std::vector<size_t> m;
     int rc = group_shares(g, kind, timeslot, 0, clk, res, m);
@@ -593,21 +627,18 @@ static int group_rows_partitioned(fa_group* g, int kind, uint32_t timeslot, void
     if (total > cap) return gfail(g, FA_ERR_CAPACITY, "output buffer too small");
     rc = group_each(g, "fetch", [&](size_t r) { return m[r] ? fa_rows_fetch(g->m[r], kind, res[r], m[r], (uint8_t*)out + at[r] * rb, m[r]) : FA_OK; });
     clk.mark("fetch");
-    if (clk.on) fprintf(stderr, "[flowagg group] partitioned read of kind %d, %zu members, %zu rows out; ms:%s\n", kind, n, total, clk.line.c_str());
+    clk.done(total);
     return rc;
 }
 extern "C" int fa_group_read_window_partitioned(fa_group* g, int kind, uint32_t timeslot, void* out, size_t cap, size_t* share_rows, size_t* n_out) {
     int rc = group_args(g, out, cap, n_out);
-    if (rc) return rc;
-    return group_rows_partitioned(g, kind, timeslot, out, cap, share_rows, n_out);
+    return rc ? rc : group_rows_partitioned(g, kind, timeslot, out, cap, share_rows, n_out);
 }
 extern "C" int fa_group_close_window_partitioned(fa_group* g, int kind, uint32_t timeslot, void* out, size_t cap, size_t* share_rows, size_t* n_out) {
     int rc = group_args(g, out, cap, n_out);
-    if (rc) return rc;
-    if (kind != RK_5M && kind != RK_APP) return gfail(g, FA_ERR_ARG, "fa_group_close_window_partitioned: not a windowed row kind");
-    rc = group_rows_partitioned(g, kind, timeslot, out, cap, share_rows, n_out);
-    if (rc) return rc;
-    return group_drop(g, kind, timeslot);
+    if (!rc) rc = group_windowed(g, kind, "fa_group_close_window_partitioned");
+    if (!rc) rc = group_rows_partitioned(g, kind, timeslot, out, cap, share_rows, n_out);
+    return rc ? rc : group_drop(g, kind, timeslot);
 }
 
 // ---- exact top talkers over the members' tables -------------------------------------------------------------------------------
@@ -621,7 +652,7 @@ extern "C" int fa_group_top_talkers(fa_group* g, int dst, size_t k, fa_talker_ro
     if (rc) return rc;
     if (dst != 0 && dst != 1) return gfail(g, FA_ERR_ARG, "fa_group_top_talkers: bad argument");
     const int kind = dst ? RK_TALKERS_DST : RK_TALKERS_SRC;
-    const size_t n = g->m.size(), rb = sizeof(TalkRow);
+    const size_t n = g->m.size();
     *n_out = 0;
     for (size_t i = 0; i < n; i++)  // (before anything is collected or exchanged)
         if (!g->m[i]->talk) {
@@ -630,44 +661,15 @@ extern "C" int fa_group_top_talkers(fa_group* g, int dst, size_t k, fa_talker_ro
             return rc;
         }
     StepClock clk;
-    size_t root = 0, m = 0;
-    fa_ctx* c = g->m[0];
-    const void* d = nullptr;
-    if (n == 1) {
-        rc = fa_rows_device(c, kind, 0, k, &d, &m);
-        if (rc) return gfail_member(g, 0, rc, "rows");
-        clk.mark("rows");
-    } else {
-        std::vector<const void*> res;
-        std::vector<size_t> cnt;
-        rc = group_shares(g, kind, 0, k, clk, res, cnt);
-        if (rc) return rc;
-        size_t total = 0;
-        for (size_t r = 0; r < n; r++) total += cnt[r];
-        if (!total) return FA_OK;
-        root = g->next_root++ % n;
-        c = g->m[root];
-        // (the root's exchange buffer held the input of its own share's merge: dead, its result sits in the merge's buffers)
-        rc = group_recv(g, root, total * rb);
-        if (rc) return gfail_member(g, root, rc, "rows");
-        size_t at = 0;
-        for (size_t p = 0; p < n; p++) {
-            if (group_copy(g, root, (uint8_t*)c->xch_buf + at * rb, p, res[p], cnt[p] * rb) != hipSuccess) return gfail(g, FA_ERR_HIP, "share gather copy failed");
-            at += cnt[p];
-        }
-        (void)hipSetDevice(c->cfg.device);
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return gfail(g, FA_ERR_HIP, "share gather failed");
-        clk.mark("gather");
-        rc = fa_rows_merge_device(c, kind, c->xch_buf, total, k, &d, &m);
-        if (rc) return gfail_member(g, root, rc, "merge");
-        clk.mark("merge of the shares");
-    }
-    *n_out = m;
-    if (m > cap) return gfail(g, FA_ERR_CAPACITY, "output buffer too small");
-    rc = fa_rows_fetch(c, kind, d, m, out, cap);
-    clk.mark("fetch");
-    if (clk.on) fprintf(stderr, "[flowagg group] top talkers (%s), %zu members, k %zu, %zu rows out; ms:%s\n", dst ? "DstAddr" : "SrcAddr", n, k, m, clk.line.c_str());
-    return rc ? gfail_member(g, root, rc, "fetch") : FA_OK;
+    if (clk.on) clk.head = std::string("top talkers (") + (dst ? "DstAddr" : "SrcAddr") + "), " + std::to_string(n) + " members, k " + std::to_string(k) + ",";
+    if (n == 1) return group_rows_merged(g, kind, 0, k, k, out, cap, n_out, &clk);  // (the one member's first k rows are the result)
+    std::vector<const void*> res;
+    std::vector<size_t> cnt;
+    RootRows top;
+    rc = group_shares(g, kind, 0, k, clk, res, cnt);
+    if (!rc) rc = group_gather_merge(g, kind, res, cnt, k, &clk, top);
+    if (rc || !top.m) return rc;
+    return group_emit(g, kind, top, out, cap, n_out, &clk);
 }
 
 // ---- what a consumer asks before a flush, and at exit ----------------------------------------------------------------------

@@ -45,24 +45,10 @@ def partitions_of(rank: int, world: int, n_partitions: int):
     return [p for p in range(n_partitions) if p % world == rank]
 
 
-def merge_rows_host(parts) -> np.ndarray:
-    """SummingMergeTree collapse (create.sh:70-90) of partial row sets: rows with equal
-    (date,timeslot,src_as,dst_as,etype) are summed (mod 2^64); output sorted by key."""
-    parts = [np.ascontiguousarray(p, dtype=ROW5M_DTYPE) for p in parts if len(p)]
-    if not parts:
-        return np.zeros(0, dtype=ROW5M_DTYPE)
-    rows = np.concatenate(parts)
-    order = np.lexsort((rows["etype"], rows["dst_as"], rows["src_as"], rows["timeslot"], rows["date"]))
-    rows = rows[order]
-    key = np.stack([rows[f] for f in ("date", "timeslot", "src_as", "dst_as", "etype")], axis=1)
-    first = np.ones(len(rows), dtype=bool)
-    first[1:] = (key[1:] != key[:-1]).any(axis=1)
-    starts = np.nonzero(first)[0]
-    out = rows[starts].copy()
-    with np.errstate(over="ignore"):
-        for f in ("bytes", "packets", "count"):
-            out[f] = np.add.reduceat(rows[f], starts)
-    return out
+def _be64_halves(a16):
+    """(high, low): the two big-endian u64 halves of n 16-byte keys - ordering by them orders by the key BYTES."""
+    a = np.ascontiguousarray(a16)
+    return a[:, :8].copy().view(">u8").reshape(-1), a[:, 8:].copy().view(">u8").reshape(-1)
 
 
 def _merge_sorted_groups(rows, key_cols, sum_cols):
@@ -84,52 +70,51 @@ def _merge_sorted_groups(rows, key_cols, sum_cols):
     return out
 
 
+def _merge_host(parts, dtype, group_order, key_cols, sum_cols, emit_order=None):
+    """Partial row sets -> one row per key: concatenate, sort by group_order(rows) (np.lexsort keys, least significant first),
+    sum equal keys, and - where the kind's emit order is not its key order - sort again by emit_order(rows)."""
+    parts = [np.ascontiguousarray(p, dtype=dtype) for p in parts if len(p)]
+    if not parts:
+        return np.zeros(0, dtype=dtype)
+    rows = np.concatenate(parts)
+    rows = _merge_sorted_groups(rows[np.lexsort(group_order(rows))], key_cols, sum_cols)
+    return rows if emit_order is None else rows[np.lexsort(emit_order(rows))]
+
+
+def _heaviest_first(rows):
+    return np.uint64(0xFFFFFFFFFFFFFFFF) - rows["weight"]
+
+
+def merge_rows_host(parts) -> np.ndarray:
+    """SummingMergeTree collapse (create.sh:70-90) of partial row sets: rows with equal
+    (date,timeslot,src_as,dst_as,etype) are summed (mod 2^64); output sorted by key."""
+    key = ("date", "timeslot", "src_as", "dst_as", "etype")
+    return _merge_host(parts, ROW5M_DTYPE, lambda r: tuple(r[f] for f in reversed(key)), key, ("bytes", "packets", "count"))
+
+
 def merge_rows_app_host(parts) -> np.ndarray:
     """Partial (SrcAddr,DstPort,Proto) row sets -> one row per key, sorted like fa_read_window_app."""
-    parts = [np.ascontiguousarray(p, dtype=ROW_APP_DTYPE) for p in parts if len(p)]
-    if not parts:
-        return np.zeros(0, dtype=ROW_APP_DTYPE)
-    rows = np.concatenate(parts)
-    addr = np.ascontiguousarray(rows["src_addr"])
-    hi = addr[:, :8].copy().view(">u8").reshape(-1)
-    lo = addr[:, 8:].copy().view(">u8").reshape(-1)
-    order = np.lexsort((rows["proto"], rows["dst_port"], lo, hi, rows["timeslot"], rows["date"]))
-    return _merge_sorted_groups(rows[order], ("date", "timeslot", "src_addr", "dst_port", "proto"), ("bytes", "packets", "count"))
+    return _merge_host(parts, ROW_APP_DTYPE, lambda r: (r["proto"], r["dst_port"]) + _be64_halves(r["src_addr"])[::-1] + (r["timeslot"], r["date"]),
+                       ("date", "timeslot", "src_addr", "dst_port", "proto"), ("bytes", "packets", "count"))
 
 
 def merge_ports_host(parts) -> np.ndarray:
     """Partial GROUP BY port row sets -> merged, ORDER BY weight DESC, port (viz-ch.json:358,604)."""
-    parts = [np.ascontiguousarray(p, dtype=PORT_ROW_DTYPE) for p in parts if len(p)]
-    if not parts:
-        return np.zeros(0, dtype=PORT_ROW_DTYPE)
-    rows = np.concatenate(parts)
-    rows = _merge_sorted_groups(rows[np.argsort(rows["port"], kind="stable")], ("port",), ("weight", "count"))
-    return rows[np.lexsort((rows["port"], np.uint64(0xFFFFFFFFFFFFFFFF) - rows["weight"]))]
+    return _merge_host(parts, PORT_ROW_DTYPE, lambda r: (r["port"],), ("port",), ("weight", "count"), lambda r: (r["port"], _heaviest_first(r)))
 
 
 def merge_minutes_host(parts) -> np.ndarray:
     """Partial per-minute series -> merged, ORDER BY minute (viz-ch.json:74)."""
-    parts = [np.ascontiguousarray(p, dtype=MINUTE_ROW_DTYPE) for p in parts if len(p)]
-    if not parts:
-        return np.zeros(0, dtype=MINUTE_ROW_DTYPE)
-    rows = np.concatenate(parts)
-    return _merge_sorted_groups(rows[np.argsort(rows["minute"], kind="stable")], ("minute",), ("weight", "count"))
+    return _merge_host(parts, MINUTE_ROW_DTYPE, lambda r: (r["minute"],), ("minute",), ("weight", "count"))
 
 
 def merge_talkers_host(parts) -> np.ndarray:
     """Partial exact top-talker row sets -> one row per (key, etype), weight and count summed mod 2^64, _pad zeroed,
     ORDER BY weight DESC, key bytes, etype (fa_top_talkers' order; merge.cuh RowOpsTalk restated)."""
-    parts = [np.ascontiguousarray(p, dtype=TALKER_ROW_DTYPE) for p in parts if len(p)]
-    if not parts:
-        return np.zeros(0, dtype=TALKER_ROW_DTYPE)
-    rows = np.concatenate(parts)
-    key = np.ascontiguousarray(rows["key"])
-    hi, lo = key[:, :8].copy().view(">u8").reshape(-1), key[:, 8:].copy().view(">u8").reshape(-1)
-    rows = _merge_sorted_groups(rows[np.lexsort((rows["etype"], lo, hi))], ("key", "etype"), ("weight", "count"))
+    by_key = lambda r: (r["etype"],) + _be64_halves(r["key"])[::-1]  # noqa: E731
+    rows = _merge_host(parts, TALKER_ROW_DTYPE, by_key, ("key", "etype"), ("weight", "count"), lambda r: by_key(r) + (_heaviest_first(r),))
     rows["_pad"] = 0
-    key = np.ascontiguousarray(rows["key"])
-    hi, lo = key[:, :8].copy().view(">u8").reshape(-1), key[:, 8:].copy().view(">u8").reshape(-1)
-    return rows[np.lexsort((rows["etype"], lo, hi, np.uint64(0xFFFFFFFFFFFFFFFF) - rows["weight"]))]
+    return rows
 
 
 def allgather_struct(rows: np.ndarray, dtype, group=None, device=None):
@@ -184,16 +169,14 @@ def _key_words(rows: np.ndarray, kind: int):
         return [(rows["dst_as"].astype(u64) << u64(32)) | rows["etype"].astype(u64),
                 (rows["timeslot"].astype(u64) << u64(32)) | rows["src_as"].astype(u64)]
     if kind == ROWS_APP:
-        addr = np.ascontiguousarray(rows["src_addr"])
-        return [(rows["dst_port"].astype(u64) << u64(32)) | rows["proto"].astype(u64),
-                addr[:, 8:].copy().view(">u8").reshape(-1).astype(u64), addr[:, :8].copy().view(">u8").reshape(-1).astype(u64),
-                rows["timeslot"].astype(u64)]
+        hi, lo = _be64_halves(rows["src_addr"])
+        return [(rows["dst_port"].astype(u64) << u64(32)) | rows["proto"].astype(u64), lo.astype(u64), hi.astype(u64), rows["timeslot"].astype(u64)]
     if kind in (ROWS_PORT_SRC, ROWS_PORT_DST):
         return [rows["port"].astype(u64)]
     if kind == ROWS_MINUTE:
         return [rows["minute"].astype(u64)]
-    key = np.ascontiguousarray(rows["key"])
-    words = [key[:, 8:].copy().view(">u8").reshape(-1).astype(u64), key[:, :8].copy().view(">u8").reshape(-1).astype(u64)]
+    hi, lo = _be64_halves(rows["key"])
+    words = [lo.astype(u64), hi.astype(u64)]
     if kind in (ROWS_TALKERS_SRC, ROWS_TALKERS_DST):
         return [rows["etype"].astype(u64)] + words
     if kind in (ROWS_TOPK_SRC, ROWS_TOPK_DST):
@@ -225,6 +208,66 @@ def _all_ok(ok: bool, what: str, group=None, own_error=None):
         raise own_error
     if int(t.item()) == 0:
         raise RankFailed("window close: a rank failed in %s" % what)
+
+
+class _Close:
+    """One window close of `kind` across ranks: its stages, and the rule that lets no rank wait for one that failed.
+    A rank whose LOCAL step fails keeps its error and enters the next collective all the same, with a stand-in that says so (a
+    count of -1): every rank then raises there instead of waiting - RankFailed on the others, its own error on this one.  A
+    failure behind the last collective is settled by `finish` (_all_ok): nobody returns rows - or drops a window - alone."""
+
+    def __init__(self, agg, kind, group=None):
+        from . import ROW_DTYPES
+        self.agg, self.kind, self.group, self.err = agg, kind, group, None
+        self.row_bytes = ROW_DTYPES[kind].itemsize
+
+    # -- the protocol
+    def local(self, step, stand_in=None):
+        from . import FlowAggError
+        try:
+            return step()
+        except FlowAggError as e:
+            self.err = e
+            return stand_in
+
+    def exchange(self, collective):
+        try:
+            return collective()
+        except RankFailed:
+            if self.err is not None:
+                raise self.err
+            raise
+
+    def finish(self, what, result):
+        _all_ok(self.err is None, what, group=self.group, own_error=self.err)
+        return result
+
+    # -- the stages: (device buffer, rows) each
+    def exchange_by_owner(self, timeslot):
+        """this rank's rows, cut by owner (hash of the key) in HBM -> one all-to-all -> every rank's rows of the keys THIS rank owns"""
+        import torch.distributed as dist
+        world = dist.get_world_size(self.group)
+
+        def cut():
+            ptr, n = self.agg.rows_device(self.kind, timeslot)
+            return self.agg.rows_partition_device(self.kind, ptr, n, world)
+        pptr, counts = self.local(cut, (0, [-1] * world))
+        return self.exchange(lambda: alltoall_device_rows(pptr, counts, self.row_bytes, group=self.group))
+
+    def gather(self, ptr, n):
+        """n rows in this rank's HBM (-1: it failed) -> every rank's, back to back on every rank"""
+        return self.exchange(lambda: allgather_device_rows(ptr, n, self.row_bytes, group=self.group))
+
+    def merge(self, buf, total, k):
+        """the received rows merged in HBM, cut after k (0: all) -> (device pointer, rows) for a further exchange"""
+        return self.local(lambda: self.agg.rows_merge_device(self.kind, buf.data_ptr(), total, k), (0, -1))
+
+    def merge_and_fetch(self, buf, total, k, what):
+        """the last stage: the received rows merged in HBM (emit order), one copy to the host, and the ranks' agreement"""
+        def last():
+            mptr, m = self.agg.rows_merge_device(self.kind, buf.data_ptr(), total, k)
+            return self.agg.rows_fetch(self.kind, mptr, m)
+        return self.finish(what, self.local(last))
 
 
 def allgather_device_rows(ptr: int, n: int, row_bytes: int, group=None):
@@ -285,26 +328,9 @@ def rows_merged(agg, kind, timeslot=0xFFFFFFFF, k_local=0, k=0, group=None) -> n
     """One kind of rows merged across ranks at window close, identical on every rank: fa_rows_device (this rank's
     result in HBM: extracted, sub-buckets folded, sorted) -> all-gather of the device buffers -> fa_rows_merge_device
     (radix sort + segmented sums in HBM, emit order) -> one copy of the result to the host."""
-    from . import ROW_DTYPES, FlowAggError
-    err = None
-    try:
-        ptr, n = agg.rows_device(kind, timeslot, k_local)
-    except FlowAggError as e:  # (the others must not wait for this rank in the collective: it takes part with count -1)
-        err, ptr, n = e, 0, -1
-    try:
-        buf, total = allgather_device_rows(ptr, n, ROW_DTYPES[kind].itemsize, group=group)
-    except RankFailed:
-        if err is not None:
-            raise err
-        raise
-    rows = None
-    try:
-        mptr, m = agg.rows_merge_device(kind, buf.data_ptr(), total, k)
-        rows = agg.rows_fetch(kind, mptr, m)
-    except FlowAggError as e:
-        err = e
-    _all_ok(err is None, "the merge of the gathered rows", group=group, own_error=err)
-    return rows
+    close = _Close(agg, kind, group)
+    ptr, n = close.local(lambda: agg.rows_device(kind, timeslot, k_local), (0, -1))
+    return close.merge_and_fetch(*close.gather(ptr, n), k, "the merge of the gathered rows")
 
 
 def alltoall_device_rows(ptr: int, counts, row_bytes: int, group=None):
@@ -345,29 +371,8 @@ def rows_merged_partitioned(agg, kind, timeslot=0xFFFFFFFF, group=None) -> np.nd
     (every rank's rows of those keys, summed) and in the kind's merge order.  fa_rows_device -> fa_rows_partition_device
     (groups by owner, in HBM) -> one all-to-all -> fa_rows_merge_device on 1 / world of the keys -> copy out.  The union
     of the ranks' shares is what rows_merged returns on every rank - without any rank receiving or sorting all of it."""
-    import torch.distributed as dist
-    from . import ROW_DTYPES, FlowAggError
-    world = dist.get_world_size(group)
-    err = None
-    try:
-        ptr, n = agg.rows_device(kind, timeslot)
-        pptr, counts = agg.rows_partition_device(kind, ptr, n, world)
-    except FlowAggError as e:
-        err, pptr, counts = e, 0, [-1] * world
-    try:
-        buf, total = alltoall_device_rows(pptr, counts, ROW_DTYPES[kind].itemsize, group=group)
-    except RankFailed:
-        if err is not None:
-            raise err
-        raise
-    rows = None
-    try:
-        mptr, m = agg.rows_merge_device(kind, buf.data_ptr(), total, 0)
-        rows = agg.rows_fetch(kind, mptr, m)
-    except FlowAggError as e:
-        err = e
-    _all_ok(err is None, "the merge of its share", group=group, own_error=err)
-    return rows
+    close = _Close(agg, kind, group)
+    return close.merge_and_fetch(*close.exchange_by_owner(timeslot), 0, "the merge of its share")
 
 
 def close_window_app_partitioned(agg, timeslot, group=None) -> np.ndarray:
@@ -415,40 +420,10 @@ def top_talkers_merged(agg, dst, k=0, group=None) -> np.ndarray:
     WHOLE table travels, hash-partitioned: rows_device(k = 0) -> fa_rows_partition_device -> one all-to-all -> rows_merge_device
     cut at k (this rank's share: its keys, complete - the global first k are among the shares' first k) -> all-gather of the
     shares' k rows -> rows_merge_device cut at k.  k = 0: every group."""
-    import torch.distributed as dist
-    from . import ROW_DTYPES, ROWS_TALKERS_DST, ROWS_TALKERS_SRC, FlowAggError
-    kind = ROWS_TALKERS_DST if dst else ROWS_TALKERS_SRC
-    world, rb = dist.get_world_size(group), ROW_DTYPES[kind].itemsize
-    err = None
-    try:
-        ptr, n = agg.rows_device(kind, k=0)
-        pptr, counts = agg.rows_partition_device(kind, ptr, n, world)
-    except FlowAggError as e:  # (the others must not wait for this rank in the collective: it takes part with counts of -1)
-        err, pptr, counts = e, 0, [-1] * world
-    try:
-        buf, total = alltoall_device_rows(pptr, counts, rb, group=group)
-    except RankFailed:
-        if err is not None:
-            raise err
-        raise
-    try:
-        sptr, m = agg.rows_merge_device(kind, buf.data_ptr(), total, k)
-    except FlowAggError as e:
-        err, sptr, m = e, 0, -1
-    try:
-        buf, total = allgather_device_rows(sptr, m, rb, group=group)
-    except RankFailed:
-        if err is not None:
-            raise err
-        raise
-    rows = None
-    try:
-        mptr, m = agg.rows_merge_device(kind, buf.data_ptr(), total, k)
-        rows = agg.rows_fetch(kind, mptr, m)
-    except FlowAggError as e:
-        err = e
-    _all_ok(err is None, "the merge of the shares' rows", group=group, own_error=err)
-    return rows
+    from . import ALL_TIMESLOTS, ROWS_TALKERS_DST, ROWS_TALKERS_SRC
+    close = _Close(agg, ROWS_TALKERS_DST if dst else ROWS_TALKERS_SRC, group)
+    sptr, m = close.merge(*close.exchange_by_owner(ALL_TIMESLOTS), k)  # this rank's share, cut at k
+    return close.merge_and_fetch(*close.gather(sptr, m), k, "the merge of the shares' rows")
 
 
 def allgather_rows(rows: np.ndarray, group=None, device=None):

@@ -79,6 +79,42 @@ def _worker(rank, world, port, q):
         ok = ok and rank == 1
     except d.RankFailed:
         ok = ok and rank != 1
+    # ... and the object that carries that rule through a close (dist._Close), driven with host stand-ins: a local step that
+    # fails keeps the rank's error and hands a count of -1 into the next collective, where every rank raises
+    def counts_exchange(n):  # what allgather_device_rows does with its counts, on CPU tensors
+        got = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+        dist.all_gather(got, torch.tensor([n], dtype=torch.int64))
+        got = [int(c.item()) for c in got]
+        if min(got) < 0:
+            raise d.RankFailed("rank(s) %s could not produce their rows" % [r for r, v in enumerate(got) if v < 0])
+        return got
+
+    def local_step(fail, value):
+        if fail:
+            raise fa.FlowAggError(-1, "rank 1's own error")
+        return value
+    close, outcome = d._Close(None, kinds.R5M), "returned"
+    try:  # a rank failing BEFORE the collective
+        n = close.local(lambda: local_step(rank == 1, 7 + rank), -1)
+        ok = ok and n == (-1 if rank == 1 else 7) and (close.err is not None) == (rank == 1)
+        close.exchange(lambda: counts_exchange(n))
+    except fa.FlowAggError as e:
+        outcome = "own %d" % e.code
+    except d.RankFailed:
+        outcome = "other"
+    ok = ok and outcome == ("own -1" if rank == 1 else "other")
+    close, outcome = d._Close(None, kinds.R5M), "returned"
+    try:  # a rank failing BEHIND it: the exchange is good, the last local step fails, the finishing _all_ok settles it
+        n = close.local(lambda: local_step(False, 7 + rank), -1)
+        ok = ok and close.exchange(lambda: counts_exchange(n)) == [7, 8]
+        close.finish("a test", close.local(lambda: local_step(rank == 1, "rows")))
+    except fa.FlowAggError as e:
+        outcome = "own %d" % e.code
+    except d.RankFailed:
+        outcome = "other"
+    ok = ok and outcome == ("own -1" if rank == 1 else "other")
+    close = d._Close(None, kinds.R5M)  # nobody fails: the result comes back on every rank
+    ok = ok and close.finish("a test", close.local(lambda: local_step(False, "rows"))) == "rows"
     for dst in (0, 1):
         ports = d.merge_ports_host(d.allgather_struct(po.top_ports(rows[sel], status[sel], dst), d.PORT_ROW_DTYPE, device="cpu"))
         ok = ok and ports.tobytes() == po.top_ports(rows, status, dst).tobytes()
