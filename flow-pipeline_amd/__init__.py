@@ -150,6 +150,8 @@ EXPORTS = [
     "fa_reserve_ingest",
     "fa_talkers_enable", "fa_talkers_fold_columns_device", "fa_top_talkers", "fa_merge_talkers", "fa_talkers_reset", "fa_talkers_stats",
     "fa_merge_talkers_device", "fa_group_top_talkers",
+    "fa_talkers_enable_buckets", "fa_top_talkers_range", "fa_talkers_range_rows_device", "fa_talkers_buckets", "fa_talkers_drop_before",
+    "fa_group_top_talkers_range",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -317,6 +319,12 @@ def lib():
     L.fa_talkers_stats.argtypes = [vp, C.POINTER(TalkersStats)]
     L.fa_merge_talkers_device.argtypes = [vp, C.c_int, vp, sz]
     L.fa_group_top_talkers.argtypes = [vp, C.c_int, sz, vp, sz, szp]
+    L.fa_talkers_enable_buckets.argtypes = [vp, u32, u32]
+    L.fa_top_talkers_range.argtypes = [vp, C.c_int, u32, u32, sz, vp, sz, szp]
+    L.fa_talkers_range_rows_device.argtypes = [vp, C.c_int, u32, u32, sz, C.POINTER(C.c_void_p), szp]
+    L.fa_talkers_buckets.argtypes = [vp, vp, sz, szp]
+    L.fa_talkers_drop_before.argtypes = [vp, u32]
+    L.fa_group_top_talkers_range.argtypes = [vp, C.c_int, u32, u32, sz, vp, sz, szp]
     _LIB = L
     return L
 
@@ -427,6 +435,13 @@ def _rows_with_room(call, chk, dtype, cap, fresh=np.empty):
             continue
         chk(rc)
         return out[:n.value]
+
+
+NO_UPPER_BOUND = 0xFFFFFFFF  # t_hi of a talker range: to the end of the 32-bit time axis, its last bucket included
+
+
+def _talker_range(t_lo, t_hi):
+    return (0 if t_lo is None else int(t_lo)), (NO_UPPER_BOUND if t_hi is None else int(t_hi))
 
 
 class FlowAgg:
@@ -634,21 +649,47 @@ class FlowAgg:
         self._chk(self._L.fa_dashboard_reset(self._h))
 
     # -- exact top talkers (opt-in second pass) ---------------------------------------------
-    def talkers_enable(self, capacity_log2=0):
+    def talkers_enable(self, capacity_log2=0, bucket_secs=0):
         """From now on every ingest also folds its records' SrcAddr / DstAddr into two exact tables, grouped as the
-        dashboards' top-talker panels group them (viz-ch.json:233,479)."""
-        self._chk(self._L.fa_talkers_enable(self._h, capacity_log2))
+        dashboards' top-talker panels group them (viz-ch.json:233,479).  bucket_secs > 0: the tables get a time axis
+        (fa_talkers_enable_buckets) - top_talkers(t_lo, t_hi), talkers_buckets and talkers_drop_before work on it."""
+        if bucket_secs:
+            self._chk(self._L.fa_talkers_enable_buckets(self._h, capacity_log2, bucket_secs))
+        else:
+            self._chk(self._L.fa_talkers_enable(self._h, capacity_log2))
 
     def fold_columns_device(self, cols: Columns, n: int):
         """The same fold for columns that are already decoded (device pointers; src_addr, dst_addr, etype, bytes,
         sampling_rate and status are read)."""
         self._chk(self._L.fa_talkers_fold_columns_device(self._h, C.byref(cols), n))
 
-    def top_talkers(self, dst: int, k: int = 0) -> np.ndarray:
+    def top_talkers(self, dst: int, k: int = 0, t_lo=None, t_hi=None) -> np.ndarray:
         """GROUP BY the rendered SrcAddr (dst=0) / DstAddr (dst=1) ORDER BY sum(Bytes*SamplingRate) DESC, key bytes, etype:
-        every group (k=0) or the first k.  format_addr(row["key"], row["etype"]) is the string the panel shows."""
-        return _rows_with_room(lambda out, cap, n: self._L.fa_top_talkers(self._h, dst, int(k), out.ctypes.data, cap, C.byref(n)),
-                               self._chk, TALKER_ROW_DTYPE, max(int(k), 1) if k else 1 << 12, np.zeros).copy()
+        every group (k=0) or the first k.  format_addr(row["key"], row["etype"]) is the string the panel shows.
+        t_lo / t_hi (a bucketed ctx): only the records with t_lo <= TimeFlowStart (32 bits) < t_hi; either one alone
+        leaves the other end open (0 / NO_UPPER_BOUND)."""
+        if t_lo is None and t_hi is None:
+            call = lambda out, cap, n: self._L.fa_top_talkers(self._h, dst, int(k), out.ctypes.data, cap, C.byref(n))
+        else:
+            lo, hi = _talker_range(t_lo, t_hi)
+            call = lambda out, cap, n: self._L.fa_top_talkers_range(self._h, dst, lo, hi, int(k), out.ctypes.data, cap, C.byref(n))
+        return _rows_with_room(call, self._chk, TALKER_ROW_DTYPE, max(int(k), 1) if k else 1 << 12, np.zeros).copy()
+
+    def talkers_range_rows_device(self, dst: int, t_lo=None, t_hi=None, k: int = 0):
+        """-> (device pointer, n): top_talkers(dst, k, t_lo, t_hi) left in HBM (valid until the ctx's next call) - rows of
+        kind ROWS_TALKERS_SRC / _DST for rows_partition_device / rows_merge_device."""
+        lo, hi = _talker_range(t_lo, t_hi)
+        p, n = C.c_void_p(), C.c_size_t()
+        self._chk(self._L.fa_talkers_range_rows_device(self._h, dst, lo, hi, int(k), C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
+
+    def talkers_buckets(self) -> np.ndarray:
+        """The bucket starts held in either table, ascending."""
+        return _rows_with_room(lambda out, cap, n: self._L.fa_talkers_buckets(self._h, out.ctypes.data, cap, C.byref(n)), self._chk, np.uint32, 1 << 10, np.zeros).copy()
+
+    def talkers_drop_before(self, t: int):
+        """Removes every bucket that starts below t (on the bucket grid).  Records below t that arrive later open their bucket again."""
+        self._chk(self._L.fa_talkers_drop_before(self._h, int(t)))
 
     def merge_talkers(self, dst: int, rows: np.ndarray):
         r = np.ascontiguousarray(rows, dtype=TALKER_ROW_DTYPE)
@@ -789,11 +830,15 @@ class FlowGroup:
         self._chk(self._L.fa_group_topk(self._h, key_set, int(k), out.ctypes.data, len(out), C.byref(n)))
         return out[:n.value].copy()
 
-    def top_talkers(self, dst: int, k: int = 0, cap=None) -> np.ndarray:
-        """FlowAgg.top_talkers of ONE ctx that folded every member's partition, byte for byte: exact, merged in HBM."""
+    def top_talkers(self, dst: int, k: int = 0, cap=None, t_lo=None, t_hi=None) -> np.ndarray:
+        """FlowAgg.top_talkers of ONE ctx that folded every member's partition, byte for byte: exact, merged in HBM.
+        t_lo / t_hi: FlowAgg.top_talkers' range (every member bucketed, with one bucket_secs)."""
         kind = ROWS_TALKERS_DST if dst else ROWS_TALKERS_SRC
         cap = cap if cap is not None else (max(int(k), 1) if k else 1 << 12)
-        return self._rows(lambda out, c, n: self._L.fa_group_top_talkers(self._h, dst, int(k), out.ctypes.data, c, C.byref(n)), kind, cap)
+        if t_lo is None and t_hi is None:
+            return self._rows(lambda out, c, n: self._L.fa_group_top_talkers(self._h, dst, int(k), out.ctypes.data, c, C.byref(n)), kind, cap)
+        lo, hi = _talker_range(t_lo, t_hi)
+        return self._rows(lambda out, c, n: self._L.fa_group_top_talkers_range(self._h, dst, lo, hi, int(k), out.ctypes.data, c, C.byref(n)), kind, cap)
 
     def stats(self) -> dict:
         s = Stats()

@@ -460,6 +460,8 @@ static void mark(StepClock* clk, const char* what) {
     if (clk) clk->mark(what);
 }
 
+// where member i's rows come from: fa_rows_device of the read's (kind, timeslot) unless a caller says otherwise
+typedef std::function<int(size_t i, const void** d_rows, size_t* n)> GroupRowsSource;
 struct RootRows {  // m rows at d, in member `root`'s HBM
     size_t root = 0, m = 0;
     const void* d = nullptr;
@@ -504,13 +506,14 @@ static int group_emit(fa_group* g, int kind, const RootRows& res, void* out, siz
 // gathered (small sets): every member's own result (collected, sub-buckets folded, sorted, cut at k_local) -> one root -> the
 // caller's buffer.  An empty result returns with *n_out = 0 and no fetch - unless the read is clocked (the talkers of a group of
 // one), whose line has always reported the fetch of no rows too.
-static int group_rows_merged(fa_group* g, int kind, uint32_t timeslot, size_t k_local, size_t k, void* out, size_t cap, size_t* n_out, StepClock* clk = nullptr) {
+static int group_rows_merged(fa_group* g, int kind, uint32_t timeslot, size_t k_local, size_t k, void* out, size_t cap, size_t* n_out, StepClock* clk = nullptr,
+                             const GroupRowsSource& rows_of = nullptr) {
     const size_t n = g->m.size();
     if (!row_bytes_of(kind)) return gfail(g, FA_ERR_ARG, "unknown row kind");
     *n_out = 0;
     std::vector<const void*> ptr(n, nullptr);
     std::vector<size_t> cnt(n, 0);
-    int rc = group_each(g, "rows", [&](size_t i) { return fa_rows_device(g->m[i], kind, timeslot, k_local, &ptr[i], &cnt[i]); });
+    int rc = group_each(g, "rows", [&](size_t i) { return rows_of ? rows_of(i, &ptr[i], &cnt[i]) : fa_rows_device(g->m[i], kind, timeslot, k_local, &ptr[i], &cnt[i]); });
     if (rc) return rc;
     mark(clk, "rows");
     RootRows res;
@@ -567,14 +570,16 @@ extern "C" int fa_group_topk(fa_group* g, uint32_t key_set, size_t k, fa_topk_ro
 // its share - 1 / n of the keys, complete - and the shares leave through the members' own PCIe links in parallel, back to
 // back in the caller's buffer: share 0 first, each in the kind's emit order, a key in exactly one share.
 // The shares: member r's merged rows (res[r], m[r] of them, in r's HBM) of the keys it owns, cut after k rows (0: all).
-static int group_shares(fa_group* g, int kind, uint32_t timeslot, size_t k, StepClock& clk, std::vector<const void*>& res, std::vector<size_t>& m) {
+// rows_of: where member i's rows come from (all of them, uncut) - fa_rows_device of (kind, timeslot) unless the caller says otherwise.
+static int group_shares(fa_group* g, int kind, uint32_t timeslot, size_t k, StepClock& clk, std::vector<const void*>& res, std::vector<size_t>& m,
+                        const GroupRowsSource& rows_of = nullptr) {
     const size_t n = g->m.size(), rb = row_bytes_of(kind);
     std::vector<const void*> part(n, nullptr);
     std::vector<size_t> counts(n * n, 0);  // counts[p * n + r]: rows member p holds for member r
     int rc = group_each(g, "rows", [&](size_t i) {
         const void* d = nullptr;
         size_t m = 0;
-        int r = fa_rows_device(g->m[i], kind, timeslot, 0, &d, &m);
+        int r = rows_of ? rows_of(i, &d, &m) : fa_rows_device(g->m[i], kind, timeslot, 0, &d, &m);
         if (r) return r;
         return fa_rows_partition_device(g->m[i], kind, d, m, (uint32_t)n, &part[i], &counts[i * n]);
     });
@@ -647,29 +652,53 @@ extern "C" int fa_group_close_window_partitioned(fa_group* g, int kind, uint32_t
 // the first k rows of the keys it owns - each key in exactly one share, with its complete sums, so under the total order (weight
 // DESC, key bytes, etype) the global first k are among the shares' first k.  Stage 2 gathers those n x k rows on one root and
 // merges them with the same cut.  The result is fa_top_talkers of ONE ctx that folded every partition, byte for byte.
-extern "C" int fa_group_top_talkers(fa_group* g, int dst, size_t k, fa_talker_row* out, size_t cap, size_t* n_out) {
+// range (fa_group_top_talkers_range): every member's rows come from fa_talkers_range_rows_device instead of fa_rows_device - the
+// members are bucketed, with one bucket_secs.
+static int group_top_talkers(fa_group* g, int dst, const uint32_t* range, size_t k, fa_talker_row* out, size_t cap, size_t* n_out) {
     int rc = group_args(g, out, cap, n_out);
     if (rc) return rc;
     if (dst != 0 && dst != 1) return gfail(g, FA_ERR_ARG, "fa_group_top_talkers: bad argument");
     const int kind = dst ? RK_TALKERS_DST : RK_TALKERS_SRC;
     const size_t n = g->m.size();
     *n_out = 0;
-    for (size_t i = 0; i < n; i++)  // (before anything is collected or exchanged)
+    for (size_t i = 0; i < n; i++) {  // (before anything is collected or exchanged; gfail_member names member i in every member's error)
         if (!g->m[i]->talk) {
             rc = gfail_member(g, i, kind_enabled(g->m[i], kind), "top talkers");
             g->m[i]->err = "group: " + g->err;
             return rc;
         }
+        if (!range) continue;
+        const char* why = !talk_bucket_secs(g->m[i]) ? TALK_NOT_BUCKETED : talk_bucket_secs(g->m[i]) != talk_bucket_secs(g->m[0]) ? "bucket_secs differs from member 0's" : nullptr;
+        if (!why) continue;
+        rc = gfail_member(g, i, fail(g->m[i], why == TALK_NOT_BUCKETED ? FA_ERR_UNSUPPORTED : FA_ERR_ARG, why), "top talkers of a range");
+        g->m[i]->err = "group: " + g->err;
+        return rc;
+    }
     StepClock clk;
-    if (clk.on) clk.head = std::string("top talkers (") + (dst ? "DstAddr" : "SrcAddr") + "), " + std::to_string(n) + " members, k " + std::to_string(k) + ",";
-    if (n == 1) return group_rows_merged(g, kind, 0, k, k, out, cap, n_out, &clk);  // (the one member's first k rows are the result)
+    if (clk.on) clk.head = std::string("top talkers (") + (dst ? "DstAddr" : "SrcAddr") + (range ? ", ranged" : "") + "), " + std::to_string(n) + " members, k " + std::to_string(k) + ",";
+    GroupRowsSource all_rows, first_k;  // (empty: fa_rows_device)
+    if (range) {
+        all_rows = [=](size_t i, const void** d, size_t* m) { return fa_talkers_range_rows_device(g->m[i], dst, range[0], range[1], 0, d, m); };
+        first_k = [=](size_t i, const void** d, size_t* m) { return fa_talkers_range_rows_device(g->m[i], dst, range[0], range[1], k, d, m); };
+    }
+    if (n == 1) return group_rows_merged(g, kind, 0, k, k, out, cap, n_out, &clk, first_k);  // (the one member's first k rows are the result)
     std::vector<const void*> res;
     std::vector<size_t> cnt;
     RootRows top;
-    rc = group_shares(g, kind, 0, k, clk, res, cnt);
+    rc = group_shares(g, kind, 0, k, clk, res, cnt, all_rows);
     if (!rc) rc = group_gather_merge(g, kind, res, cnt, k, &clk, top);
     if (rc || !top.m) return rc;
     return group_emit(g, kind, top, out, cap, n_out, &clk);
+}
+extern "C" int fa_group_top_talkers(fa_group* g, int dst, size_t k, fa_talker_row* out, size_t cap, size_t* n_out) {
+    return group_top_talkers(g, dst, nullptr, k, out, cap, n_out);
+}
+// fa_top_talkers_range of ONE ctx that folded every partition.  Checked before anything is exchanged: a member that is not
+// bucketed -> FA_ERR_UNSUPPORTED, members with different bucket_secs -> FA_ERR_ARG (the member is named in fa_group_last_error
+// and in every member's last error); the range itself is checked by the members, which share one grid by then.
+extern "C" int fa_group_top_talkers_range(fa_group* g, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, fa_talker_row* out, size_t cap, size_t* n_out) {
+    const uint32_t range[2] = {t_lo, t_hi};
+    return group_top_talkers(g, dst, range, k, out, cap, n_out);
 }
 
 // ---- what a consumer asks before a flush, and at exit ----------------------------------------------------------------------

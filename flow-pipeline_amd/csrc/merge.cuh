@@ -260,9 +260,10 @@ __global__ void row_heads_kernel(const typename RowOps<KIND>::Row* rows, const u
         flags[i] = (i == 0 || !RowOps<KIND>::same(rows[idx[i]], rows[idx[i - 1]], fold)) ? 1u : 0u;
 }
 // One thread per run sums its rows and writes the group's row.  Runs are as long as there are ranks x sub-buckets -
-// short - but the input of fa_rows_merge_device is the caller's: a head only walks the first RUN_SERIAL rows of its
+// short - but the input of fa_rows_merge_device is the caller's, and a ranged talker read (talkers_host.inc) holds a key
+// once per bucket of the range (60 buckets for an hour of minutes): a head only walks the first RUN_SERIAL rows of its
 // run; what lies beyond (row_tail_kernel, launched only when a longer run exists) is added by the rows themselves
-// with memory-side atomics, so a degenerate input (every row the same key) costs n atomics, not one thread's n steps.
+// with memory-side atomics, so a long run (at worst every row the same key) costs its atomics, not one thread's n steps.
 constexpr uint32_t RUN_SERIAL = 32;
 template <int KIND>
 __global__ void row_reduce_kernel(const typename RowOps<KIND>::Row* rows, const uint32_t* idx, const uint32_t* flags, const uint32_t* pos,

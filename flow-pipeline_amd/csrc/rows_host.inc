@@ -30,6 +30,10 @@ static_assert(sizeof(RowOps<RK_PORT_SRC>::Row) == sizeof(RowW) && sizeof(RowOps<
 static_assert(sizeof(RowOps<RK_TOPK_SRC>::Row) == sizeof(TopkRow) && sizeof(TopkRow) == 24, "row layout");
 static_assert(sizeof(RowOps<RK_TALKERS_SRC>::Row) == sizeof(TalkRow) && sizeof(TalkRow) == sizeof(fa_talker_row) && sizeof(TalkRow) == 40, "row layout");
 static_assert(RowOps<RK_TALKERS_SRC>::NK2 <= RP_MAX_WORDS, "emit words");
+// The talker kinds' emit order: the first `need` of n rows (device memory) by fa_top_talkers' own four full-width sorts, in the
+// talker state's scratch (talkers_host.inc).  The packed emit sort below returned rows out of order on sets of a million talker
+// rows (DESIGN.md 3.7); these four sorts never did.
+static int talk_order_rows(fa_ctx* c, hipStream_t stream, const TalkRow* rows, uint32_t n, size_t need, TalkRow* out);
 extern "C" size_t fa_row_bytes(int kind) { return row_bytes_of(kind); }
 
 static int ensure_dev(fa_ctx* c, DevBuf<>& b, size_t bytes, const char* what) {
@@ -357,8 +361,9 @@ static int rows_merge_t(fa_ctx* c, hipStream_t stream, ReadClock& clk, const voi
     const bool host = to_host && c->h_rows && m_emit * sizeof(Row) <= c->h_rows.bytes();
     rc = ensure_dev(c, c->m_out[0], (size_t)m * sizeof(Row), "merged rows");
     if (rc) return rc;
-    // the groups' rows: heads sum the first RUN_SERIAL rows of their run; longer runs (only a caller's degenerate input has
-    // them) are finished with atomics by a second kernel, which needs the rows in device memory
+    // the groups' rows: heads sum the first RUN_SERIAL rows of their run; longer runs (a caller's degenerate input, or a talker
+    // key held in more than RUN_SERIAL buckets of a range) are finished with atomics by a second kernel, which needs the rows in
+    // device memory and costs one more read of a device word
     unsigned int* long_runs = &c->d_ctr->rows_count;
     HIPCHK(c, zero_word(long_runs, stream));
     auto reduce_into = [&](Row* dst) -> int {
@@ -387,7 +392,14 @@ static int rows_merge_t(fa_ctx* c, hipStream_t stream, ReadClock& clk, const voi
     }
     clk.mark("reduce", stream);
     Row* dst = red;
-    if constexpr (Ops::NK2 > 0) {  // emit order: a second sort over the groups
+    if constexpr (KIND == RK_TALKERS_SRC || KIND == RK_TALKERS_DST) {  // emit order by the talkers' own sorts (talk_order_rows)
+        rc = ensure_dev(c, c->m_out[1], m_emit * sizeof(Row), "ordered rows");
+        if (rc) return rc;
+        dst = host ? (Row*)c->h_rows : (Row*)c->m_out[1];
+        rc = talk_order_rows(c, stream, (const Row*)red, m, m_emit, dst);
+        if (rc) return rc;
+        clk.mark("emit order", stream);
+    } else if constexpr (Ops::NK2 > 0) {  // emit order: a second sort over the groups
         uint32_t* cur2 = nullptr;
         rc = rows_sort_order<KIND, true>(c, stream, (const Row*)red, m, fold, ss, &cur2, &sorted_bits);
         if (rc) return rc;
@@ -415,8 +427,11 @@ static int rows_merge(fa_ctx* c, hipStream_t stream, ReadClock& clk, int kind, c
 static bool is_talker_kind(int kind) { return kind == RK_TALKERS_SRC || kind == RK_TALKERS_DST; }
 static const char TALK_OFF[] = "top talkers are not enabled on this ctx (fa_talkers_enable)";
 static const char TALK_NOT_CANONICAL[] = "fa_merge_talkers: a row is not canonical (etype 0 or 0x800; bytes 4..15 zero under 0x800)";
-static int collect_talkers(fa_ctx* c, ReadClock& clk, int kind, const void*& in, size_t& n);
+struct TalkRange;  // a range of bucket indices of a bucketed ctx's tables (talkers_host.inc); nullptr = every slot
+static int collect_talkers(fa_ctx* c, ReadClock& clk, int kind, const TalkRange* range, const void*& in, size_t& n);
 static bool talk_rows_hold(const fa_ctx* c, const void* p);
+static const char TALK_NOT_BUCKETED[] = "the ctx's top talkers have no time axis (fa_talkers_enable_buckets)";
+static uint32_t talk_bucket_secs(const fa_ctx* c);  // 0: not enabled, or plain tables
 
 static int kind_enabled(fa_ctx* c, int kind) {
     switch (kind) {
@@ -580,7 +595,9 @@ static int collect_topk(fa_ctx* c, ReadClock& clk, int kind, size_t k, size_t se
 
 // The ctx's own result for (kind, timeslot): what the matching read call returns, left in HBM (or, to_host, written
 // straight into the pinned host buffer when it fits): the window, then collect, then merge.
-static int rows_local(fa_ctx* c, ReadClock& clk, int kind, uint32_t timeslot, size_t k, const void** out, size_t* n_out, bool to_host = false, bool* in_host = nullptr) {
+// (talk_range: the talker kinds' ranged reads - where the rows come from is the only difference)
+static int rows_local(fa_ctx* c, ReadClock& clk, int kind, uint32_t timeslot, size_t k, const void** out, size_t* n_out, bool to_host = false, bool* in_host = nullptr,
+                      const TalkRange* talk_range = nullptr) {
     *out = nullptr;
     *n_out = 0;
     if (in_host) *in_host = false;
@@ -603,7 +620,7 @@ static int rows_local(fa_ctx* c, ReadClock& clk, int kind, uint32_t timeslot, si
         case RK_APP: rc = collect_app(c, clk, w.lo, w.hi, in, n); break;
         case RK_PORT_SRC: case RK_PORT_DST: case RK_MINUTE: rc = collect_w(c, clk, kind, in, n); break;
         case RK_TOPK_SRC: case RK_TOPK_DST: rc = collect_topk(c, clk, kind, k, sel_k, sel_partial, in, n); break;
-        case RK_TALKERS_SRC: case RK_TALKERS_DST: rc = collect_talkers(c, clk, kind, in, n); break;  // (a table holds a key once: k only cuts)
+        case RK_TALKERS_SRC: case RK_TALKERS_DST: rc = collect_talkers(c, clk, kind, talk_range, in, n); break;  // (a plain table holds a key once and k only cuts; a bucketed one once per bucket: the merge sums)
         default: return fail(c, FA_ERR_ARG, "unknown row kind");
         }
         if (rc) return rc;
@@ -719,12 +736,12 @@ static int rows_copy_out(fa_ctx* c, const void* d, size_t n, size_t row_bytes, b
     }
     return copy_out_pipelined(c, out, d, n * row_bytes);
 }
-static int rows_read(fa_ctx* c, int kind, uint32_t timeslot, size_t k, void* out, size_t cap, size_t* n_out) {
+static int rows_read(fa_ctx* c, int kind, uint32_t timeslot, size_t k, void* out, size_t cap, size_t* n_out, const TalkRange* talk_range = nullptr) {
     const void* d = nullptr;
     size_t n = 0;
     bool in_host = false;
     ReadClock clk(c);
-    int rc = rows_local(c, clk, kind, timeslot, k, &d, &n, true, &in_host);
+    int rc = rows_local(c, clk, kind, timeslot, k, &d, &n, true, &in_host, talk_range);
     if (rc) return rc;
     if (n > cap) {  // (the caller asks again with room for *n_out rows; nothing was removed)
         HIPCHK(c, hipStreamSynchronize(c->stream));

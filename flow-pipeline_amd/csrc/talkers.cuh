@@ -78,6 +78,15 @@ __host__ __device__ __forceinline__ void tkey_unpack(const unsigned long long w[
     hi = (b >> 1) | ((w[2] & 3ull) << 62);
     family = (w[2] & 4ull) ? TALK_FAMILY_V4 : 0u;
 }
+// Bucketed tables (fa_talkers_enable_buckets): the group key is (bucket, address, family).  The bucket INDEX (t32 / bucket_secs,
+// 32 bits) lives in bits 8..39 of w[2], beside the 3 payload bits tkey_pack uses - index 0 packs to tkey_pack's words, and
+// tkey_unpack (which masks bits 0..2) reads the address and family of either kind of key.
+constexpr int TKEY_BUCKET_SHIFT = 8;
+__host__ __device__ __forceinline__ void tkey_pack_bucket(uint64_t lo, uint64_t hi, uint32_t family, uint32_t bucket_index, TKey& k) {
+    tkey_pack(lo, hi, family, k);
+    k.w[2] |= (unsigned long long)bucket_index << TKEY_BUCKET_SHIFT;
+}
+__host__ __device__ __forceinline__ uint32_t tkey_bucket(const unsigned long long w[3]) { return (uint32_t)(w[2] >> TKEY_BUCKET_SHIFT); }
 __host__ __device__ __forceinline__ uint32_t tkey_hash(const TKey& k) {
     return key_hash(k.w[0] ^ (k.w[2] * 0x9E3779B97F4A7C15ull), k.w[1]);
 }
@@ -192,8 +201,15 @@ struct TalkFoldArgs {
     TSlot* tab[2];
     uint32_t mask[2];
     TalkCounters* ctr;
+    // bucketed tables only (last: the plain instantiation's arguments stay where they were)
+    const uint64_t* time_flow_start;
+    uint32_t bucket_secs;  // (0 on a plain ctx)
 };
 
+// BUCKETED: the seventh column (TimeFlowStart, 61 bytes per record) gives the key its bucket index - t32 / bucket_secs with
+// t32 = (uint32_t)TimeFlowStart, the DateTime narrowing of create.sh:40.  One 32-bit division per record, plain `/`: the random
+// upserts bound this kernel, not its ALU.  Everything behind the pack works on the three key words and is shared.
+template <bool BUCKETED>
 __global__ __launch_bounds__(TALK_BLOCK) void talker_fold_kernel(TalkFoldArgs a) {
     __shared__ TalkLds L;
     for (int i = threadIdx.x; i < 2 * TALK_LDS_ENTRIES; i += TALK_BLOCK) {
@@ -211,13 +227,16 @@ __global__ __launch_bounds__(TALK_BLOCK) void talker_fold_kernel(TalkFoldArgs a)
         folded++;
         const uint32_t et = a.etype[i];
         const uint64_t w = a.bytes[i] * a.sampling_rate[i];
+        uint32_t bidx = 0;
+        if (BUCKETED) bidx = (uint32_t)a.time_flow_start[i] / a.bucket_secs;
 #pragma unroll
         for (int d = 0; d < 2; d++) {
             const uint4 q = (d ? a.dst_addr : a.src_addr)[i];
             uint64_t lo = (uint64_t)q.y << 32 | q.x, hi = (uint64_t)q.w << 32 | q.z;
             const uint32_t fam = talker_canon_words(lo, hi, et);
             TKey k;
-            tkey_pack(lo, hi, fam, k);
+            if (BUCKETED) tkey_pack_bucket(lo, hi, fam, bidx, k);
+            else tkey_pack(lo, hi, fam, k);
             const uint32_t h = tkey_hash(k);
             if (talk_lds_add(L, d, k, h, w)) absorbed++;
             else talk_upsert(a.tab[d], a.mask[d], k, h, w, 1, a.ctr, created[d]);
@@ -254,7 +273,8 @@ __global__ __launch_bounds__(TALK_BLOCK) void talker_fold_kernel(TalkFoldArgs a)
 }
 
 // Growth: every occupied slot of the old table is inserted again (key, weight, count) - the sums stay exact.
-__global__ __launch_bounds__(256) void talker_rehash_kernel(const TSlot* old_tab, uint64_t old_slots, TSlot* tab, uint32_t mask, TalkCounters* ctr, int d) {
+// floor_index (fa_talkers_drop_before; 0 = keep everything): slots of a bucket index below it are left behind.
+__global__ __launch_bounds__(256) void talker_rehash_kernel(const TSlot* old_tab, uint64_t old_slots, TSlot* tab, uint32_t mask, TalkCounters* ctr, int d, uint32_t floor_index) {
     uint32_t created = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_slots; i += (uint64_t)gridDim.x * blockDim.x) {
         const TSlot* s = &old_tab[i];
@@ -263,6 +283,7 @@ __global__ __launch_bounds__(256) void talker_rehash_kernel(const TSlot* old_tab
         k.w[0] = s->w[0];
         k.w[1] = s->w[1];
         k.w[2] = s->w[2];
+        if (tkey_bucket(k.w) < floor_index) continue;
         talk_upsert(tab, mask, k, tkey_hash(k), s->weight, s->count, ctr, created);
     }
     talk_count_created(&ctr->used[d], created);
@@ -299,9 +320,14 @@ __global__ __launch_bounds__(256) void talker_collect_kernel(const TSlot* tab, u
 // slot, three 16-byte loads, so a wave reads 64 whole lines - ballot and popcount give each row its place among the wave's,
 // and the workgroup takes the places of the round's rows with ONE returning atomic (talker_collect_kernel above: one per row,
 // all on one word).  cap = the table's own count of occupied slots; *cursor ends at the rows there were.
+// RANGED (fa_talkers_range_rows_device, bucketed tables): only the slots whose bucket index lies in [index_lo, index_last]
+// (both inclusive: the last index of the axis has no successor in 32 bits) are kept; the row carries no bucket, so a key
+// held in several buckets leaves as several rows, which the merge behind the read folds.  cap = the table's count of
+// occupied slots, an upper bound there.
 constexpr int TR_U = 4;
 constexpr int TR_BLOCK = 1024;
-__global__ __launch_bounds__(TR_BLOCK) void talker_rows_kernel(const TSlot* tab, uint32_t nslots, TalkRow* rows, uint32_t cap, unsigned int* cursor) {
+template <bool RANGED>
+__global__ __launch_bounds__(TR_BLOCK) void talker_rows_kernel(const TSlot* tab, uint32_t nslots, TalkRow* rows, uint32_t cap, unsigned int* cursor, uint32_t index_lo, uint32_t index_last) {
     __shared__ uint32_t wave_total[TR_BLOCK / 64];
     __shared__ uint32_t wg_rows;
     const uint32_t nthr = gridDim.x * blockDim.x, lane = __lane_id(), wave = threadIdx.x >> 6;
@@ -322,6 +348,10 @@ __global__ __launch_bounds__(TR_BLOCK) void talker_rows_kernel(const TSlot* tab,
 #pragma unroll
         for (int u = 0; u < TR_U; u++) {
             sel[u] = i0 + (uint32_t)u * nthr < nslots && q[u][0].x != 0ull;
+            if (RANGED) {
+                const uint32_t b = (uint32_t)(q[u][1].x >> TKEY_BUCKET_SHIFT);
+                sel[u] = sel[u] && b >= index_lo && b <= index_last;
+            }
             m[u] = __builtin_amdgcn_ballot_w64(sel[u]);
             total += (uint32_t)__builtin_popcountll(m[u]);
         }
@@ -361,6 +391,46 @@ __global__ __launch_bounds__(TR_BLOCK) void talker_rows_kernel(const TSlot* tab,
             }
         }
         __syncthreads();  // (wave_total and wg_rows are rewritten by the next round)
+    }
+}
+// fa_talkers_buckets, shaped like timeslots_kernel (maintenance.cuh).  bits == nullptr: the smallest and largest bucket index of
+// the occupied slots into range[0..1] (one atomic pair per wave); else one bit per index of [lo, lo + nbits).
+__global__ __launch_bounds__(256) void talker_buckets_kernel(const TSlot* tab, uint64_t nslots, uint32_t lo, uint32_t nbits, unsigned int* bits, unsigned int* range) {
+    uint32_t mn = 0xffffffffu, mx = 0u;
+    bool any = false;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * blockDim.x) {
+        const ulonglong2 k = *reinterpret_cast<const ulonglong2*>(&tab[i].w[2]);  // {w2, pad0}
+        if (k.x == 0) continue;  // (w2 is the last word claimed: a slot whose w2 is set holds a whole key)
+        const uint32_t b = (uint32_t)(k.x >> TKEY_BUCKET_SHIFT);
+        if (bits) {
+            if (b - lo < nbits) atomicOr(&bits[(b - lo) >> 5], 1u << ((b - lo) & 31u));
+        } else {
+            any = true;
+            mn = min(mn, b);
+            mx = max(mx, b);
+        }
+    }
+    if (!bits) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            mn = min(mn, (uint32_t)__shfl_xor((int)mn, o));
+            mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+        }
+        const bool wave_any = __builtin_amdgcn_ballot_w64(any) != 0ull;
+        if (__lane_id() == 0 && wave_any) {
+            atomicMin(&range[0], mn);
+            atomicMax(&range[1], mx);
+            range[2] = 1u;  // (a bucket was seen: index 0xFFFFFFFF is a bucket like any other)
+        }
+    }
+}
+// The bucket index of every occupied slot, compacted (fa_talkers_buckets when the indices span more than its bitmap).
+__global__ __launch_bounds__(256) void talker_bucket_list_kernel(const TSlot* tab, uint64_t nslots, uint32_t* out, uint32_t cap, unsigned int* cursor) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long w2 = tab[i].w[2];
+        if (w2 == 0) continue;
+        const unsigned int j = atomicAdd(cursor, 1u);
+        if (j < cap) out[j] = (uint32_t)(w2 >> TKEY_BUCKET_SHIFT);
     }
 }
 __device__ __forceinline__ unsigned long long talk_bswap64(unsigned long long v) { return __builtin_bswap64(v); }

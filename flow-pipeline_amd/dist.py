@@ -243,13 +243,14 @@ class _Close:
         return result
 
     # -- the stages: (device buffer, rows) each
-    def exchange_by_owner(self, timeslot):
-        """this rank's rows, cut by owner (hash of the key) in HBM -> one all-to-all -> every rank's rows of the keys THIS rank owns"""
+    def exchange_by_owner(self, timeslot, rows=None):
+        """this rank's rows, cut by owner (hash of the key) in HBM -> one all-to-all -> every rank's rows of the keys THIS rank owns.
+        rows: the local rows step, () -> (device pointer, n); rows_device(kind, timeslot) unless the caller says otherwise."""
         import torch.distributed as dist
         world = dist.get_world_size(self.group)
 
         def cut():
-            ptr, n = self.agg.rows_device(self.kind, timeslot)
+            ptr, n = rows() if rows is not None else self.agg.rows_device(self.kind, timeslot)
             return self.agg.rows_partition_device(self.kind, ptr, n, world)
         pptr, counts = self.local(cut, (0, [-1] * world))
         return self.exchange(lambda: alltoall_device_rows(pptr, counts, self.row_bytes, group=self.group))
@@ -414,15 +415,18 @@ def minute_series_merged(agg, group=None, device=None) -> np.ndarray:
     return rows_merged(agg, ROWS_MINUTE, group=group)
 
 
-def top_talkers_merged(agg, dst, k=0, group=None) -> np.ndarray:
+def top_talkers_merged(agg, dst, k=0, group=None, t_lo=None, t_hi=None) -> np.ndarray:
     """Exact top talkers across ranks, identical on every rank and equal to FlowAgg.top_talkers of one ctx that folded every
     rank's records.  A rank's top k says nothing about the global one (a key that is tenth everywhere can lead overall), so the
     WHOLE table travels, hash-partitioned: rows_device(k = 0) -> fa_rows_partition_device -> one all-to-all -> rows_merge_device
     cut at k (this rank's share: its keys, complete - the global first k are among the shares' first k) -> all-gather of the
-    shares' k rows -> rows_merge_device cut at k.  k = 0: every group."""
+    shares' k rows -> rows_merge_device cut at k.  k = 0: every group.
+    t_lo / t_hi (every rank's ctx bucketed, with one bucket_secs): FlowAgg.top_talkers' range - the local rows come from
+    talkers_range_rows_device(k = 0) instead, everything behind them is the same."""
     from . import ALL_TIMESLOTS, ROWS_TALKERS_DST, ROWS_TALKERS_SRC
     close = _Close(agg, ROWS_TALKERS_DST if dst else ROWS_TALKERS_SRC, group)
-    sptr, m = close.merge(*close.exchange_by_owner(ALL_TIMESLOTS), k)  # this rank's share, cut at k
+    ranged = None if t_lo is None and t_hi is None else (lambda: agg.talkers_range_rows_device(dst, t_lo, t_hi))
+    sptr, m = close.merge(*close.exchange_by_owner(ALL_TIMESLOTS, ranged), k)  # this rank's share, cut at k
     return close.merge_and_fetch(*close.gather(sptr, m), k, "the merge of the shares' rows")
 
 

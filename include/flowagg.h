@@ -440,6 +440,47 @@ int fa_merge_talkers_device(fa_ctx*, int dst, const void* d_rows, size_t n);
 int fa_talkers_reset(fa_ctx*);
 int fa_talkers_stats(fa_ctx*, fa_talkers_stats_t* out);
 
+/* ---- ABI 8, addition: exact top talkers for a time range (bucketed tables) ------- */
+/* Both top-talker queries read "... FROM flows_raw WHERE $timeFilter GROUP BY ..." with $dateTimeCol = TimeFlowStart
+ * (viz-ch.json:66,225,471).  fa_talkers_enable_buckets is fa_talkers_enable with a time axis: the group key becomes
+ * (bucket, canonical address, family), bucket = t32 - t32 % bucket_secs with t32 = (uint32_t)TimeFlowStart (the DateTime
+ * narrowing of create.sh:40, the rule FA_KEYS_MINUTE_SERIES follows).  bucket_secs >= 1 and divides 86400, FA_ERR_ARG
+ * otherwise.  A ctx is enabled at most once, by either call: a second call of either kind is FA_ERR_ARG.  A ctx enabled with
+ * plain fa_talkers_enable behaves exactly as before and reads no time column.
+ * On a bucketed ctx:
+ *  - fa_talkers_fold_columns_device also reads cols->time_flow_start (8-byte aligned; FA_ERR_ARG without it); the capacity
+ *    rule is unchanged (a chunk of m records adds at most m keys per table), but a key now occupies one slot PER BUCKET it
+ *    was seen in: fa_talkers_stats' used[] counts (bucket, key) slots;
+ *  - fa_top_talkers, fa_rows_device(FA_ROWS_TALKERS_*) and fa_group_top_talkers mean "every bucket held": the same result,
+ *    byte for byte, as a plain ctx over the same records;
+ *  - fa_merge_talkers / fa_merge_talkers_device return FA_ERR_UNSUPPORTED: an fa_talker_row carries no time.  Partitions
+ *    meet through rows in HBM (fa_talkers_range_rows_device -> fa_rows_partition_device -> fa_rows_merge_device, which is
+ *    what fa_group_top_talkers_range and dist.top_talkers_merged(t_lo, t_hi) do);
+ *  - fa_talkers_reset empties everything and keeps bucket_secs.
+ * Every call below returns FA_ERR_UNSUPPORTED on a ctx that is not enabled or was enabled without buckets. */
+int fa_talkers_enable_buckets(fa_ctx*, uint32_t capacity_log2, uint32_t bucket_secs);
+/* The groups of the well-formed records with t_lo <= t32 < t_hi: sums over the buckets mod 2^64, each key once, in
+ * fa_top_talkers' order (weight DESC, key bytes, etype), cut after k rows (0: all).  t_lo lies on the bucket grid; t_hi lies
+ * on the grid or is 0xFFFFFFFF = no upper bound - the only way to include the last bucket of the axis (so with
+ * bucket_secs = 1, where 0xFFFFFFFF is itself on the grid, an EXCLUSIVE bound of 0xFFFFFFFF cannot be expressed: it always
+ * means "to the end" - and t_lo = t_hi = 0xFFFFFFFF is the empty range like every t_lo == t_hi, so with bucket_secs = 1 the
+ * last second of the axis cannot be read on its own, only together with the one before it: t_lo = 0xFFFFFFFE).  Off-grid
+ * values and t_lo > t_hi are FA_ERR_ARG; t_lo == t_hi gives zero rows.  FA_ERR_CAPACITY: *n_out = rows needed.
+ * $timeFilter's exact expansion belongs to the Grafana ClickHouse plugin, which is not part of the reference tree.  It is
+ * believed to be inclusive at both ends (TimeFlowStart >= from AND TimeFlowStart <= to), so a caller would pass
+ * t_hi = to + 1 rounded up to the grid.  This is unverified. */
+int fa_top_talkers_range(fa_ctx*, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, fa_talker_row* out, size_t cap, size_t* n_out);
+/* The same result left in HBM (*d_rows: DEVICE pointer, owned by the ctx, valid until its next call): the ranged twin of
+ * fa_rows_device(FA_ROWS_TALKERS_*).  Its rows go into fa_rows_partition_device / fa_rows_merge_device with kind 8 / 9. */
+int fa_talkers_range_rows_device(fa_ctx*, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, const void** d_rows, size_t* n_out);
+/* The bucket starts held in either table, ascending (fa_open_timeslots' contract; FA_ERR_CAPACITY: *n_out = needed). */
+int fa_talkers_buckets(fa_ctx*, uint32_t* out, size_t cap, size_t* n_out);
+/* Removes every bucket that starts below t (on the grid, FA_ERR_ARG otherwise).  Slots are write-once, so both tables are
+ * rebuilt into fresh ones of the same size (twice both tables' memory for the duration: both fresh tables are allocated before
+ * either is rebuilt, so FA_ERR_NOMEM drops nothing in either direction); used[] is counted again, capacity[] stays.  No floor is remembered: a record that arrives later with a time below t is folded like any other and opens its
+ * bucket again - what a late INSERT does to flows_5m.  A consumer that wants it gone drops again. */
+int fa_talkers_drop_before(fa_ctx*, uint32_t t);
+
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
  *   if(EType = 0x800, IPv4NumToString(reinterpretAsUInt32(substring(reverse(Addr), 13, 4))), IPv6NumToString(Addr))
@@ -562,6 +603,11 @@ int fa_group_topk(fa_group*, uint32_t key_set, size_t k, fa_topk_row* out, size_
  * every partition, byte for byte.  A member without fa_talkers_enable -> FA_ERR_UNSUPPORTED before anything is exchanged (the
  * group's and every member's last error name it).  FA_ERR_CAPACITY: *n_out = rows needed. */
 int fa_group_top_talkers(fa_group*, int dst, size_t k, fa_talker_row* out, size_t cap, size_t* n_out);
+/* ABI 8, addition: fa_group_top_talkers with every member's rows coming from fa_talkers_range_rows_device(k = 0) instead of
+ * fa_rows_device; the result equals fa_top_talkers_range of ONE ctx that folded every partition.  A member that is not
+ * bucketed -> FA_ERR_UNSUPPORTED, members with different bucket_secs -> FA_ERR_ARG: both before anything is exchanged, the
+ * member named in the group's and every member's last error.  On bucketed members fa_group_top_talkers means every bucket. */
+int fa_group_top_talkers_range(fa_group*, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, fa_talker_row* out, size_t cap, size_t* n_out);
 /* fa_stats summed over the members (kernel_ns: the slowest member's last launch). */
 int fa_group_stats(fa_group*, fa_stats_t* out);
 
