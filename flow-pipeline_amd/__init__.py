@@ -85,6 +85,10 @@ class TalkersStats(C.Structure):
         return d
 
 
+class PortsStats(TalkersStats):
+    """fa_ports_stats_t: fa_talkers_stats_t's members over the bucketed port tables (SrcPort, DstPort)."""
+
+
 class MockParams(C.Structure):
     _fields_ = [
         ("mode", C.c_uint32), ("framed", C.c_uint32), ("seed", C.c_uint64),
@@ -129,6 +133,8 @@ TALKER_ROW_DTYPE = np.dtype([("key", "u1", 16), ("etype", "<u4"), ("_pad", "<u4"
 assert TALKER_ROW_DTYPE.itemsize == 40
 # geometry of the fold kernel (csrc/talkers.cuh): threads per workgroup, LDS cache entries per direction, workgroups per CU
 TALK_BLOCK, TALK_LDS_ENTRIES, TALK_WG_PER_CU = 512, 512, 2
+# ... and of the port fold kernel (csrc/ports.cuh)
+PORT_BLOCK, PORT_LDS_ENTRIES, PORT_WG_PER_CU = 512, 512, 2
 assert ROW5M_DTYPE.itemsize == 48 and FLOW_ROW_DTYPE.itemsize == 120
 assert ROW_APP_DTYPE.itemsize == 56 and PORT_ROW_DTYPE.itemsize == 24 and MINUTE_ROW_DTYPE.itemsize == 24
 ROW_DTYPES = [ROW5M_DTYPE, ROW_APP_DTYPE, PORT_ROW_DTYPE, PORT_ROW_DTYPE, MINUTE_ROW_DTYPE, TOPK_DTYPE, TOPK_DTYPE,
@@ -152,6 +158,8 @@ EXPORTS = [
     "fa_merge_talkers_device", "fa_group_top_talkers",
     "fa_talkers_enable_buckets", "fa_top_talkers_range", "fa_talkers_range_rows_device", "fa_talkers_buckets", "fa_talkers_drop_before",
     "fa_group_top_talkers_range",
+    "fa_ports_enable_buckets", "fa_ports_fold_columns_device", "fa_top_ports_range", "fa_ports_range_rows_device", "fa_ports_buckets",
+    "fa_ports_drop_before", "fa_ports_reset", "fa_ports_stats", "fa_group_top_ports_range",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -325,6 +333,15 @@ def lib():
     L.fa_talkers_buckets.argtypes = [vp, vp, sz, szp]
     L.fa_talkers_drop_before.argtypes = [vp, u32]
     L.fa_group_top_talkers_range.argtypes = [vp, C.c_int, u32, u32, sz, vp, sz, szp]
+    L.fa_ports_enable_buckets.argtypes = [vp, u32, u32]
+    L.fa_ports_fold_columns_device.argtypes = [vp, C.POINTER(Columns), sz]
+    L.fa_top_ports_range.argtypes = [vp, C.c_int, u32, u32, sz, vp, sz, szp]
+    L.fa_ports_range_rows_device.argtypes = [vp, C.c_int, u32, u32, sz, C.POINTER(C.c_void_p), szp]
+    L.fa_ports_buckets.argtypes = [vp, vp, sz, szp]
+    L.fa_ports_drop_before.argtypes = [vp, u32]
+    L.fa_ports_reset.argtypes = [vp]
+    L.fa_ports_stats.argtypes = [vp, C.POINTER(PortsStats)]
+    L.fa_group_top_ports_range.argtypes = [vp, C.c_int, u32, u32, sz, vp, sz, szp]
     _LIB = L
     return L
 
@@ -437,7 +454,7 @@ def _rows_with_room(call, chk, dtype, cap, fresh=np.empty):
         return out[:n.value]
 
 
-NO_UPPER_BOUND = 0xFFFFFFFF  # t_hi of a talker range: to the end of the 32-bit time axis, its last bucket included
+NO_UPPER_BOUND = 0xFFFFFFFF  # t_hi of a talker or port range: to the end of the 32-bit time axis, its last bucket included
 
 
 def _talker_range(t_lo, t_hi):
@@ -707,6 +724,49 @@ class FlowAgg:
         self._chk(self._L.fa_talkers_stats(self._h, C.byref(s)))
         return s.as_dict()
 
+    # -- exact top ports for a time range (opt-in, the same second pass) ---------------------
+    def ports_enable_buckets(self, capacity_log2=0, bucket_secs=60):
+        """From now on every ingest also folds its records' SrcPort / DstPort into two exact tables keyed by
+        (bucket of TimeFlowStart, port) - what the port panels group by under $timeFilter (viz-ch.json:358,604).
+        Independent of FA_KEYS_PORT_HIST and of the talkers; top_ports / merge_ports / dashboard_reset never see these tables."""
+        self._chk(self._L.fa_ports_enable_buckets(self._h, capacity_log2, bucket_secs))
+
+    def ports_fold_columns_device(self, cols: Columns, n: int):
+        """The same fold for columns that are already decoded (device pointers; src_port, dst_port, bytes, sampling_rate,
+        status and time_flow_start are read)."""
+        self._chk(self._L.fa_ports_fold_columns_device(self._h, C.byref(cols), n))
+
+    def top_ports_range(self, dst: int, k: int = 0, t_lo=None, t_hi=None) -> np.ndarray:
+        """GROUP BY SrcPort (dst=0) / DstPort (dst=1) over the records with t_lo <= TimeFlowStart (32 bits) < t_hi, ORDER BY
+        sum(Bytes*SamplingRate) DESC, port: every port (k=0) or the first k.  Either bound alone leaves the other end open."""
+        lo, hi = _talker_range(t_lo, t_hi)
+        call = lambda out, cap, n: self._L.fa_top_ports_range(self._h, dst, lo, hi, int(k), out.ctypes.data, cap, C.byref(n))
+        return _rows_with_room(call, self._chk, PORT_ROW_DTYPE, max(int(k), 1) if k else 1 << 12, np.zeros).copy()
+
+    def ports_range_rows_device(self, dst: int, t_lo=None, t_hi=None, k: int = 0):
+        """-> (device pointer, n): top_ports_range(dst, k, t_lo, t_hi) left in HBM (valid until the ctx's next call) - rows of
+        kind ROWS_PORT_SRC / _DST for rows_partition_device / rows_merge_device."""
+        lo, hi = _talker_range(t_lo, t_hi)
+        p, n = C.c_void_p(), C.c_size_t()
+        self._chk(self._L.fa_ports_range_rows_device(self._h, dst, lo, hi, int(k), C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
+
+    def ports_buckets(self) -> np.ndarray:
+        """The bucket starts held in either port table, ascending."""
+        return _rows_with_room(lambda out, cap, n: self._L.fa_ports_buckets(self._h, out.ctypes.data, cap, C.byref(n)), self._chk, np.uint32, 1 << 10, np.zeros).copy()
+
+    def ports_drop_before(self, t: int):
+        """Removes every bucket that starts below t (on the bucket grid).  Records below t that arrive later open their bucket again."""
+        self._chk(self._L.fa_ports_drop_before(self._h, int(t)))
+
+    def ports_reset(self):
+        self._chk(self._L.fa_ports_reset(self._h))
+
+    def ports_stats(self) -> dict:
+        s = PortsStats()
+        self._chk(self._L.fa_ports_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
     # -- sketches -------------------------------------------------------------------
     def cms_read(self, key_set) -> np.ndarray:
         words = self.cfg.cms_depth << self.cfg.cms_width_log2
@@ -839,6 +899,13 @@ class FlowGroup:
             return self._rows(lambda out, c, n: self._L.fa_group_top_talkers(self._h, dst, int(k), out.ctypes.data, c, C.byref(n)), kind, cap)
         lo, hi = _talker_range(t_lo, t_hi)
         return self._rows(lambda out, c, n: self._L.fa_group_top_talkers_range(self._h, dst, lo, hi, int(k), out.ctypes.data, c, C.byref(n)), kind, cap)
+
+    def top_ports_range(self, dst: int, k: int = 0, cap=None, t_lo=None, t_hi=None) -> np.ndarray:
+        """FlowAgg.top_ports_range of ONE ctx that folded every member's partition (every member enabled, with one bucket_secs)."""
+        kind = ROWS_PORT_DST if dst else ROWS_PORT_SRC
+        cap = cap if cap is not None else (max(int(k), 1) if k else 1 << 12)
+        lo, hi = _talker_range(t_lo, t_hi)
+        return self._rows(lambda out, c, n: self._L.fa_group_top_ports_range(self._h, dst, lo, hi, int(k), out.ctypes.data, c, C.byref(n)), kind, cap)
 
     def stats(self) -> dict:
         s = Stats()

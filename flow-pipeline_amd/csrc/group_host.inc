@@ -701,6 +701,27 @@ extern "C" int fa_group_top_talkers_range(fa_group* g, int dst, uint32_t t_lo, u
     return group_top_talkers(g, dst, range, k, out, cap, n_out);
 }
 
+// ---- exact top ports of a range over the members' bucketed port tables -----------------------------------------------------------
+// fa_top_ports_range of ONE ctx that folded every partition.  Port rows are a small set (at most 65536 rows per member plus its
+// large ports), so nothing is partitioned: every member's WHOLE ranged result (fa_ports_range_rows_device, k = 0 - a port that
+// no member ranks first can lead overall) is gathered on one root and merged there, cut at k.  Checked before anything is
+// collected or exchanged: a member that is not enabled -> FA_ERR_UNSUPPORTED, members with different bucket_secs -> FA_ERR_ARG.
+extern "C" int fa_group_top_ports_range(fa_group* g, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, fa_port_row* out, size_t cap, size_t* n_out) {
+    int rc = group_args(g, out, cap, n_out);
+    if (rc) return rc;
+    if (dst != 0 && dst != 1) return gfail(g, FA_ERR_ARG, "fa_group_top_ports_range: bad argument");
+    *n_out = 0;
+    for (size_t i = 0; i < g->m.size(); i++) {  // (gfail_member names member i in every member's error)
+        const uint32_t bs = port_bucket_secs(g->m[i]);
+        if (bs && bs == port_bucket_secs(g->m[0])) continue;
+        rc = gfail_member(g, i, bs ? fail(g->m[i], FA_ERR_ARG, "bucket_secs differs from member 0's") : fail(g->m[i], FA_ERR_UNSUPPORTED, PORT_OFF), "top ports of a range");
+        g->m[i]->err = "group: " + g->err;
+        return rc;
+    }
+    const GroupRowsSource all_rows = [=](size_t i, const void** d, size_t* m) { return fa_ports_range_rows_device(g->m[i], dst, t_lo, t_hi, 0, d, m); };
+    return group_rows_merged(g, dst ? RK_PORT_DST : RK_PORT_SRC, 0, 0, k, out, cap, n_out, nullptr, all_rows);
+}
+
 // ---- what a consumer asks before a flush, and at exit ----------------------------------------------------------------------
 extern "C" int fa_group_open_timeslots(fa_group* g, uint32_t* out, size_t cap, size_t* n_out) {
     int rc = group_args(g, out, cap, n_out);

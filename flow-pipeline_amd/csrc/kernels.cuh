@@ -34,3 +34,4 @@
 #include "merge.cuh"
 #include "framing.cuh"
 #include "talkers.cuh"
+#include "ports.cuh"

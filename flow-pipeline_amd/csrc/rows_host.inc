@@ -427,11 +427,15 @@ static int rows_merge(fa_ctx* c, hipStream_t stream, ReadClock& clk, int kind, c
 static bool is_talker_kind(int kind) { return kind == RK_TALKERS_SRC || kind == RK_TALKERS_DST; }
 static const char TALK_OFF[] = "top talkers are not enabled on this ctx (fa_talkers_enable)";
 static const char TALK_NOT_CANONICAL[] = "fa_merge_talkers: a row is not canonical (etype 0 or 0x800; bytes 4..15 zero under 0x800)";
-struct TalkRange;  // a range of bucket indices of a bucketed ctx's tables (talkers_host.inc); nullptr = every slot
-static int collect_talkers(fa_ctx* c, ReadClock& clk, int kind, const TalkRange* range, const void*& in, size_t& n);
+static int collect_talkers(fa_ctx* c, ReadClock& clk, int kind, const BucketRange* range, const void*& in, size_t& n);
 static bool talk_rows_hold(const fa_ctx* c, const void* p);
 static const char TALK_NOT_BUCKETED[] = "the ctx's top talkers have no time axis (fa_talkers_enable_buckets)";
 static uint32_t talk_bucket_secs(const fa_ctx* c);  // 0: not enabled, or plain tables
+// the bucketed port tables live in ports_host.inc (PortState): the port kinds' RANGED reads collect from them - and from nothing
+// else; the un-ranged reads never look at them
+static const char PORT_OFF[] = "bucketed port tables are not enabled on this ctx (fa_ports_enable_buckets)";
+static int collect_ports_range(fa_ctx* c, ReadClock& clk, int kind, const BucketRange& range, const void*& in, size_t& n);
+static uint32_t port_bucket_secs(const fa_ctx* c);  // 0: not enabled
 
 static int kind_enabled(fa_ctx* c, int kind) {
     switch (kind) {
@@ -595,13 +599,15 @@ static int collect_topk(fa_ctx* c, ReadClock& clk, int kind, size_t k, size_t se
 
 // The ctx's own result for (kind, timeslot): what the matching read call returns, left in HBM (or, to_host, written
 // straight into the pinned host buffer when it fits): the window, then collect, then merge.
-// (talk_range: the talker kinds' ranged reads - where the rows come from is the only difference)
+// (range: the ranged reads of the talker kinds and of the port kinds - where the rows come from is the only difference: a
+// bucketed table of talkers_host.inc / ports_host.inc instead of the kind's un-ranged state)
 static int rows_local(fa_ctx* c, ReadClock& clk, int kind, uint32_t timeslot, size_t k, const void** out, size_t* n_out, bool to_host = false, bool* in_host = nullptr,
-                      const TalkRange* talk_range = nullptr) {
+                      const BucketRange* range = nullptr) {
     *out = nullptr;
     *n_out = 0;
     if (in_host) *in_host = false;
-    int rc = kind_enabled(c, kind);
+    const bool ports_ranged = range && (kind == RK_PORT_SRC || kind == RK_PORT_DST);
+    int rc = ports_ranged ? (c->ports ? FA_OK : fail(c, FA_ERR_UNSUPPORTED, PORT_OFF)) : kind_enabled(c, kind);
     if (rc) return rc;
     Window w;
     if ((kind == RK_5M || kind == RK_APP) && !window_of(c, timeslot, w)) return FA_OK;  // not a bucket boundary: no rows
@@ -618,9 +624,9 @@ static int rows_local(fa_ctx* c, ReadClock& clk, int kind, uint32_t timeslot, si
         switch (kind) {
         case RK_5M: rc = collect_5m(c, clk, w.lo, w.hi, in, n); break;
         case RK_APP: rc = collect_app(c, clk, w.lo, w.hi, in, n); break;
-        case RK_PORT_SRC: case RK_PORT_DST: case RK_MINUTE: rc = collect_w(c, clk, kind, in, n); break;
+        case RK_PORT_SRC: case RK_PORT_DST: case RK_MINUTE: rc = ports_ranged ? collect_ports_range(c, clk, kind, *range, in, n) : collect_w(c, clk, kind, in, n); break;
         case RK_TOPK_SRC: case RK_TOPK_DST: rc = collect_topk(c, clk, kind, k, sel_k, sel_partial, in, n); break;
-        case RK_TALKERS_SRC: case RK_TALKERS_DST: rc = collect_talkers(c, clk, kind, talk_range, in, n); break;  // (a plain table holds a key once and k only cuts; a bucketed one once per bucket: the merge sums)
+        case RK_TALKERS_SRC: case RK_TALKERS_DST: rc = collect_talkers(c, clk, kind, range, in, n); break;  // (a plain table holds a key once and k only cuts; a bucketed one once per bucket: the merge sums)
         default: return fail(c, FA_ERR_ARG, "unknown row kind");
         }
         if (rc) return rc;
@@ -736,12 +742,12 @@ static int rows_copy_out(fa_ctx* c, const void* d, size_t n, size_t row_bytes, b
     }
     return copy_out_pipelined(c, out, d, n * row_bytes);
 }
-static int rows_read(fa_ctx* c, int kind, uint32_t timeslot, size_t k, void* out, size_t cap, size_t* n_out, const TalkRange* talk_range = nullptr) {
+static int rows_read(fa_ctx* c, int kind, uint32_t timeslot, size_t k, void* out, size_t cap, size_t* n_out, const BucketRange* range = nullptr) {
     const void* d = nullptr;
     size_t n = 0;
     bool in_host = false;
     ReadClock clk(c);
-    int rc = rows_local(c, clk, kind, timeslot, k, &d, &n, true, &in_host, talk_range);
+    int rc = rows_local(c, clk, kind, timeslot, k, &d, &n, true, &in_host, range);
     if (rc) return rc;
     if (n > cap) {  // (the caller asks again with room for *n_out rows; nothing was removed)
         HIPCHK(c, hipStreamSynchronize(c->stream));

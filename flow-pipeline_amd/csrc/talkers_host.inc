@@ -221,23 +221,6 @@ static int talk_fold_cols(fa_ctx* c, const TalkCols& p, size_t n) {
     return FA_OK;
 }
 
-// The second pass of an enabled ctx's ingest call (ingest_device_any): the call's n records decoded again in chunks -
-// fa_decode_device's launch on the sub-range (d_buf, len, d_off + i, m) - and each chunk's columns folded, all on the ctx stream
-// behind the launches of the ingest itself.
-static int talk_fold_records(fa_ctx* c, const void* d_buf, size_t len, const uint32_t* d_off, size_t n) {
-    for (size_t i = 0; i < n;) {
-        const size_t m = std::min({n - i, talk_chunk_cap(c), (size_t)c->cfg.max_batch_records});
-        fa_columns cols;
-        int rc = decode_device_records(c, d_buf, len, (size_t)((double)len * (double)m / (double)n), d_off + i, m, &cols);
-        if (rc) return rc;
-        const TalkCols p{cols.src_addr, cols.dst_addr, cols.etype, cols.bytes, cols.sampling_rate, cols.status, cols.time_flow_start};
-        rc = talk_fold_cols(c, p, m);
-        if (rc) return rc;
-        i += m;
-    }
-    return FA_OK;
-}
-
 extern "C" int fa_talkers_fold_columns_device(fa_ctx* c, const fa_columns* cols, size_t n) {
     TALK_ENTER(c);
     if (n == 0) return FA_OK;
@@ -314,24 +297,19 @@ extern "C" int fa_merge_talkers_device(fa_ctx* c, int dst, const void* d_rows, s
 
 // ---- the talker row kinds of the device-resident close (rows_host.inc: rows_local, fa_rows_merge_device) ---------------------
 static bool talk_rows_hold(const fa_ctx* c, const void* p) { return c->talk && inside(c->talk->rows, p); }
-// [t_lo, t_hi) of a bucketed ctx as bucket indices (the last one inclusive: the last index of the axis has no successor)
-struct TalkRange {
-    uint32_t index_lo = 0, index_last = 0;
-    bool empty = false;  // t_lo == t_hi
-};
-static int talk_range_of(fa_ctx* c, uint32_t t_lo, uint32_t t_hi, TalkRange& r) {
-    const uint32_t bs = c->talk->bucket_secs;
-    if (t_lo % bs || (t_hi != 0xFFFFFFFFu && t_hi % bs)) return fail(c, FA_ERR_ARG, "talker range: t_lo and t_hi lie on the bucket grid (t_hi = 0xFFFFFFFF: no upper bound)");
-    if (t_lo > t_hi) return fail(c, FA_ERR_ARG, "talker range: t_lo > t_hi");
-    r.empty = t_lo == t_hi;
-    r.index_lo = t_lo / bs;
-    r.index_last = t_hi == 0xFFFFFFFFu ? 0xFFFFFFFFu / bs : t_hi / bs - (r.empty ? 0u : 1u);
-    return FA_OK;
+// [t_lo, t_hi) on the grid of bucket_secs as bucket indices (bucket_range.h states the rule): the talker tables' ranged reads
+// and the port tables' (ports_host.inc) share it.
+static int talk_range_of(fa_ctx* c, uint32_t bucket_secs, uint32_t t_lo, uint32_t t_hi, BucketRange& r) {
+    switch (bucket_range_of(bucket_secs, t_lo, t_hi, r)) {
+    case BUCKET_RANGE_OFF_GRID: return fail(c, FA_ERR_ARG, "range: t_lo and t_hi lie on the bucket grid (t_hi = 0xFFFFFFFF: no upper bound)");
+    case BUCKET_RANGE_REVERSED: return fail(c, FA_ERR_ARG, "range: t_lo > t_hi");
+    default: return FA_OK;
+    }
 }
 // Table d's occupied slots as fa_talker_row, unordered, in the state's row buffer: the exact count first (it sizes the buffer
 // and reports lost updates), then one scan of the table.  range: only the slots of those buckets (their count is not known
 // beforehand: the table's count bounds it, and the cursor says how many there were).
-static int collect_talkers(fa_ctx* c, ReadClock& clk, int kind, const TalkRange* range, const void*& in, size_t& n) {
+static int collect_talkers(fa_ctx* c, ReadClock& clk, int kind, const BucketRange* range, const void*& in, size_t& n) {
     TalkState* t = c->talk;
     const int d = kind == RK_TALKERS_DST;
     TalkCounters h;
@@ -493,16 +471,16 @@ static int talk_order_rows(fa_ctx* c, hipStream_t stream, const TalkRow* rows, u
 extern "C" int fa_top_talkers_range(fa_ctx* c, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, fa_talker_row* out, size_t cap, size_t* n_out) {
     TALK_ENTER_BUCKETED(c);
     if ((dst != 0 && dst != 1) || !n_out || (!out && cap)) return fail(c, FA_ERR_ARG, "fa_top_talkers_range: bad argument");
-    TalkRange r;
-    int rc = talk_range_of(c, t_lo, t_hi, r);
+    BucketRange r;
+    int rc = talk_range_of(c, c->talk->bucket_secs, t_lo, t_hi, r);
     if (rc) return rc;
     return rows_read(c, dst ? RK_TALKERS_DST : RK_TALKERS_SRC, 0, k, out, cap, n_out, &r);
 }
 extern "C" int fa_talkers_range_rows_device(fa_ctx* c, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, const void** d_rows, size_t* n_out) {
     TALK_ENTER_BUCKETED(c);
     if ((dst != 0 && dst != 1) || !n_out || !d_rows) return fail(c, FA_ERR_ARG, "fa_talkers_range_rows_device: bad argument");
-    TalkRange r;
-    int rc = talk_range_of(c, t_lo, t_hi, r);
+    BucketRange r;
+    int rc = talk_range_of(c, c->talk->bucket_secs, t_lo, t_hi, r);
     if (rc) return rc;
     const int kind = dst ? RK_TALKERS_DST : RK_TALKERS_SRC;
     ReadClock clk(c);
@@ -513,28 +491,22 @@ extern "C" int fa_talkers_range_rows_device(fa_ctx* c, int dst, uint32_t t_lo, u
     return FA_OK;
 }
 
-// The bucket starts held in either table, ascending (fa_open_timeslots' contract).  Min and max index first; a span of up to 2^16
-// indices is answered from one bit per index, a wider one (bucket_secs = 1 over days, stray times) from the slots' own indices.
-extern "C" int fa_talkers_buckets(fa_ctx* c, uint32_t* out, size_t cap, size_t* n_out) {
-    TALK_ENTER_BUCKETED(c);
-    if (!n_out || (!out && cap)) return fail(c, FA_ERR_ARG, "fa_talkers_buckets: bad argument");
-    TalkState* t = c->talk;
-    TalkCounters h;
-    int rc = talk_settle(c, h);
-    if (rc) return rc;
-    t->used_ub[0] = h.used[0];
-    t->used_ub[1] = h.used[1];
+// The bucket starts held in a pair of bucketed tables, ascending (fa_open_timeslots' contract): what fa_talkers_buckets and
+// fa_ports_buckets (ports_host.inc) answer.  Min and max index first; a span of up to 2^16 indices is answered from one bit per
+// index, a wider one (bucket_secs = 1 over days, stray times) from the slots' own indices.
+//   held: the occupied slots of both tables; scratch: a buffer of the state, dead otherwise;
+//   scan(lo, nbits, bits, range): launches the tables' buckets kernel over both tables (bits == nullptr: min / max into range);
+//   list(out, cap, cursor): launches their bucket-list kernel over both.
+template <class Scan, class List>
+static int bucket_starts(fa_ctx* c, uint32_t bucket_secs, size_t held, DevBuf<>& scratch, Scan&& scan, List&& list, uint32_t* out, size_t cap, size_t* n_out) {
     constexpr uint32_t MAXBITS = 1u << 16;
-    const size_t held = (size_t)(h.used[0] + h.used[1]);
-    rc = ensure_dev(c, t->rows, std::max<size_t>(MAXBITS / 8 + 64, held * sizeof(uint32_t) + 64), "talker buckets");
+    int rc = ensure_dev(c, scratch, std::max<size_t>(MAXBITS / 8 + 64, held * sizeof(uint32_t) + 64), "buckets");
     if (rc) return rc;
-    unsigned int* range = (unsigned int*)t->rows.get();  // {min, max, any, cursor}
+    unsigned int* range = (unsigned int*)scratch.get();  // {min, max, any, cursor}
     unsigned int* bits = range + 16;
     const unsigned int init[4] = {0xffffffffu, 0u, 0u, 0u};
     HIPCHK(c, hipMemcpyAsync(range, init, sizeof init, hipMemcpyHostToDevice, c->stream));
-    auto grid = [&](int d) { return dim3((unsigned)std::min<uint64_t>(((1ull << t->log2[d]) + 255) / 256, (uint64_t)c->num_cus * 8)); };
-    for (int d = 0; d < 2; d++)
-        hipLaunchKernelGGL(talker_buckets_kernel, grid(d), dim3(256), 0, c->stream, (const TSlot*)t->tab[d], 1ull << t->log2[d], 0u, 0u, (unsigned int*)nullptr, range);
+    scan(0u, 0u, (unsigned int*)nullptr, range);
     HIPCHK(c, hipGetLastError());
     unsigned int r[3] = {0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(r, range, sizeof r, hipMemcpyDeviceToHost, c->stream));
@@ -544,8 +516,7 @@ extern "C" int fa_talkers_buckets(fa_ctx* c, uint32_t* out, size_t cap, size_t* 
         if (r[1] - r[0] < MAXBITS) {
             const uint32_t nbits = r[1] - r[0] + 1u, nwords = (nbits + 31u) / 32u;
             HIPCHK(c, hipMemsetAsync(bits, 0, nwords * sizeof(unsigned int), c->stream));
-            for (int d = 0; d < 2; d++)
-                hipLaunchKernelGGL(talker_buckets_kernel, grid(d), dim3(256), 0, c->stream, (const TSlot*)t->tab[d], 1ull << t->log2[d], r[0], nbits, bits, range);
+            scan(r[0], nbits, bits, range);
             HIPCHK(c, hipGetLastError());
             std::vector<unsigned int> hb(nwords);
             HIPCHK(c, hipMemcpyAsync(hb.data(), bits, nwords * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
@@ -553,23 +524,41 @@ extern "C" int fa_talkers_buckets(fa_ctx* c, uint32_t* out, size_t cap, size_t* 
             for (uint32_t i = 0; i < nbits; i++)
                 if (hb[i >> 5] >> (i & 31u) & 1u) idx.push_back(r[0] + i);
         } else {
-            uint32_t* list = (uint32_t*)(range + 16);
-            for (int d = 0; d < 2; d++)
-                hipLaunchKernelGGL(talker_bucket_list_kernel, grid(d), dim3(256), 0, c->stream, (const TSlot*)t->tab[d], 1ull << t->log2[d], list, (uint32_t)held, range + 3);
+            list((uint32_t*)(range + 16), (uint32_t)held, range + 3);
             HIPCHK(c, hipGetLastError());
             unsigned int got = 0;
             HIPCHK(c, read_word(range + 3, got, c->stream));
-            if (got != held) return fail(c, FA_ERR_HIP, "internal: the talker tables' slots and their counts differ");
+            if (got != held) return fail(c, FA_ERR_HIP, "internal: the bucketed tables' slots and their counts differ");
             idx.resize(got);
-            if (got) HIPCHK(c, hipMemcpy(idx.data(), list, (size_t)got * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if (got) HIPCHK(c, hipMemcpy(idx.data(), range + 16, (size_t)got * sizeof(uint32_t), hipMemcpyDeviceToHost));
             std::sort(idx.begin(), idx.end());
             idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
         }
     }
     *n_out = idx.size();
     if (idx.size() > cap) return fail(c, FA_ERR_CAPACITY, "output buffer too small");
-    for (size_t i = 0; i < idx.size(); i++) out[i] = idx[i] * t->bucket_secs;
+    for (size_t i = 0; i < idx.size(); i++) out[i] = idx[i] * bucket_secs;
     return FA_OK;
+}
+extern "C" int fa_talkers_buckets(fa_ctx* c, uint32_t* out, size_t cap, size_t* n_out) {
+    TALK_ENTER_BUCKETED(c);
+    if (!n_out || (!out && cap)) return fail(c, FA_ERR_ARG, "fa_talkers_buckets: bad argument");
+    TalkState* t = c->talk;
+    TalkCounters h;
+    int rc = talk_settle(c, h);
+    if (rc) return rc;
+    t->used_ub[0] = h.used[0];
+    t->used_ub[1] = h.used[1];
+    auto grid = [&](int d) { return dim3((unsigned)std::min<uint64_t>(((1ull << t->log2[d]) + 255) / 256, (uint64_t)c->num_cus * 8)); };
+    return bucket_starts(
+        c, t->bucket_secs, (size_t)(h.used[0] + h.used[1]), t->rows,
+        [&](uint32_t lo, uint32_t nbits, unsigned int* bits, unsigned int* range) {
+            for (int d = 0; d < 2; d++) hipLaunchKernelGGL(talker_buckets_kernel, grid(d), dim3(256), 0, c->stream, (const TSlot*)t->tab[d], 1ull << t->log2[d], lo, nbits, bits, range);
+        },
+        [&](uint32_t* list, uint32_t list_cap, unsigned int* cursor) {
+            for (int d = 0; d < 2; d++) hipLaunchKernelGGL(talker_bucket_list_kernel, grid(d), dim3(256), 0, c->stream, (const TSlot*)t->tab[d], 1ull << t->log2[d], list, list_cap, cursor);
+        },
+        out, cap, n_out);
 }
 
 // Removes every bucket that starts below t.  The slots are write-once, so nothing is deleted in place: each table is rebuilt into

@@ -404,9 +404,17 @@ def close_window_app_merged(agg, timeslot, group=None, device=None) -> np.ndarra
     return rows
 
 
-def top_ports_merged(agg, dst, k=None, group=None, device=None) -> np.ndarray:
-    """GROUP BY port across ranks (every rank's port rows travel: a port just below the cut everywhere can lead overall)."""
+def top_ports_merged(agg, dst, k=None, group=None, device=None, t_lo=None, t_hi=None) -> np.ndarray:
+    """GROUP BY port across ranks (every rank's port rows travel: a port just below the cut everywhere can lead overall).
+    t_lo / t_hi (every rank's ctx with ports_enable_buckets, one bucket_secs): FlowAgg.top_ports_range across ranks, identical
+    on every rank and equal to that call on one ctx that folded every rank's records - the local rows come from
+    ports_range_rows_device(k = 0) and are gathered and merged, cut at k (None or 0: every port).  Without a range the call
+    reads the FA_KEYS_PORT_HIST state, as ever."""
     from . import ROWS_PORT_DST, ROWS_PORT_SRC
+    if t_lo is not None or t_hi is not None:
+        close = _Close(agg, ROWS_PORT_DST if dst else ROWS_PORT_SRC, group)
+        ptr, n = close.local(lambda: agg.ports_range_rows_device(dst, t_lo, t_hi), (0, -1))
+        return close.merge_and_fetch(*close.gather(ptr, n), int(k or 0), "the merge of the gathered port rows")
     return rows_merged(agg, ROWS_PORT_DST if dst else ROWS_PORT_SRC, k_local=0, k=0 if k is None else max(int(k), 1), group=group)[:k]
 
 

@@ -481,6 +481,56 @@ int fa_talkers_buckets(fa_ctx*, uint32_t* out, size_t cap, size_t* n_out);
  * bucket again - what a late INSERT does to flows_5m.  A consumer that wants it gone drops again. */
 int fa_talkers_drop_before(fa_ctx*, uint32_t t);
 
+/* ---- ABI 8, addition: exact top ports for a time range (bucketed port tables) ---- */
+/* Both port panels read "... FROM flows_raw WHERE $timeFilter GROUP BY SrcPort" / "DstPort" (viz-ch.json:358,604) with
+ * $dateTimeCol = TimeFlowStart.  fa_ports_enable_buckets gives the ctx two hash tables of its own (SrcPort, DstPort; 32-byte
+ * slots) whose group key is (bucket, port):
+ *  - bucket = t32 - t32 % bucket_secs with t32 = (uint32_t)TimeFlowStart: the DateTime narrowing of create.sh:40, the rule of
+ *    FA_KEYS_MINUTE_SERIES and of fa_talkers_enable_buckets;
+ *  - port = the whole 32-bit column value (the column is UInt32): 65536 and above are keys like any other, never dropped or
+ *    folded together;
+ *  - values: sum(Bytes*SamplingRate) mod 2^64 and count(); only status == 0 records count; a group of weight 0 is still a row.
+ * bucket_secs >= 1 and divides 86400; capacity_log2 is 0 (-> 16) or 8..30; FA_ERR_ARG otherwise, and for a second enable.
+ * The feature takes no key_sets bit, does not depend on FA_KEYS_PORT_HIST, and is independent of the talkers: a ctx may enable
+ * either, both or neither.  From the enable on every successful fa_ingest / fa_ingest_device also folds its records' ports in
+ * the second pass the talkers use (each chunk is decoded once for every enabled fold; the consequences listed there - the
+ * column block is overwritten, decode_launches include the pass, a failing fold fails the call - hold here too).  The tables
+ * grow by themselves (doubling, load kept at or below 1/2; FA_ERR_TABLE_FULL beyond 2^30 slots).
+ * UNCHANGED: fa_top_ports, fa_merge_ports, fa_dashboard_reset and fa_rows_device(FA_ROWS_PORT_*) keep their meaning.  They read
+ * (and clear) the FA_KEYS_PORT_HIST state and nothing else: they never read or clear the bucketed tables, and nothing below
+ * reads or clears the FA_KEYS_PORT_HIST state.
+ * Every call below except the enable returns FA_ERR_UNSUPPORTED on a ctx that is not enabled. */
+typedef struct {
+    uint64_t used[2], capacity[2];   /* SrcPort, DstPort tables: occupied (bucket, port) slots / slots */
+    uint64_t records_folded;         /* status == 0 records folded so far */
+    uint64_t records_absorbed;       /* (record, direction) updates that ended in a workgroup's LDS cache, not in a global atomic */
+    uint64_t grows;                  /* table rebuilds that doubled a table */
+    uint64_t fold_launches, fold_ns_total; /* the fold kernel alone, hipEvent */
+} fa_ports_stats_t;
+int fa_ports_enable_buckets(fa_ctx*, uint32_t capacity_log2, uint32_t bucket_secs);
+/* The same fold for callers that already decode: n records of `cols` - any DEVICE pointers; only src_port, dst_port, bytes,
+ * sampling_rate, status and time_flow_start are read, each naturally aligned (4 / 4 / 8 / 8 / 1 / 8 bytes).  A missing or
+ * misaligned column is FA_ERR_ARG.  Asynchronous on the ctx stream. */
+int fa_ports_fold_columns_device(fa_ctx*, const fa_columns* cols, size_t n);
+/* dst = 0: GROUP BY SrcPort, 1: DstPort, over the well-formed records with t_lo <= t32 < t_hi: sums over the buckets mod 2^64,
+ * each port once, in fa_top_ports' order (weight DESC, then port ascending), cut after k rows (0: all).  The range rule is
+ * fa_top_talkers_range's, word for word: both bounds on the bucket grid, t_hi = 0xFFFFFFFF = no upper bound (the only way to
+ * include the last bucket of the axis), t_lo == t_hi the empty range, off-grid bounds and t_lo > t_hi FA_ERR_ARG.
+ * FA_ERR_CAPACITY: *n_out = rows needed. */
+int fa_top_ports_range(fa_ctx*, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, fa_port_row* out, size_t cap, size_t* n_out);
+/* The same result left in HBM (*d_rows: DEVICE pointer, owned by the ctx, valid until its next call), as rows of kind
+ * FA_ROWS_PORT_SRC / _DST for fa_rows_partition_device / fa_rows_merge_device. */
+int fa_ports_range_rows_device(fa_ctx*, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, const void** d_rows, size_t* n_out);
+/* The bucket starts held in either table, ascending (fa_talkers_buckets' contract; FA_ERR_CAPACITY: *n_out = needed). */
+int fa_ports_buckets(fa_ctx*, uint32_t* out, size_t cap, size_t* n_out);
+/* Removes every bucket that starts below t (on the grid, FA_ERR_ARG otherwise): fa_talkers_drop_before's contract.  Both tables
+ * are rebuilt into fresh ones of the same size, both allocated before either is rebuilt (FA_ERR_NOMEM drops nothing); used[] is
+ * counted again, capacity[] stays.  No floor is remembered: a later record with a time below t opens its bucket again. */
+int fa_ports_drop_before(fa_ctx*, uint32_t t);
+/* Empties both tables (they keep their size and bucket_secs); the counters of fa_ports_stats go on counting. */
+int fa_ports_reset(fa_ctx*);
+int fa_ports_stats(fa_ctx*, fa_ports_stats_t* out);
+
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
  *   if(EType = 0x800, IPv4NumToString(reinterpretAsUInt32(substring(reverse(Addr), 13, 4))), IPv6NumToString(Addr))
@@ -608,6 +658,11 @@ int fa_group_top_talkers(fa_group*, int dst, size_t k, fa_talker_row* out, size_
  * bucketed -> FA_ERR_UNSUPPORTED, members with different bucket_secs -> FA_ERR_ARG: both before anything is exchanged, the
  * member named in the group's and every member's last error.  On bucketed members fa_group_top_talkers means every bucket. */
 int fa_group_top_talkers_range(fa_group*, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, fa_talker_row* out, size_t cap, size_t* n_out);
+/* ABI 8, addition: fa_top_ports_range of ONE ctx that folded every partition.  Port rows are a small set: every member's whole
+ * ranged result (fa_ports_range_rows_device, k = 0) is gathered on one member and merged there, cut at k.  A member without
+ * fa_ports_enable_buckets -> FA_ERR_UNSUPPORTED, members with different bucket_secs -> FA_ERR_ARG: both before anything is
+ * exchanged, the member named in the group's and every member's last error. */
+int fa_group_top_ports_range(fa_group*, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, fa_port_row* out, size_t cap, size_t* n_out);
 /* fa_stats summed over the members (kernel_ns: the slowest member's last launch). */
 int fa_group_stats(fa_group*, fa_stats_t* out);
 
