@@ -89,6 +89,21 @@ class PortsStats(TalkersStats):
     """fa_ports_stats_t: fa_talkers_stats_t's members over the bucketed port tables (SrcPort, DstPort)."""
 
 
+class RawPart(C.Structure):
+    """fa_raw_part: one flows_raw part (a Native block of one Date) inside the bytes a take returned."""
+    _fields_ = [("date", C.c_uint32), ("t_min", C.c_uint32), ("t_max", C.c_uint32), ("_pad", C.c_uint32),
+                ("rows", C.c_uint64), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class RawStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "records_in", "records_bad", "rows_out", "parts_out", "bytes_out", "chunks", "pending_parts", "pending_bytes",
+        "build_ns_total", "build_launches")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class MockParams(C.Structure):
     _fields_ = [
         ("mode", C.c_uint32), ("framed", C.c_uint32), ("seed", C.c_uint64),
@@ -130,6 +145,8 @@ ROW_APP48_DTYPE = np.dtype([("src_addr", "u1", 16), ("dst_port", "<u4"), ("proto
 PORT_ROW_DTYPE = np.dtype([("port", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
 MINUTE_ROW_DTYPE = np.dtype([("minute", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
 TALKER_ROW_DTYPE = np.dtype([("key", "u1", 16), ("etype", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
+RAW_PART_DTYPE = np.dtype([("date", "<u4"), ("t_min", "<u4"), ("t_max", "<u4"), ("_pad", "<u4"), ("rows", "<u8"), ("offset", "<u8"), ("bytes", "<u8")])
+assert RAW_PART_DTYPE.itemsize == C.sizeof(RawPart) == 40 and C.sizeof(RawStats) == 80
 assert TALKER_ROW_DTYPE.itemsize == 40
 # geometry of the fold kernel (csrc/talkers.cuh): threads per workgroup, LDS cache entries per direction, workgroups per CU
 TALK_BLOCK, TALK_LDS_ENTRIES, TALK_WG_PER_CU = 512, 512, 2
@@ -160,6 +177,8 @@ EXPORTS = [
     "fa_group_top_talkers_range",
     "fa_ports_enable_buckets", "fa_ports_fold_columns_device", "fa_top_ports_range", "fa_ports_range_rows_device", "fa_ports_buckets",
     "fa_ports_drop_before", "fa_ports_reset", "fa_ports_stats", "fa_group_top_ports_range",
+    "fa_raw_part_bytes", "fa_flow_rows_to_native", "fa_raw_enable", "fa_raw_build_columns_device", "fa_raw_take", "fa_raw_take_device",
+    "fa_raw_reset", "fa_raw_stats",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -342,6 +361,15 @@ def lib():
     L.fa_ports_reset.argtypes = [vp]
     L.fa_ports_stats.argtypes = [vp, C.POINTER(PortsStats)]
     L.fa_group_top_ports_range.argtypes = [vp, C.c_int, u32, u32, sz, vp, sz, szp]
+    L.fa_raw_part_bytes.argtypes = [u64]
+    L.fa_raw_part_bytes.restype = sz
+    L.fa_flow_rows_to_native.argtypes = [vp, sz, vp, sz, szp]
+    L.fa_raw_enable.argtypes = [vp, u32]
+    L.fa_raw_build_columns_device.argtypes = [vp, C.POINTER(Columns), sz]
+    L.fa_raw_take.argtypes = [vp, vp, sz, szp, vp, sz, szp]
+    L.fa_raw_take_device.argtypes = [vp, C.POINTER(vp), szp, vp, sz, szp]
+    L.fa_raw_reset.argtypes = [vp]
+    L.fa_raw_stats.argtypes = [vp, C.POINTER(RawStats)]
     _LIB = L
     return L
 
@@ -377,6 +405,18 @@ def rows_to_rowbinary(rows: np.ndarray) -> bytes:
     rc = lib().fa_rows_to_rowbinary(r.ctypes.data, len(r), out.ctypes.data, out.size, C.byref(n))
     if rc:
         raise FlowAggError(rc, "fa_rows_to_rowbinary")
+    return out[:n.value].tobytes()
+
+
+def flow_rows_to_native(rows: np.ndarray) -> bytes:
+    """Decoded rows of ONE Date (status 0, ascending 32-bit TimeReceived) -> one flows_raw part: a ClickHouse Native block for
+    `INSERT INTO flows_raw FORMAT Native` (create.sh:36-62 column list).  Host code, no GPU."""
+    r = np.ascontiguousarray(rows, dtype=FLOW_ROW_DTYPE)
+    out = np.empty(lib().fa_raw_part_bytes(len(r)), dtype=np.uint8)
+    n = C.c_size_t()
+    rc = lib().fa_flow_rows_to_native(r.ctypes.data, len(r), out.ctypes.data, out.size, C.byref(n))
+    if rc:
+        raise FlowAggError(rc, "fa_flow_rows_to_native")
     return out[:n.value].tobytes()
 
 
@@ -765,6 +805,53 @@ class FlowAgg:
     def ports_stats(self) -> dict:
         s = PortsStats()
         self._chk(self._L.fa_ports_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
+    # -- flows_raw parts: sorted Native blocks per Date (opt-in, the same second pass) ---------
+    def raw_enable(self, chunk_records=0):
+        """From now on every ingest also builds flows_raw parts from its decoded columns: per chunk of at most chunk_records
+        records (0: 2^20) one ClickHouse Native block per Date, rows in stable order of the 32-bit TimeReceived, malformed
+        records dropped (create.sh:36-68).  The parts wait in HBM until raw_take."""
+        self._chk(self._L.fa_raw_enable(self._h, chunk_records))
+
+    def raw_build_columns(self, cols: Columns, n: int):
+        """The same build for columns that are already decoded (device pointers; all 15 columns and status are read).
+        Synchronous: the columns are not referenced after the call."""
+        self._chk(self._L.fa_raw_build_columns_device(self._h, C.byref(cols), n))
+
+    def raw_take(self, out: np.ndarray | None = None):
+        """-> (bytes, parts): every pending part back to back, in build order - the payload of `INSERT INTO flows_raw FORMAT
+        Native` - and their descriptions (RAW_PART_DTYPE: date, t_min, t_max, rows, offset, bytes); the pending parts are
+        cleared.  out: a uint8 buffer to fill (page-locked: one copy-engine transfer); bytes is then a view of it."""
+        nbytes, nparts = C.c_size_t(), C.c_size_t()
+        st = self.raw_stats()
+        cap, pcap = int(st["pending_bytes"]), max(int(st["pending_parts"]), 1)
+        while True:  # (its own ask-again loop: two buffers, and a caller's byte buffer is reused when it has room)
+            buf = out if out is not None and out.dtype == np.uint8 and out.size >= cap else np.empty(cap, dtype=np.uint8)
+            parts = np.zeros(pcap, dtype=RAW_PART_DTYPE)
+            rc = self._L.fa_raw_take(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(nbytes), parts.ctypes.data, pcap, C.byref(nparts))
+            if rc == -6:
+                cap, pcap = nbytes.value, max(nparts.value, 1)
+                continue
+            self._chk(rc)
+            data = buf[:nbytes.value]
+            return (data if out is not None and buf is out else data.tobytes()), parts[:nparts.value]
+
+    def raw_take_device(self):
+        """-> (device pointer, bytes, parts): raw_take with the bytes left in HBM (valid until the ctx's next ingest / raw call)."""
+        st = self.raw_stats()
+        pcap = max(int(st["pending_parts"]), 1)
+        parts = np.zeros(pcap, dtype=RAW_PART_DTYPE)
+        p, nbytes, nparts = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        self._chk(self._L.fa_raw_take_device(self._h, C.byref(p), C.byref(nbytes), parts.ctypes.data, pcap, C.byref(nparts)))
+        return p.value or 0, nbytes.value, parts[:nparts.value]
+
+    def raw_reset(self):
+        self._chk(self._L.fa_raw_reset(self._h))
+
+    def raw_stats(self) -> dict:
+        s = RawStats()
+        self._chk(self._L.fa_raw_stats(self._h, C.byref(s)))
         return s.as_dict()
 
     # -- sketches -------------------------------------------------------------------

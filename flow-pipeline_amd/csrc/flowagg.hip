@@ -31,6 +31,7 @@
 #include "buffers.h"
 #include "kernels.cuh"
 #include "launch_plan.h"
+#include "raw.cuh"
 
 using namespace fa;
 
@@ -222,6 +223,7 @@ struct fa_ctx {
 
     struct TalkState* talk = nullptr;  // exact top talkers (fa_talkers_enable; talkers_host.inc), nullptr = not enabled
     struct PortState* ports = nullptr;  // bucketed port tables (fa_ports_enable_buckets; ports_host.inc), nullptr = not enabled
+    struct RawState* raw = nullptr;     // flows_raw parts (fa_raw_enable; raw_host.inc), nullptr = not enabled
 
     fa_stats_t stats{};
     uint64_t used_base = 0;  // groups created before the current counter epoch
@@ -253,11 +255,12 @@ static int fail(fa_ctx* c, int code, const char* msg) {
     if (c) c->err = msg;
     return code;
 }
-// exact top talkers (talkers_host.inc) and bucketed port tables (ports_host.inc): the second pass behind an ingest call's launches
-// - one decode per chunk for every enabled fold - and the states' release
+// exact top talkers (talkers_host.inc), bucketed port tables (ports_host.inc) and flows_raw parts (raw_host.inc): the second pass
+// behind an ingest call's launches (second_pass.inc) - one decode per chunk for every enabled fold - and the states' release
 static int second_pass_records(fa_ctx* c, const void* d_buf, size_t len, const uint32_t* d_off, size_t n);
 static void talk_destroy(fa_ctx* c);
 static void port_destroy(fa_ctx* c);
+static void raw_destroy(fa_ctx* c);
 
 extern "C" uint32_t fa_abi_version(void) { return FA_ABI_VERSION; }
 
@@ -546,6 +549,7 @@ extern "C" void fa_destroy(fa_ctx* c) {
         }
     talk_destroy(c);
     port_destroy(c);
+    raw_destroy(c);
     const hipStream_t streams[3] = {c->copy_stream, c->cand_stream, c->stream};
     delete c;  // every buffer is released here (fa_ctx's members own them): before the streams go, as ever
     for (hipStream_t s : streams)
@@ -578,6 +582,8 @@ static bool bucket_range(const fa_ctx* c, uint32_t timeslot, uint32_t& lo, uint3
 #include "group_host.inc"
 #include "talkers_host.inc"
 #include "ports_host.inc"
+#include "raw_host.inc"
+#include "second_pass.inc"
 
 extern "C" int fa_stats(fa_ctx* c, fa_stats_t* out) {
     FA_ON_DEVICE(c);

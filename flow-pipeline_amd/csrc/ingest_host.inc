@@ -376,14 +376,14 @@ static int ingest_device_any(fa_ctx* c, const void* d_buf, size_t len, const voi
             used += bytes;
             i += m;
         }
-        // exact top talkers / bucketed ports: the second pass, once per call, behind everything the call queued (the offsets of the split above)
-        return c->talk || c->ports ? second_pass_records(c, d_buf, len, off, total) : FA_OK;
+        // exact top talkers / bucketed ports / flows_raw parts: the second pass, once per call, behind everything the call queued (the offsets of the split above)
+        return c->talk || c->ports || c->raw ? second_pass_records(c, d_buf, len, off, total) : FA_OK;
     }
     if (n == 0) return FA_OK;
     if (!d_buf || len >= (1ull << 32) || n > c->cfg.max_batch_records || ((uintptr_t)d_buf & 15) || ((uintptr_t)d_off & 3))
         return fail(c, FA_ERR_ARG, "fa_ingest_device: bad buffer (16-byte aligned, < 4 GiB, n <= max_batch_records)");
     const int rc = ingest_device_records(c, d_buf, len, len, d_off, n);
-    if (rc || !(c->talk || c->ports)) return rc;
+    if (rc || !(c->talk || c->ports || c->raw)) return rc;
     return second_pass_records(c, d_buf, len, (const uint32_t*)d_off, n);
 }
 

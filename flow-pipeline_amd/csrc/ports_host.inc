@@ -1,5 +1,5 @@
-// ports_host.inc - host side of the bucketed port tables (included by flowagg.hip: one translation unit; device side: ports.cuh),
-// and the ONE second pass an ingest call runs for every enabled fold (talkers_host.inc, this file).
+// ports_host.inc - host side of the bucketed port tables (included by flowagg.hip: one translation unit; device side: ports.cuh).
+// The ONE second pass an ingest call runs for every enabled fold is second_pass.inc.
 //
 // Capacity rule: talkers_host.inc's, per table.  The host keeps an upper bound used_ub of the occupied slots (a chunk of m
 // records adds at most m keys); before a launch, if (used_ub + m) * 2 > capacity, the stream is synchronised and the device's
@@ -195,34 +195,6 @@ static int port_fold_cols(fa_ctx* c, const PortCols& p, size_t n) {
         t->fold_launches++;
         t->used_ub[0] += m;
         t->used_ub[1] += m;
-        i += m;
-    }
-    return FA_OK;
-}
-
-// ---- the second pass of an ingest call (ingest_device_any) ---------------------------------------------------------------------
-// A ctx with an enabled fold - the talkers, the port tables, or both - decodes the call's n records again in chunks
-// (fa_decode_device's launch on the sub-range (d_buf, len, d_off + i, m)): each chunk is decoded ONCE and its columns handed to
-// every enabled fold, all on the ctx stream behind the launches of the ingest itself.  A chunk is as long as the smallest cap
-// of the enabled folds allows (and max_batch_records); a ctx with one fold runs what it ran when that fold had the pass alone.
-static int second_pass_records(fa_ctx* c, const void* d_buf, size_t len, const uint32_t* d_off, size_t n) {
-    for (size_t i = 0; i < n;) {
-        size_t m = std::min(n - i, (size_t)c->cfg.max_batch_records);
-        if (c->talk) m = std::min(m, talk_chunk_cap(c));
-        if (c->ports) m = std::min(m, port_chunk_cap(c));
-        fa_columns cols;
-        int rc = decode_device_records(c, d_buf, len, (size_t)((double)len * (double)m / (double)n), d_off + i, m, &cols);
-        if (rc) return rc;
-        if (c->talk) {
-            const TalkCols p{cols.src_addr, cols.dst_addr, cols.etype, cols.bytes, cols.sampling_rate, cols.status, cols.time_flow_start};
-            rc = talk_fold_cols(c, p, m);
-            if (rc) return rc;
-        }
-        if (c->ports) {
-            const PortCols p{cols.src_port, cols.dst_port, cols.bytes, cols.sampling_rate, cols.time_flow_start, cols.status};
-            rc = port_fold_cols(c, p, m);
-            if (rc) return rc;
-        }
         i += m;
     }
     return FA_OK;

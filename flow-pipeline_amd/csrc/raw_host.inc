@@ -1,0 +1,358 @@
+// raw_host.inc - host side of the flows_raw parts (included by flowagg.hip: one translation unit; device side and the part format:
+// raw.cuh).  A ctx with fa_raw_enable hands every decoded chunk of the second pass (second_pass.inc) to raw_build_cols, which
+// appends the chunk's parts - one Native block per Date, rows in stable t32 order - to ONE device image; fa_raw_take delivers
+// the image with one copy.
+//
+// Memory: the image holds header + 110 bytes per row that was built and not yet taken, and grows by doubling (at least to
+// what is needed; the old image is copied inside HBM).  Scratch: 24 bytes per record of the largest chunk plus hipcub's
+// temporary storage.  Both are kept until fa_raw_reset / fa_destroy.
+// One host synchronisation per chunk: the part list (a few entries) is read before the gather is launched, because the
+// image's layout depends on the rows per Date.
+
+struct RawState {
+    size_t chunk = (size_t)1 << 20;
+    DevBuf<uint8_t> img;   // the pending parts, back to back
+    size_t used = 0;       // bytes of img that hold pending parts
+    std::vector<fa_raw_part> pending;
+    DevBuf<> scratch;      // flags, positions, 2 x keys, 2 x indices, the part list, hipcub storage
+    PinnedBuf<uint8_t> h_list;  // the part list's first RAW_LIST_FIRST bytes on their way to the host
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // build start, order done, first gather launch, gather done
+    bool ev_pending = false;
+    uint64_t records_in = 0, records_bad = 0, rows_out = 0, parts_out = 0, bytes_out = 0, chunks = 0;
+    uint64_t order_ns = 0, gather_ns = 0, launches = 0;
+};
+static constexpr size_t RAW_LIST_FIRST = 4096;  // header + 255 entries: what one small copy brings
+
+static void raw_destroy(fa_ctx* c) {
+    RawState* t = c->raw;
+    if (!t) return;
+    if (getenv("FA_VERBOSE"))
+        fprintf(stderr, "[flowagg] raw parts: %llu records in %llu chunks, order %llu ns, gather %llu ns\n", (unsigned long long)t->records_in, (unsigned long long)t->chunks,
+                (unsigned long long)t->order_ns, (unsigned long long)t->gather_ns);
+    for (hipEvent_t e : t->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete t;
+    c->raw = nullptr;
+}
+
+#define RAW_ENTER(c, fn)                                                                                   \
+    FA_ON_DEVICE(c);                                                                                       \
+    if (!(c)) return FA_ERR_ARG;                                                                           \
+    if ((c)->sticky) return (c)->sticky;                                                                   \
+    if (!(c)->raw) return fail((c), FA_ERR_ARG, fn ": fa_raw_enable was not called on this ctx")
+
+// ---- host only: the part's size and the encoder the CPU tests and a consumer without a GPU sink use ---------------------------
+extern "C" size_t fa_raw_part_bytes(uint64_t rows) { return (size_t)raw_col_offset(RAW_COLS_H, rows, RAW_NCOLS); }
+
+extern "C" int fa_flow_rows_to_native(const fa_flow_row* rows, size_t n, uint8_t* out, size_t cap, size_t* bytes_out) {
+    if ((!rows && n) || !bytes_out) return FA_ERR_ARG;
+    for (size_t i = 0; i < n; i++) {  // one Date, status 0, ascending t32
+        const uint32_t t = (uint32_t)rows[i].time_received;
+        if (rows[i].status != 0) return FA_ERR_ARG;
+        if (i && (t < (uint32_t)rows[i - 1].time_received || t / 86400u != (uint32_t)rows[0].time_received / 86400u)) return FA_ERR_ARG;
+    }
+    const size_t need = fa_raw_part_bytes(n);
+    *bytes_out = need;
+    if (need > cap || !out) return FA_ERR_CAPACITY;
+    uint8_t* p = out;
+    auto put = [&](uint64_t v, int bytes) {
+        for (int i = 0; i < bytes; i++) *p++ = (uint8_t)(v >> (8 * i));
+    };
+    auto varuint = [&](uint64_t v) {
+        while (v >= 128) *p++ = (uint8_t)(v | 128), v >>= 7;
+        *p++ = (uint8_t)v;
+    };
+    varuint(RAW_NCOLS);
+    varuint(n);
+    for (uint32_t c = 0; c < RAW_NCOLS; c++) {
+        const RawColDef& d = RAW_COLS_H[c];
+        varuint(d.name_len);
+        memcpy(p, d.name, d.name_len), p += d.name_len;
+        varuint(d.type_len);
+        memcpy(p, d.type, d.type_len), p += d.type_len;
+        for (size_t i = 0; i < n; i++) {
+            const fa_flow_row& r = rows[i];
+            switch (c) {
+            case 0: put((uint32_t)r.time_received / 86400u, 2); break;
+            case 1: put((uint32_t)r.time_received, 4); break;
+            case 2: put((uint32_t)r.time_flow_start, 4); break;
+            case 3: put(r.sequence_num, 4); break;
+            case 4: put(r.sampling_rate, 8); break;
+            case 5: memcpy(p, r.sampler_address, 16), p += 16; break;
+            case 6: memcpy(p, r.src_addr, 16), p += 16; break;
+            case 7: memcpy(p, r.dst_addr, 16), p += 16; break;
+            case 8: put(r.src_as, 4); break;
+            case 9: put(r.dst_as, 4); break;
+            case 10: put(r.etype, 4); break;
+            case 11: put(r.proto, 4); break;
+            case 12: put(r.src_port, 4); break;
+            case 13: put(r.dst_port, 4); break;
+            case 14: put(r.bytes, 8); break;
+            default: put(r.packets, 8);
+            }
+        }
+    }
+    return FA_OK;
+}
+
+// ---- enable -------------------------------------------------------------------------------------------------------------------
+extern "C" int fa_raw_enable(fa_ctx* c, uint32_t chunk_records) {
+    FA_ON_DEVICE(c);
+    if (!c) return FA_ERR_ARG;
+    if (c->sticky) return c->sticky;
+    if (c->raw) return fail(c, FA_ERR_ARG, "fa_raw_enable: already enabled");
+    if (chunk_records > (1u << 24)) return fail(c, FA_ERR_ARG, "fa_raw_enable: chunk_records is 0 (default 2^20) or 1..2^24");
+    RawState* t = new RawState();
+    if (chunk_records) t->chunk = chunk_records;
+    c->raw = t;
+    bool ok = t->h_list.grow(RAW_LIST_FIRST);
+    for (int i = 0; i < 4 && ok; i++) ok = hipEventCreate(&t->ev[i]) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        raw_destroy(c);
+        return fail(c, FA_ERR_NOMEM, "fa_raw_enable: allocating the part list's staging failed");
+    }
+    return FA_OK;
+}
+
+static size_t raw_chunk_cap(const fa_ctx* c) { return c->raw->chunk; }
+
+// the gather of the last build has finished (the caller synchronised, or does so here): its time is added
+static void raw_read_events(RawState* t) {
+    if (!t->ev_pending) return;
+    float ms = 0;
+    if (hipEventSynchronize(t->ev[3]) == hipSuccess && hipEventElapsedTime(&ms, t->ev[2], t->ev[3]) == hipSuccess) t->gather_ns += (uint64_t)((double)ms * 1e6);
+    t->ev_pending = false;
+}
+
+// Room for `more` bytes behind the pending parts.  A larger image is allocated first and the pending bytes are copied inside
+// HBM: when the allocation fails nothing has changed.
+static int raw_reserve_image(fa_ctx* c, size_t more) {
+    RawState* t = c->raw;
+    const size_t need = t->used + more;
+    if (t->img.bytes() >= need) return FA_OK;
+    DevBuf<uint8_t> bigger;
+    if (!bigger.grow(std::max<size_t>(need, std::max<size_t>(2 * t->img.bytes(), (size_t)1 << 20)))) {
+        (void)hipGetLastError();
+        return fail(c, FA_ERR_NOMEM, "hipMalloc(raw part image) failed; the chunk's parts were not built");
+    }
+    if (t->used) HIPCHK(c, hipMemcpyAsync(bigger, t->img, t->used, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    t->img = std::move(bigger);
+    return FA_OK;
+}
+
+// One chunk of m <= raw_chunk_cap decoded records -> its parts appended to the image.
+static int raw_build_chunk(fa_ctx* c, const fa_columns& cols, size_t m) {
+    RawState* t = c->raw;
+    if (m == 0) return FA_OK;
+    raw_read_events(t);
+    // scratch: flags, positions (m + 1 words each), keys and indices in and out (m words each), the part list, hipcub storage
+    const uint32_t n = (uint32_t)m;
+    size_t tmp_scan = 0, tmp_sort = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n + 1), c->stream);
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 32, c->stream);
+    const size_t words = align256(((size_t)n + 1) * 4), tmp_bytes = align256(std::max(tmp_scan, tmp_sort));
+    const size_t list_bytes = align256(sizeof(RawPartsHeader) + (size_t)RAW_MAX_DATES * sizeof(RawPartEntry));
+    int rc = ensure_dev(c, t->scratch, 6 * words + list_bytes + tmp_bytes, "raw part scratch");
+    if (rc) return rc;
+    uint8_t* sb = (uint8_t*)t->scratch.get();
+    uint32_t *flag = (uint32_t*)sb, *pos = (uint32_t*)(sb + words), *key_in = (uint32_t*)(sb + 2 * words), *key = (uint32_t*)(sb + 3 * words);
+    uint32_t *idx_in = (uint32_t*)(sb + 4 * words), *idx = (uint32_t*)(sb + 5 * words);
+    RawPartsHeader* hdr = (RawPartsHeader*)(sb + 6 * words);
+    RawPartEntry* list = (RawPartEntry*)(hdr + 1);
+    void* tmp = sb + 6 * words + list_bytes;
+
+    // ---- order
+    const dim3 grid((n + 1 + 255) / 256), block(256);
+    (void)hipEventRecord(t->ev[0], c->stream);
+    HIPCHK(c, hipMemsetAsync(hdr, 0, sizeof(RawPartsHeader), c->stream));
+    hipLaunchKernelGGL(raw_flag_kernel, grid, block, 0, c->stream, cols.status, n, flag);
+    size_t tb = tmp_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum(tmp, tb, (const uint32_t*)flag, pos, (int)(n + 1), c->stream) != hipSuccess) return fail(c, FA_ERR_HIP, "scan failed");
+    hipLaunchKernelGGL(raw_key_kernel, grid, block, 0, c->stream, cols.status, cols.time_received, n, (const uint32_t*)pos, key_in, idx_in);
+    tb = tmp_bytes;
+    if (hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint32_t*)key_in, key, (const uint32_t*)idx_in, idx, (int)n, 0, 32, c->stream) != hipSuccess)
+        return fail(c, FA_ERR_HIP, "sort failed");
+    hipLaunchKernelGGL(raw_parts_kernel, grid, block, 0, c->stream, (const uint32_t*)key, (const uint32_t*)pos, n, hdr, list, RAW_MAX_DATES);
+    (void)hipEventRecord(t->ev[1], c->stream);
+    HIPCHK(c, hipGetLastError());
+    t->launches += 5;
+    // ---- the part list: one small copy
+    HIPCHK(c, hipMemcpyAsync(t->h_list, hdr, RAW_LIST_FIRST, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, t->ev[0], t->ev[1]) == hipSuccess) t->order_ns += (uint64_t)((double)ms * 1e6);
+    }
+    const RawPartsHeader h = *(const RawPartsHeader*)t->h_list.get();
+    if (h.good > n || h.nparts > RAW_MAX_DATES || (h.good != 0) != (h.nparts != 0)) return fail(c, FA_ERR_HIP, "internal: the raw part list is inconsistent");
+    std::vector<RawPartEntry> ent(h.nparts);
+    const size_t first = std::min<size_t>(h.nparts, (RAW_LIST_FIRST - sizeof(RawPartsHeader)) / sizeof(RawPartEntry));
+    if (first) memcpy(ent.data(), t->h_list.get() + sizeof(RawPartsHeader), first * sizeof(RawPartEntry));
+    if (h.nparts > first) HIPCHK(c, hipMemcpy(ent.data() + first, list + first, (h.nparts - first) * sizeof(RawPartEntry), hipMemcpyDeviceToHost));
+    std::sort(ent.begin(), ent.end(), [](const RawPartEntry& x, const RawPartEntry& y) { return x.start < y.start; });
+    // (the counters move only once the chunk's parts are certain to be built: rows_out + records_bad == records_in always holds)
+    auto count_chunk = [&] {
+        t->records_in += n;
+        t->records_bad += n - h.good;
+        t->chunks++;
+    };
+    if (!h.nparts) {
+        count_chunk();
+        return FA_OK;
+    }
+    // ---- the image's layout, then the gather: one launch per part
+    size_t bytes = 0;
+    for (size_t i = 0; i < ent.size(); i++) bytes += fa_raw_part_bytes((i + 1 < ent.size() ? ent[i + 1].start : h.good) - ent[i].start);
+    rc = raw_reserve_image(c, bytes);
+    if (rc) return rc;
+    count_chunk();
+    (void)hipEventRecord(t->ev[2], c->stream);  // (behind the part list's round trip and the image's growth: the gather launches alone)
+    for (size_t i = 0; i < ent.size(); i++) {
+        const uint32_t end = i + 1 < ent.size() ? ent[i + 1].start : h.good;
+        fa_raw_part p{};
+        p.date = ent[i].t_min / 86400u;
+        p.t_min = ent[i].t_min;
+        p.t_max = i + 1 < ent.size() ? ent[i + 1].prev_t_max : h.last_t_max;
+        p.rows = end - ent[i].start;
+        p.offset = t->used;
+        p.bytes = fa_raw_part_bytes(p.rows);
+        RawGatherArgs a{};
+        a.part = t->img + t->used;
+        a.key = key + ent[i].start;
+        a.idx = idx + ent[i].start;
+        const void* src[RAW_NCOLS] = {nullptr, nullptr, cols.time_flow_start, cols.sequence_num, cols.sampling_rate, cols.sampler_address, cols.src_addr, cols.dst_addr,
+                                      cols.src_as, cols.dst_as, cols.etype, cols.proto, cols.src_port, cols.dst_port, cols.bytes, cols.packets};
+        memcpy(a.src, src, sizeof src);
+        a.rows = (uint32_t)p.rows;
+        a.date = p.date;
+        uint64_t tiles = 0;
+        for (uint32_t col = 0; col < RAW_NCOLS; col++)
+            tiles += raw_col_tiles((uint64_t)(uintptr_t)(a.part + raw_col_offset(RAW_COLS_H, p.rows, col) + raw_col_header_len(RAW_COLS_H[col])), p.rows * RAW_COLS_H[col].width);
+        hipLaunchKernelGGL(raw_gather_kernel, dim3((unsigned)tiles), dim3(RAW_BLOCK), 0, c->stream, a);
+        HIPCHK(c, hipGetLastError());
+        t->launches++;
+        t->used += p.bytes;
+        t->pending.push_back(p);
+        t->rows_out += p.rows;
+        t->parts_out++;
+        t->bytes_out += p.bytes;
+    }
+    (void)hipEventRecord(t->ev[3], c->stream);
+    t->ev_pending = true;
+    return FA_OK;
+}
+
+static fa_columns raw_cols_at(const fa_columns& s, size_t i) {
+    fa_columns o = s;
+    o.time_received += i, o.time_flow_start += i, o.sampling_rate += i, o.bytes += i, o.packets += i;
+    o.sequence_num += i, o.src_as += i, o.dst_as += i, o.etype += i, o.proto += i, o.src_port += i, o.dst_port += i;
+    o.sampler_address += 16 * i, o.src_addr += 16 * i, o.dst_addr += 16 * i;
+    o.status += i;
+    return o;
+}
+
+// n decoded records -> parts, a chunk at a time
+static int raw_build_cols(fa_ctx* c, const fa_columns& cols, size_t n) {
+    for (size_t i = 0; i < n;) {
+        const size_t m = std::min(n - i, raw_chunk_cap(c));
+        int rc = raw_build_chunk(c, raw_cols_at(cols, i), m);
+        if (rc) return rc;
+        i += m;
+    }
+    return FA_OK;
+}
+
+extern "C" int fa_raw_build_columns_device(fa_ctx* c, const fa_columns* cols, size_t n) {
+    RAW_ENTER(c, "fa_raw_build_columns_device");
+    if (n == 0) return FA_OK;
+    if (!cols) return fail(c, FA_ERR_ARG, "fa_raw_build_columns_device: null argument");
+    const void* p8[] = {cols->time_received, cols->time_flow_start, cols->sampling_rate, cols->bytes, cols->packets};
+    const void* p4[] = {cols->sequence_num, cols->src_as, cols->dst_as, cols->etype, cols->proto, cols->src_port, cols->dst_port};
+    const void* p16[] = {cols->sampler_address, cols->src_addr, cols->dst_addr};
+    bool ok = cols->status != nullptr;
+    for (const void* p : p8) ok = ok && p && !((uintptr_t)p & 7);
+    for (const void* p : p4) ok = ok && p && !((uintptr_t)p & 3);
+    for (const void* p : p16) ok = ok && p && !((uintptr_t)p & 15);
+    if (!ok) return fail(c, FA_ERR_ARG, "fa_raw_build_columns_device: all 15 columns and status are needed, each naturally aligned (8 / 4 / 16 / 1 bytes)");
+    const int rc = raw_build_cols(c, *cols, n);
+    // the gather launches of the last chunk still read the caller's columns: they are done before the call returns
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    HIPCHK(c, e);
+    return FA_OK;
+}
+
+// ---- take, reset, statistics -----------------------------------------------------------------------------------------------------
+static int raw_take_check(fa_ctx* c, size_t cap, bool have_out, size_t* bytes_out, fa_raw_part* parts, size_t parts_cap, size_t* n_parts) {
+    RawState* t = c->raw;
+    *bytes_out = t->used;
+    *n_parts = t->pending.size();
+    if (t->used > cap || (t->used && !have_out) || t->pending.size() > parts_cap || (!parts && !t->pending.empty()))
+        return fail(c, FA_ERR_CAPACITY, "fa_raw_take: a buffer is too small (bytes and parts needed are returned); nothing was taken");
+    return FA_OK;
+}
+static void raw_clear(RawState* t, fa_raw_part* parts) {
+    if (parts && !t->pending.empty()) memcpy(parts, t->pending.data(), t->pending.size() * sizeof(fa_raw_part));
+    t->pending.clear();
+    t->used = 0;
+}
+
+extern "C" int fa_raw_take(fa_ctx* c, uint8_t* out, size_t cap, size_t* bytes_out, fa_raw_part* parts, size_t parts_cap, size_t* n_parts) {
+    RAW_ENTER(c, "fa_raw_take");
+    if (!bytes_out || !n_parts) return fail(c, FA_ERR_ARG, "fa_raw_take: null argument");
+    RawState* t = c->raw;
+    int rc = raw_take_check(c, cap, out != nullptr, bytes_out, parts, parts_cap, n_parts);
+    if (rc) return rc;
+    if (t->used) HIPCHK(c, hipMemcpyAsync(out, t->img, t->used, hipMemcpyDeviceToHost, c->stream));  // (page-locked `out`: one copy-engine transfer)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    raw_read_events(t);
+    raw_clear(t, parts);
+    return FA_OK;
+}
+
+extern "C" int fa_raw_take_device(fa_ctx* c, const void** d_bytes, size_t* bytes_out, fa_raw_part* parts, size_t parts_cap, size_t* n_parts) {
+    RAW_ENTER(c, "fa_raw_take_device");
+    if (!d_bytes || !bytes_out || !n_parts) return fail(c, FA_ERR_ARG, "fa_raw_take_device: null argument");
+    RawState* t = c->raw;
+    *d_bytes = nullptr;
+    int rc = raw_take_check(c, t->used, true, bytes_out, parts, parts_cap, n_parts);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    raw_read_events(t);
+    *d_bytes = t->used ? t->img.get() : nullptr;
+    raw_clear(t, parts);
+    return FA_OK;
+}
+
+// Drops the pending parts and releases the image and the scratch; the counters of fa_raw_stats go on counting.
+extern "C" int fa_raw_reset(fa_ctx* c) {
+    RAW_ENTER(c, "fa_raw_reset");
+    RawState* t = c->raw;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    raw_read_events(t);
+    raw_clear(t, nullptr);
+    t->img.reset();
+    t->scratch.reset();
+    return FA_OK;
+}
+
+extern "C" int fa_raw_stats(fa_ctx* c, fa_raw_stats_t* out) {
+    RAW_ENTER(c, "fa_raw_stats");
+    if (!out) return fail(c, FA_ERR_ARG, "fa_raw_stats: null argument");
+    RawState* t = c->raw;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    raw_read_events(t);
+    out->records_in = t->records_in;
+    out->records_bad = t->records_bad;
+    out->rows_out = t->rows_out;
+    out->parts_out = t->parts_out;
+    out->bytes_out = t->bytes_out;
+    out->chunks = t->chunks;
+    out->pending_parts = t->pending.size();
+    out->pending_bytes = t->used;
+    out->build_ns_total = t->order_ns + t->gather_ns;
+    out->build_launches = t->launches;
+    return FA_OK;
+}

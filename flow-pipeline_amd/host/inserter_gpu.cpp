@@ -34,6 +34,9 @@
 //   - -topk.mode exact|candidates (fa_config.topk_mode): candidates (64 k slots per set) is the default with more than one claimed
 //     partition - the exact mode's sets hold EVERY address (2 x 32 B x 2^-gpu.keyset.log2 per partition);
 //   - a key set without a sink (-key.sets includes 8, no -out.app) is closed all the same: its windows are dropped, not kept.
+//   - -out.raw.native=PATH: every ctx builds flows_raw parts (fa_raw_enable: per chunk and Date one sorted ClickHouse Native block,
+//     create.sh:36-68); after every flush the partition's parts are taken and appended to PATH under the writer's lock, so the
+//     file is a valid concatenation of blocks for `INSERT INTO flows_raw FORMAT Native`.
 #include <atomic>
 #include <chrono>
 #include <cstdarg>
@@ -73,6 +76,7 @@ struct Flags {
     long KeySets = FA_KEYS_AS_PAIR;
     std::string InputFiles, InputFormat = "framed";
     std::string OutRowBinary, OutTsv, OffsetsOut, MetricsDump;
+    std::string OutRawNative;  // flows_raw parts of every flush, appended: ClickHouse Native blocks (fa_raw_take)
     std::string OutApp, OutTopk, GpuTransport = "peer";  // raw fa_row_app records / "src|dst <hex key> <weight>" lines; peer | rccl
     long TopkK = 100;
     long TableLog2 = 0, KeysetLog2 = 0, WideLog2 = 0;  // fa_config capacities (0 = the library's defaults)
@@ -151,6 +155,7 @@ static Flags parse_flags(int argc, char** argv) {
         {"postgres.host", &f.PostgresHost}, {"postgres.dbname", &f.PostgresDbName}, {"input.files", &f.InputFiles},
         {"input.format", &f.InputFormat}, {"out.rowbinary", &f.OutRowBinary}, {"out.tsv", &f.OutTsv},
         {"offsets.out", &f.OffsetsOut}, {"metrics.dump", &f.MetricsDump}, {"out.app", &f.OutApp}, {"out.topk", &f.OutTopk},
+        {"out.raw.native", &f.OutRawNative},
         {"gpu.transport", &f.GpuTransport}, {"topk.mode", &f.TopkMode}, {"phases.out", &f.PhasesOut}};
     std::map<std::string, long*> ints = {
         {"flush.count", &f.FlushCount}, {"postgres.port", &f.PostgresPort}, {"gpu.devices", &f.GpuDevices},
@@ -299,6 +304,7 @@ struct ConsumerGroupHandler {
 // ---- the sink -----------------------------------------------------------------------------------------------
 static std::atomic<uint64_t> Inserts{0};  // insert_count (inserter.go:44-49)
 static std::atomic<uint64_t> RowsOut{0}, Flushes{0};
+static std::atomic<uint64_t> RawRowsOut{0};  // flows_raw rows written by -out.raw.native
 
 class RowWriter {  // flows_5m rows of closed windows: RowBinary for clickhouse-client / HTTP, TSV for humans
 public:
@@ -307,6 +313,16 @@ public:
         if (!f.OutTsv.empty() && !(tsv_ = fopen(f.OutTsv.c_str(), "w"))) fatal("cannot open %s", f.OutTsv.c_str());
         if (!f.OutApp.empty() && !(app_ = fopen(f.OutApp.c_str(), "wb"))) fatal("cannot open %s", f.OutApp.c_str());
         if (!f.OutTopk.empty() && !(topk_ = fopen(f.OutTopk.c_str(), "w"))) fatal("cannot open %s", f.OutTopk.c_str());
+        if (!f.OutRawNative.empty() && !(raw_ = fopen(f.OutRawNative.c_str(), "wb"))) fatal("cannot open %s", f.OutRawNative.c_str());
+    }
+    bool wantsRaw() const { return raw_ != nullptr; }
+    // a partition's flows_raw parts: whole Native blocks, written under the lock - the file is a concatenation of blocks whatever
+    // the number of partition threads
+    void writeRaw(const uint8_t* bytes, size_t n, uint64_t rows) {
+        if (!n || !raw_) return;
+        std::lock_guard<std::mutex> g(mu_);
+        if (fwrite(bytes, 1, n, raw_) != n) fatal("short write on the raw Native sink");
+        RawRowsOut += rows;
     }
     bool wantsApp() const { return app_ != nullptr; }
     bool wantsTopk() const { return topk_ != nullptr; }
@@ -347,7 +363,8 @@ public:
         if (tsv_) fclose(tsv_);
         if (app_) fclose(app_);
         if (topk_) fclose(topk_);
-        rb_ = tsv_ = app_ = topk_ = nullptr;
+        if (raw_) fclose(raw_);
+        rb_ = tsv_ = app_ = topk_ = raw_ = nullptr;
     }
 
 private:
@@ -357,6 +374,7 @@ private:
     FILE* tsv_ = nullptr;
     FILE* app_ = nullptr;
     FILE* topk_ = nullptr;
+    FILE* raw_ = nullptr;
 };
 
 // one aggregation context per claimed partition (fa_ctx is not thread-safe; distinct ctxs are independent)
@@ -385,6 +403,8 @@ struct PartitionState {
     std::unique_ptr<uint64_t[]> offsets;
     size_t offsets_cap = 0;
     size_t pending = 0;             // messages in the batch
+    std::vector<uint8_t> raw_bytes;  // -out.raw.native: the flush's parts on their way to the file
+    std::vector<fa_raw_part> raw_parts;
     ConsumerMessage last{};         // the newest of them: offsets of one partition are monotone, marking it commits the batch
     Phases ph;
     size_t bytes() const { return run ? run_len : buf.size(); }
@@ -479,6 +499,7 @@ public:
                     const size_t bytes = (size_t)f_.BatchBytes + (64u << 10), recs = std::min<size_t>(bytes / 48, (size_t)1 << 24);
                     if ((rc = fa_reserve_ingest(p->ctx, bytes, recs)) != 0) fatal("fa_reserve_ingest: %d %s", rc, fa_last_error(p->ctx));
                 }
+                if (out_.wantsRaw() && (rc = fa_raw_enable(p->ctx, 0)) != 0) fatal("fa_raw_enable: %d %s", rc, fa_last_error(p->ctx));
                 ctxs.push_back(p->ctx);
             }
             if (f_.BatchBytes > 0) {  // the batch's offsets: allocated and touched here, not page by page inside the consume loop
@@ -576,6 +597,7 @@ public:
             // fa_ingest copies into library-owned pinned memory before returning
             int rc = fa_ingest(p.ctx, data, len, p.offsets.get(), n);
             if (rc != 0) fatal("fa_ingest: %d %s", rc, fa_last_error(p.ctx));  // sink error is fatal, inserter.go:102-105
+            if (out_.wantsRaw()) takeRaw(p);
             t0 = now_s();
             p.ph.ingest += t0 - t1;
         }
@@ -588,6 +610,22 @@ public:
         p.ph.bytes += len;
         p.reset();
         p.ph.mark += now_s() - t0;
+    }
+
+    // -out.raw.native: the parts the flush built (fa_raw_enable: per chunk and Date one sorted Native block) leave HBM with one
+    // copy and are appended to the file; a too small buffer is told its size and asked again
+    void takeRaw(PartitionState& p) {
+        size_t bytes = 0, nparts = 0;
+        int rc = fa_raw_take(p.ctx, p.raw_bytes.data(), p.raw_bytes.size(), &bytes, p.raw_parts.data(), p.raw_parts.size(), &nparts);
+        if (rc == FA_ERR_CAPACITY) {
+            if (bytes > p.raw_bytes.size()) p.raw_bytes.resize(bytes + bytes / 4);
+            if (nparts > p.raw_parts.size()) p.raw_parts.resize(nparts + 8);
+            rc = fa_raw_take(p.ctx, p.raw_bytes.data(), p.raw_bytes.size(), &bytes, p.raw_parts.data(), p.raw_parts.size(), &nparts);
+        }
+        if (rc != 0) fatal("fa_raw_take: %d %s", rc, fa_last_error(p.ctx));
+        uint64_t rows = 0;
+        for (size_t i = 0; i < nparts; i++) rows += p.raw_parts[i].rows;
+        out_.writeRaw(p.raw_bytes.data(), bytes, rows);
     }
 
     // emits the finished windows of the WHOLE topic to the bulk-load sinks: flows_5m rows (create.sh:70-90) merged over the
@@ -818,6 +856,7 @@ int main(int argc, char** argv) {
                 (unsigned long long)Inserts.load());
         fprintf(fp, "# TYPE flowagg_flushes counter\nflowagg_flushes %llu\n", (unsigned long long)Flushes.load());
         fprintf(fp, "# TYPE flowagg_rows_out counter\nflowagg_rows_out %llu\n", (unsigned long long)RowsOut.load());
+        fprintf(fp, "# TYPE flowagg_raw_rows_out counter\nflowagg_raw_rows_out %llu\n", (unsigned long long)RawRowsOut.load());
         fprintf(fp, "# TYPE flowagg_records_bad counter\nflowagg_records_bad %llu\n", (unsigned long long)s.bad());
         fclose(fp);
     }

@@ -1,4 +1,5 @@
-"""Columnar spill of the decoded projection: `flows_raw`-equivalent Parquet files.
+"""Columnar spill of the decoded projection: `flows_raw`-equivalent Parquet files, and the reader / plain encoder of the
+ClickHouse Native blocks the library builds on the device (``read_native``, ``native_from_rows``; numpy only).
 
 The dashboards of the reference scan ``flows_raw`` (``viz-ch.json:74-604``); with the
 ClickHouse Kafka-engine table and its materialized views gone, the raw rows
@@ -14,7 +15,7 @@ one Parquet file with the column list and types of ``flows_raw`` (``create.sh:36
 time columns are applied here as ClickHouse applies them in ``flows_raw_view``; malformed records
 (status != 0) are dropped (``inserter/inserter.go:125-126``).  ClickHouse loads such a file with
 ``INSERT INTO flows_raw FORMAT Parquet``; offline checks read it with pyarrow / pandas.
-Host-side Python only (pyarrow): nothing here is on the hot path.
+Host-side Python only (pyarrow for the Parquet half): nothing here is on the hot path.
 """
 from __future__ import annotations
 
@@ -65,3 +66,105 @@ def spill_parquet(rows: np.ndarray, path: str, compression="zstd") -> int:
     table = to_arrow(rows)
     pq.write_table(table, path, compression=compression)
     return table.num_rows
+
+
+# ---- ClickHouse Native blocks of flows_raw (numpy only) ----------------------------------------------------------------------
+# One part = one Native block without BlockInfo: varuint(16) varuint(rows), then per column of COLUMNS
+# varuint(len(name)) name varuint(len(type)) type and `rows` little-endian values (format restated from the ClickHouse
+# documentation; no server was available to load it into).  The library builds such blocks on the device (fa_raw_*); this
+# is the reader for offline checks and the plain encoder behind the CPU tests.
+NATIVE_TYPES = {"Date": ("Date", "<u2"), "TimeReceived": ("DateTime", "<u4"), "TimeFlowStart": ("DateTime", "<u4"),
+                "SequenceNum": ("UInt32", "<u4"), "SamplingRate": ("UInt64", "<u8"), "SamplerAddress": ("FixedString(16)", "u1"),
+                "SrcAddr": ("FixedString(16)", "u1"), "DstAddr": ("FixedString(16)", "u1"), "SrcAS": ("UInt32", "<u4"),
+                "DstAS": ("UInt32", "<u4"), "EType": ("UInt32", "<u4"), "Proto": ("UInt32", "<u4"), "SrcPort": ("UInt32", "<u4"),
+                "DstPort": ("UInt32", "<u4"), "Bytes": ("UInt64", "<u8"), "Packets": ("UInt64", "<u8")}
+_ROW_FIELDS = {"SequenceNum": "sequence_num", "SamplingRate": "sampling_rate", "SamplerAddress": "sampler_address", "SrcAddr": "src_addr",
+               "DstAddr": "dst_addr", "SrcAS": "src_as", "DstAS": "dst_as", "EType": "etype", "Proto": "proto", "SrcPort": "src_port",
+               "DstPort": "dst_port", "Bytes": "bytes", "Packets": "packets"}
+
+
+def _varuint(v: int) -> bytes:
+    out = bytearray()
+    while v >= 128:
+        out.append((v & 127) | 128)
+        v >>= 7
+    out.append(v)
+    return bytes(out)
+
+
+def _read_varuint(b: np.ndarray, p: int):
+    v = shift = 0
+    while True:
+        if p >= len(b) or shift > 63:
+            raise ValueError("truncated or overlong varuint at byte %d" % p)
+        x = int(b[p])
+        p += 1
+        v |= (x & 127) << shift
+        shift += 7
+        if x < 128:
+            return v, p
+
+
+def read_native(data) -> list:
+    """A concatenation of flows_raw Native blocks -> one {column: array} per block, in order (FixedString(16) columns as
+    uint8[rows, 16]).  Anything that is not a whole number of blocks with the 16 columns and types of flows_raw - a trailing
+    byte included - raises ValueError."""
+    b = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+    blocks, p = [], 0
+    while p < len(b):
+        ncols, p = _read_varuint(b, p)
+        rows, p = _read_varuint(b, p)
+        if ncols != len(COLUMNS):
+            raise ValueError("a flows_raw block has %d columns, this one %d" % (len(COLUMNS), ncols))
+        block = {}
+        for want in COLUMNS:
+            got = []
+            for _ in range(2):
+                n, p = _read_varuint(b, p)
+                if p + n > len(b):
+                    raise ValueError("truncated column header")
+                got.append(bytes(b[p:p + n]).decode("ascii", "replace"))
+                p += n
+            ctype, dt = NATIVE_TYPES[want]
+            if got != [want, ctype]:
+                raise ValueError("column %s %s where %s %s is expected" % (got[0], got[1], want, ctype))
+            width = 16 if dt == "u1" else np.dtype(dt).itemsize
+            if p + rows * width > len(b):
+                raise ValueError("truncated column %s" % want)
+            col = b[p:p + rows * width]
+            block[want] = col.reshape(rows, 16).copy() if dt == "u1" else col.copy().view(dt)
+            p += rows * width
+        blocks.append(block)
+    return blocks
+
+
+def native_from_rows(rows: np.ndarray) -> bytes:
+    """Decoded rows (the fields of FLOW_ROW_DTYPE; ``status`` optional) -> flows_raw Native blocks as the library builds them
+    for ONE chunk: malformed rows dropped, the rest in stable order of the 32-bit TimeReceived, one block per Date in ascending
+    Date, no block without rows."""
+    if "status" in rows.dtype.names:
+        rows = rows[rows["status"] == 0]
+    t32 = (rows["time_received"] & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    order = np.argsort(t32, kind="stable")
+    rows, t32 = rows[order], t32[order]
+    date = t32 // np.uint32(86400)
+    cuts = [0] + [int(i) for i in np.nonzero(date[1:] != date[:-1])[0] + 1] + [len(rows)]
+    out = bytearray()
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        if hi == lo:
+            continue
+        r = rows[lo:hi]
+        out += _varuint(len(COLUMNS)) + _varuint(hi - lo)
+        for name in COLUMNS:
+            ctype, dt = NATIVE_TYPES[name]
+            out += _varuint(len(name)) + name.encode() + _varuint(len(ctype)) + ctype.encode()
+            if name == "Date":
+                col = date[lo:hi].astype("<u2")
+            elif name == "TimeReceived":
+                col = t32[lo:hi].astype("<u4")
+            elif name == "TimeFlowStart":
+                col = (r["time_flow_start"] & np.uint64(0xFFFFFFFF)).astype("<u4")
+            else:
+                col = np.ascontiguousarray(r[_ROW_FIELDS[name]]).astype(dt, copy=False)
+            out += np.ascontiguousarray(col).tobytes()
+    return bytes(out)

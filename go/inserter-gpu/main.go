@@ -94,6 +94,7 @@ var (
 	OutRowBin   = flag.String("out.rowbinary", "", "Append closed flows_5m rows to this file as ClickHouse RowBinary")
 	MarkAfter   = flag.Bool("mark.after.close", true, "Commit a batch's offsets only after every window it touched has been emitted")
 	GpuTransport = flag.String("gpu.transport", "peer", "Window-close exchange between the GPUs: peer (hipMemcpyPeer over xGMI) or rccl (sketches by ncclAllReduce)")
+	OutRawNative = flag.String("out.raw.native", "", "Append every flush's flows_raw parts to this file as ClickHouse Native blocks (one sorted block per chunk and Date)")
 	OutTopk      = flag.String("out.topk", "", "At the end of a session write the top -topk.k SrcAddr / DstAddr of the merged Count-Min sketches here (key.sets 2 / 4)")
 	TopkK        = flag.Int("topk.k", 100, "Rows of -out.topk per sketch")
 	TableLog2    = flag.Int("gpu.table.log2", 0, "log2 slots of a context's flows_5m table (0 = library default)")
@@ -116,6 +117,9 @@ type partitionState struct {
 	// partition are monotone and MarkMessage commits "everything up to here", so a batch is one message (its
 	// last) plus the timeslots that were open right after it was ingested.
 	unmarked []batchMark
+	// -out.raw.native: the flush's parts on their way to the file
+	rawBytes []byte
+	rawParts []C.fa_raw_part
 }
 
 type batchMark struct {
@@ -132,6 +136,7 @@ type state struct {
 	group   *C.fa_group
 	closeMu sync.RWMutex
 	rows5m  []C.fa_row5m // row buffer of the window close (under closeMu): kept between closes
+	rawMu   sync.Mutex   // -out.raw.native: a flush's parts are appended whole, whatever the number of partition goroutines
 }
 
 func (s *state) metricsHTTP() {
@@ -179,7 +184,43 @@ func newPartition(partition int32, claims int) *partitionState {
 			log.Fatalf("fa_reserve_ingest: %d %s", int(rc), C.GoString(C.fa_last_error(ctx)))
 		}
 	}
+	if *OutRawNative != "" {
+		if rc := C.fa_raw_enable(ctx, 0); rc != 0 {
+			log.Fatalf("fa_raw_enable: %d %s", int(rc), C.GoString(C.fa_last_error(ctx)))
+		}
+	}
 	return &partitionState{ctx: ctx, offsets: []uint64{0}}
+}
+
+// takeRaw: the parts the flush built (fa_raw_enable) leave HBM with one copy; a too small buffer is told its size and asked
+// again.  Errors are RETURNED (the caller holds closeMu for reading, see openTimeslots).
+func (p *partitionState) takeRaw() ([]byte, error) {
+	var nb, np C.size_t
+	take := func() C.int {
+		var b *C.uint8_t
+		var q *C.fa_raw_part
+		if len(p.rawBytes) > 0 {
+			b = (*C.uint8_t)(unsafe.Pointer(&p.rawBytes[0]))
+		}
+		if len(p.rawParts) > 0 {
+			q = &p.rawParts[0]
+		}
+		return C.fa_raw_take(p.ctx, b, C.size_t(len(p.rawBytes)), &nb, q, C.size_t(len(p.rawParts)), &np)
+	}
+	rc := take()
+	if rc == C.FA_ERR_CAPACITY {
+		if int(nb) > len(p.rawBytes) {
+			p.rawBytes = make([]byte, int(nb)+int(nb)/4)
+		}
+		if int(np) > len(p.rawParts) {
+			p.rawParts = make([]C.fa_raw_part, int(np)+8)
+		}
+		rc = take()
+	}
+	if rc != 0 {
+		return nil, fmt.Errorf("fa_raw_take: %d %s", int(rc), C.GoString(C.fa_last_error(p.ctx)))
+	}
+	return p.rawBytes[:int(nb)], nil
 }
 
 // flush = inserter.go:90-111 with the per-row db.Exec loop replaced by one fa_ingest.
@@ -198,12 +239,21 @@ func (p *partitionState) flush(s *state, session sarama.ConsumerGroupSession) {
 	if rc == 0 && *MarkAfter {
 		open, openErr = p.openTimeslots() // the batch's records can only sit in timeslots that are open now
 	}
+	var raw []byte
+	if rc == 0 && openErr == nil && *OutRawNative != "" {
+		raw, openErr = p.takeRaw()
+	}
 	s.closeMu.RUnlock() // (released before ANY fatal error: sinkFatal's last-resort close wants the write lock)
 	if rc != 0 {
 		sinkFatal("fa_ingest: %d %s", int(rc), C.GoString(C.fa_last_error(p.ctx)))
 	}
 	if openErr != nil {
 		sinkFatal("%v", openErr)
+	}
+	if len(raw) > 0 {
+		s.rawMu.Lock()
+		appendFile(*OutRawNative, raw)
+		s.rawMu.Unlock()
 	}
 	Inserts.Add(float64(n))
 	if *MarkAfter {

@@ -531,6 +531,67 @@ int fa_ports_drop_before(fa_ctx*, uint32_t t);
 int fa_ports_reset(fa_ctx*);
 int fa_ports_stats(fa_ctx*, fa_ports_stats_t* out);
 
+/* ---- ABI 8, addition: flows_raw parts built on the device (sorted Native blocks per Date) ---- */
+/* flows_raw (create.sh:36-68) is a MergeTree PARTITION BY Date ORDER BY TimeReceived filled by
+ * "SELECT toDate(TimeReceived) AS Date, * FROM flows": one inserted block becomes one part per Date, sorted by the narrowed
+ * TimeReceived.  A ctx with fa_raw_enable builds exactly that from the decoded columns in HBM.  One PART is one ClickHouse
+ * Native block without BlockInfo:
+ *   varuint(16) varuint(rows), then per column in the order of create.sh:38-59
+ *   varuint(len(name)) name varuint(len(type)) type, rows little-endian values:
+ *   Date Date (2 B, t32 / 86400) | TimeReceived, TimeFlowStart DateTime (4 B: the low 32 bits of the UInt64) | SequenceNum UInt32 |
+ *   SamplingRate UInt64 | SamplerAddress, SrcAddr, DstAddr FixedString(16) | SrcAS, DstAS, EType, Proto, SrcPort, DstPort UInt32 |
+ *   Bytes, Packets UInt64 - 110 payload bytes per row.
+ * `INSERT INTO flows_raw FORMAT Native` takes any concatenation of such blocks.  The format is restated from the ClickHouse
+ * documentation: no server was available to load it into (the caveat of fa_rows_to_rowbinary).
+ * Rows: records with status != 0 are dropped (inserter.go:125-126); inside a part the rows stand in STABLE ascending order of
+ * t32 = (uint32_t)TimeReceived (whether MergeTree's own block sort is stable is unverified; stable is deterministic); a part holds
+ * one Date; the parts of one chunk come out in ascending Date; a part without rows is never emitted.  Outside the oracle's time
+ * domain (TimeReceived >= 2^32) the narrowing above is applied; parity with ClickHouse there is unverified.
+ * Opt-in per ctx and additive: no key_sets bit, no change to any other call's result.  On an enabled ctx the second pass of
+ * every fa_ingest / fa_ingest_device (the pass of fa_talkers_enable / fa_ports_enable_buckets: each chunk decoded once for
+ * every enabled fold, the consequences listed there) also builds the chunk's parts: a chunk is at most chunk_records records
+ * (and the other folds' caps), so one ingest call gives parts per (chunk, Date), in build order.  The builder waits for the
+ * stream once per chunk (the image's layout depends on the rows per Date).
+ * Memory: pending parts accumulate in ONE device image until they are taken - header + 110 bytes per untaken row (at most
+ * twice that while the image grows), plus 24 bytes per record of the largest chunk of scratch; kept until fa_raw_reset.
+ * A failed allocation is FA_ERR_NOMEM: the chunk's parts are not built, the parts built before stay pending, the ctx stays usable.
+ * There is no group or dist door: parts of different partitions are independent parts of one table and need no merge.
+ * Every call below except fa_raw_enable returns FA_ERR_ARG (text in fa_last_error) on a ctx that is not enabled. */
+typedef struct {
+    uint32_t date, t_min, t_max, _pad; /* the part's Date; smallest and largest t32 in it */
+    uint64_t rows, offset, bytes;      /* offset / bytes: where the part lies in the bytes returned by the take */
+} fa_raw_part;
+typedef struct {
+    uint64_t records_in, records_bad;  /* records handed to the builder; of them status != 0, dropped */
+    uint64_t rows_out, parts_out, bytes_out; /* built so far (rows_out + records_bad == records_in) */
+    uint64_t chunks;                   /* non-empty chunks built */
+    uint64_t pending_parts, pending_bytes; /* built and not yet taken */
+    uint64_t build_ns_total;           /* device time of the order step and of the gather launches, hipEvent (the part list's round
+                                          trip to the host and a growth of the image lie between the two and are not counted) */
+    uint64_t build_launches;           /* launches those steps queued (5 per chunk + 1 per part) */
+} fa_raw_stats_t;
+/* Host only, no ctx: bytes of a part of `rows` rows (header + 110 * rows). */
+size_t fa_raw_part_bytes(uint64_t rows);
+/* Host only, no ctx, the twin of fa_rows_to_rowbinary: n rows of ONE Date with status 0 in ascending t32 -> one part
+ * (FA_ERR_ARG otherwise).  FA_ERR_CAPACITY (and the size in *bytes_out) when cap is too small. */
+int fa_flow_rows_to_native(const fa_flow_row* rows, size_t n, uint8_t* out, size_t cap, size_t* bytes_out);
+/* chunk_records: 0 = default (2^20), at most 2^24.  A second call is FA_ERR_ARG. */
+int fa_raw_enable(fa_ctx*, uint32_t chunk_records);
+/* The door for columns already in HBM: n records of `cols` - DEVICE pointers, all 15 columns and status, each naturally aligned
+ * (8 / 4 / 16 / 1 bytes; FA_ERR_ARG otherwise) - become parts, chunk_records at a time.  n == 0 and chunks without a good
+ * record produce no part and return FA_OK.  Synchronous (unlike the talkers' and the ports' doors): the ctx stream has drained when
+ * the call returns, so the columns are not referenced after it and may be freed or overwritten at once. */
+int fa_raw_build_columns_device(fa_ctx*, const fa_columns* cols, size_t n);
+/* Every pending part, in build order, back to back in `out` (one copy; page-locked `out`: one copy-engine transfer), their
+ * descriptions in `parts`; the pending parts are cleared.  If either buffer is too small: FA_ERR_CAPACITY, *bytes_out and
+ * *n_parts = what is needed, nothing is consumed. */
+int fa_raw_take(fa_ctx*, uint8_t* out, size_t cap, size_t* bytes_out, fa_raw_part* parts, size_t parts_cap, size_t* n_parts);
+/* The same, the bytes left in HBM (*d_bytes: DEVICE pointer, owned by the ctx, valid until its next ingest / raw call). */
+int fa_raw_take_device(fa_ctx*, const void** d_bytes, size_t* bytes_out, fa_raw_part* parts, size_t parts_cap, size_t* n_parts);
+/* Drops the pending parts and releases the image and the scratch; the counters of fa_raw_stats go on counting. */
+int fa_raw_reset(fa_ctx*);
+int fa_raw_stats(fa_ctx*, fa_raw_stats_t* out);
+
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
  *   if(EType = 0x800, IPv4NumToString(reinterpretAsUInt32(substring(reverse(Addr), 13, 4))), IPv6NumToString(Addr))
