@@ -104,6 +104,15 @@ class RawStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RawLz4Stats(C.Structure):
+    """fa_raw_lz4_stats_t: what the ctx's LZ4 compressions (raw_take_lz4, lz4_frame_device) have done so far."""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "frames", "blocks", "stored_blocks", "bytes_in", "bytes_out", "compress_launches", "device_ns", "block_ns", "pack_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class MockParams(C.Structure):
     _fields_ = [
         ("mode", C.c_uint32), ("framed", C.c_uint32), ("seed", C.c_uint64),
@@ -179,6 +188,7 @@ EXPORTS = [
     "fa_ports_drop_before", "fa_ports_reset", "fa_ports_stats", "fa_group_top_ports_range",
     "fa_raw_part_bytes", "fa_flow_rows_to_native", "fa_raw_enable", "fa_raw_build_columns_device", "fa_raw_take", "fa_raw_take_device",
     "fa_raw_reset", "fa_raw_stats",
+    "fa_raw_take_lz4", "fa_raw_take_lz4_device", "fa_lz4_frame_device", "fa_lz4_frame", "fa_lz4_frame_bound", "fa_raw_lz4_stats",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -370,6 +380,13 @@ def lib():
     L.fa_raw_take_device.argtypes = [vp, C.POINTER(vp), szp, vp, sz, szp]
     L.fa_raw_reset.argtypes = [vp]
     L.fa_raw_stats.argtypes = [vp, C.POINTER(RawStats)]
+    L.fa_raw_take_lz4.argtypes = [vp, vp, sz, szp, vp, sz, szp]
+    L.fa_raw_take_lz4_device.argtypes = [vp, C.POINTER(vp), szp, vp, sz, szp]
+    L.fa_lz4_frame_device.argtypes = [vp, vp, sz, C.POINTER(vp), szp]
+    L.fa_lz4_frame.argtypes = [vp, sz, vp, sz, szp]
+    L.fa_lz4_frame_bound.argtypes = [sz]
+    L.fa_lz4_frame_bound.restype = sz
+    L.fa_raw_lz4_stats.argtypes = [vp, C.POINTER(RawLz4Stats)]
     _LIB = L
     return L
 
@@ -417,6 +434,18 @@ def flow_rows_to_native(rows: np.ndarray) -> bytes:
     rc = lib().fa_flow_rows_to_native(r.ctypes.data, len(r), out.ctypes.data, out.size, C.byref(n))
     if rc:
         raise FlowAggError(rc, "fa_flow_rows_to_native")
+    return out[:n.value].tobytes()
+
+
+def lz4_frame(data) -> bytes:
+    """Bytes -> one LZ4 frame of the form raw_take_lz4 writes (independent 64 KiB blocks, no checksums): fa_lz4_frame, the
+    host twin of the device encoder.  Host code, no GPU."""
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.empty(lib().fa_lz4_frame_bound(a.size), dtype=np.uint8)
+    n = C.c_size_t()
+    rc = lib().fa_lz4_frame(a.ctypes.data if a.size else None, a.size, out.ctypes.data, out.size, C.byref(n))
+    if rc:
+        raise FlowAggError(rc, "fa_lz4_frame")
     return out[:n.value].tobytes()
 
 
@@ -845,6 +874,43 @@ class FlowAgg:
         p, nbytes, nparts = C.c_void_p(), C.c_size_t(), C.c_size_t()
         self._chk(self._L.fa_raw_take_device(self._h, C.byref(p), C.byref(nbytes), parts.ctypes.data, pcap, C.byref(nparts)))
         return p.value or 0, nbytes.value, parts[:nparts.value]
+
+    def raw_take_lz4(self, out: np.ndarray | None = None):
+        """raw_take with every part delivered as one LZ4 frame, compressed in HBM (include/flowagg.h "LZ4 frames of the flows_raw
+        parts"): -> (bytes, parts); the bytes are a valid LZ4 stream, parts[i]'s offset / bytes describe its frame, which decodes
+        to the part (spill.lz4_frames_decode)."""
+        nbytes, nparts = C.c_size_t(), C.c_size_t()
+        cap, pcap = 0, max(int(self.raw_stats()["pending_parts"]), 1)
+        while True:  # (the first call learns the size: the frames are kept, the second call only copies)
+            buf = out if out is not None and out.dtype == np.uint8 and out.size >= cap else np.empty(cap, dtype=np.uint8)
+            parts = np.zeros(pcap, dtype=RAW_PART_DTYPE)
+            rc = self._L.fa_raw_take_lz4(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(nbytes), parts.ctypes.data, pcap, C.byref(nparts))
+            if rc == -6:
+                cap, pcap = nbytes.value, max(nparts.value, 1)
+                continue
+            self._chk(rc)
+            data = buf[:nbytes.value]
+            return (data if out is not None and buf is out else data.tobytes()), parts[:nparts.value]
+
+    def raw_take_lz4_device(self):
+        """-> (device pointer, bytes, parts): raw_take_lz4 with the frames left in HBM (valid until the ctx's next ingest, raw or lz4 call)."""
+        pcap = max(int(self.raw_stats()["pending_parts"]), 1)
+        parts = np.zeros(pcap, dtype=RAW_PART_DTYPE)
+        p, nbytes, nparts = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        self._chk(self._L.fa_raw_take_lz4_device(self._h, C.byref(p), C.byref(nbytes), parts.ctypes.data, pcap, C.byref(nparts)))
+        return p.value or 0, nbytes.value, parts[:nparts.value]
+
+    def lz4_frame_device(self, d_in_ptr: int, n: int):
+        """n bytes in HBM -> (device pointer, bytes) of ONE LZ4 frame in HBM (owned by the ctx, valid until its next ingest, raw or
+        lz4 call).  Works without raw_enable."""
+        p, nbytes = C.c_void_p(), C.c_size_t()
+        self._chk(self._L.fa_lz4_frame_device(self._h, d_in_ptr or None, n, C.byref(p), C.byref(nbytes)))
+        return p.value or 0, nbytes.value
+
+    def raw_lz4_stats(self) -> dict:
+        s = RawLz4Stats()
+        self._chk(self._L.fa_raw_lz4_stats(self._h, C.byref(s)))
+        return s.as_dict()
 
     def raw_reset(self):
         self._chk(self._L.fa_raw_reset(self._h))

@@ -31,6 +31,7 @@
 #include "buffers.h"
 #include "kernels.cuh"
 #include "launch_plan.h"
+#include "lz4.cuh"
 #include "raw.cuh"
 
 using namespace fa;
@@ -224,6 +225,7 @@ struct fa_ctx {
     struct TalkState* talk = nullptr;  // exact top talkers (fa_talkers_enable; talkers_host.inc), nullptr = not enabled
     struct PortState* ports = nullptr;  // bucketed port tables (fa_ports_enable_buckets; ports_host.inc), nullptr = not enabled
     struct RawState* raw = nullptr;     // flows_raw parts (fa_raw_enable; raw_host.inc), nullptr = not enabled
+    struct Lz4State* lz4 = nullptr;     // LZ4 frames (lz4_host.inc), nullptr until the first fa_raw_take_lz4 / fa_lz4_frame_device
 
     fa_stats_t stats{};
     uint64_t used_base = 0;  // groups created before the current counter epoch
@@ -261,6 +263,8 @@ static int second_pass_records(fa_ctx* c, const void* d_buf, size_t len, const u
 static void talk_destroy(fa_ctx* c);
 static void port_destroy(fa_ctx* c);
 static void raw_destroy(fa_ctx* c);
+static void lz4_destroy(fa_ctx* c);
+static void lz4_release(fa_ctx* c);
 
 extern "C" uint32_t fa_abi_version(void) { return FA_ABI_VERSION; }
 
@@ -550,6 +554,7 @@ extern "C" void fa_destroy(fa_ctx* c) {
     talk_destroy(c);
     port_destroy(c);
     raw_destroy(c);
+    lz4_destroy(c);
     const hipStream_t streams[3] = {c->copy_stream, c->cand_stream, c->stream};
     delete c;  // every buffer is released here (fa_ctx's members own them): before the streams go, as ever
     for (hipStream_t s : streams)
@@ -583,6 +588,7 @@ static bool bucket_range(const fa_ctx* c, uint32_t timeslot, uint32_t& lo, uint3
 #include "talkers_host.inc"
 #include "ports_host.inc"
 #include "raw_host.inc"
+#include "lz4_host.inc"
 #include "second_pass.inc"
 
 extern "C" int fa_stats(fa_ctx* c, fa_stats_t* out) {

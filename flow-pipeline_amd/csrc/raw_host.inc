@@ -20,6 +20,7 @@ struct RawState {
     bool ev_pending = false;
     uint64_t records_in = 0, records_bad = 0, rows_out = 0, parts_out = 0, bytes_out = 0, chunks = 0;
     uint64_t order_ns = 0, gather_ns = 0, launches = 0;
+    uint64_t takes = 0;    // times the pending parts were cleared (a take, a reset): frames made of them before are stale (lz4_host.inc)
 };
 static constexpr size_t RAW_LIST_FIRST = 4096;  // header + 255 entries: what one small copy brings
 
@@ -297,6 +298,7 @@ static void raw_clear(RawState* t, fa_raw_part* parts) {
     if (parts && !t->pending.empty()) memcpy(parts, t->pending.data(), t->pending.size() * sizeof(fa_raw_part));
     t->pending.clear();
     t->used = 0;
+    t->takes++;
 }
 
 extern "C" int fa_raw_take(fa_ctx* c, uint8_t* out, size_t cap, size_t* bytes_out, fa_raw_part* parts, size_t parts_cap, size_t* n_parts) {
@@ -335,6 +337,7 @@ extern "C" int fa_raw_reset(fa_ctx* c) {
     raw_clear(t, nullptr);
     t->img.reset();
     t->scratch.reset();
+    lz4_release(c);
     return FA_OK;
 }
 

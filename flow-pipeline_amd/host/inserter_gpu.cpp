@@ -37,6 +37,11 @@
 //   - -out.raw.native=PATH: every ctx builds flows_raw parts (fa_raw_enable: per chunk and Date one sorted ClickHouse Native block,
 //     create.sh:36-68); after every flush the partition's parts are taken and appended to PATH under the writer's lock, so the
 //     file is a valid concatenation of blocks for `INSERT INTO flows_raw FORMAT Native`.
+//   - -out.raw.native.lz4=PATH: the same parts, each as one LZ4 frame compressed in HBM (fa_raw_take_lz4: about a quarter of the
+//     bytes cross PCIe); the file is a valid LZ4 stream of Native blocks (`INSERT ... FROM INFILE 'x.lz4'`, or the body of an HTTP
+//     insert with Content-Encoding: lz4).  May be given together with -out.raw.native: the flush's parts are built once and
+//     taken once, as frames; the plain file receives the bytes the frames decode to (lz4_frames_to_plain below - the library
+//     clears the parts with a successful take of either kind, and decoding costs less than a second, four times larger copy).
 #include <atomic>
 #include <chrono>
 #include <cstdarg>
@@ -77,6 +82,7 @@ struct Flags {
     std::string InputFiles, InputFormat = "framed";
     std::string OutRowBinary, OutTsv, OffsetsOut, MetricsDump;
     std::string OutRawNative;  // flows_raw parts of every flush, appended: ClickHouse Native blocks (fa_raw_take)
+    std::string OutRawNativeLz4;  // ... the same parts as LZ4 frames (fa_raw_take_lz4)
     std::string OutApp, OutTopk, GpuTransport = "peer";  // raw fa_row_app records / "src|dst <hex key> <weight>" lines; peer | rccl
     long TopkK = 100;
     long TableLog2 = 0, KeysetLog2 = 0, WideLog2 = 0;  // fa_config capacities (0 = the library's defaults)
@@ -156,6 +162,7 @@ static Flags parse_flags(int argc, char** argv) {
         {"input.format", &f.InputFormat}, {"out.rowbinary", &f.OutRowBinary}, {"out.tsv", &f.OutTsv},
         {"offsets.out", &f.OffsetsOut}, {"metrics.dump", &f.MetricsDump}, {"out.app", &f.OutApp}, {"out.topk", &f.OutTopk},
         {"out.raw.native", &f.OutRawNative},
+        {"out.raw.native.lz4", &f.OutRawNativeLz4},
         {"gpu.transport", &f.GpuTransport}, {"topk.mode", &f.TopkMode}, {"phases.out", &f.PhasesOut}};
     std::map<std::string, long*> ints = {
         {"flush.count", &f.FlushCount}, {"postgres.port", &f.PostgresPort}, {"gpu.devices", &f.GpuDevices},
@@ -314,8 +321,20 @@ public:
         if (!f.OutApp.empty() && !(app_ = fopen(f.OutApp.c_str(), "wb"))) fatal("cannot open %s", f.OutApp.c_str());
         if (!f.OutTopk.empty() && !(topk_ = fopen(f.OutTopk.c_str(), "w"))) fatal("cannot open %s", f.OutTopk.c_str());
         if (!f.OutRawNative.empty() && !(raw_ = fopen(f.OutRawNative.c_str(), "wb"))) fatal("cannot open %s", f.OutRawNative.c_str());
+        if (!f.OutRawNativeLz4.empty() && !(rawlz4_ = fopen(f.OutRawNativeLz4.c_str(), "wb"))) fatal("cannot open %s", f.OutRawNativeLz4.c_str());
     }
-    bool wantsRaw() const { return raw_ != nullptr; }
+    bool wantsRaw() const { return raw_ != nullptr || rawlz4_ != nullptr; }
+    bool wantsRawPlain() const { return raw_ != nullptr; }
+    bool wantsRawLz4() const { return rawlz4_ != nullptr; }
+    // a partition's parts as LZ4 frames and, where both files are written, the bytes they decode to: under ONE hold of the lock, so
+    // that the two files list the parts in the same order
+    void writeRawLz4(const uint8_t* frames, size_t n, const uint8_t* plain, size_t nplain, uint64_t rows) {
+        if (!n || !rawlz4_) return;
+        std::lock_guard<std::mutex> g(mu_);
+        if (fwrite(frames, 1, n, rawlz4_) != n) fatal("short write on the raw Native LZ4 sink");
+        if (raw_ && nplain && fwrite(plain, 1, nplain, raw_) != nplain) fatal("short write on the raw Native sink");
+        RawRowsOut += rows;
+    }
     // a partition's flows_raw parts: whole Native blocks, written under the lock - the file is a concatenation of blocks whatever
     // the number of partition threads
     void writeRaw(const uint8_t* bytes, size_t n, uint64_t rows) {
@@ -364,7 +383,8 @@ public:
         if (app_) fclose(app_);
         if (topk_) fclose(topk_);
         if (raw_) fclose(raw_);
-        rb_ = tsv_ = app_ = topk_ = raw_ = nullptr;
+        if (rawlz4_) fclose(rawlz4_);
+        rb_ = tsv_ = app_ = topk_ = raw_ = rawlz4_ = nullptr;
     }
 
 private:
@@ -375,7 +395,61 @@ private:
     FILE* app_ = nullptr;
     FILE* topk_ = nullptr;
     FILE* raw_ = nullptr;
+    FILE* rawlz4_ = nullptr;
 };
+
+// The frames fa_raw_take_lz4 wrote (include/flowagg.h: independent blocks of at most 64 KiB, no checksums) -> the bytes they
+// decode to, appended to `out`.  The input comes from the library, so anything unexpected is fatal; every read and every copy
+// is checked against its buffer all the same.
+static void lz4_frames_to_plain(const uint8_t* in, size_t n, std::vector<uint8_t>& out) {
+    static const uint8_t header[7] = {0x04, 0x22, 0x4D, 0x18, 0x60, 0x40, 0x82};
+    size_t p = 0;
+    while (p < n) {
+        if (n - p < 7 || memcmp(in + p, header, 7) != 0) fatal("LZ4 frames: no frame header at byte %zu", p);
+        p += 7;
+        for (;;) {
+            if (n - p < 4) fatal("LZ4 frames: truncated");
+            const uint32_t word = (uint32_t)in[p] | (uint32_t)in[p + 1] << 8 | (uint32_t)in[p + 2] << 16 | (uint32_t)in[p + 3] << 24;
+            p += 4;
+            if (!word) break;
+            const size_t size = word & 0x7FFFFFFFu, base = out.size();
+            if (size > 65536 || size > n - p) fatal("LZ4 frames: block size %zu at byte %zu", size, p - 4);
+            const uint8_t *s = in + p, *end = s + size;
+            p += size;
+            if (word >> 31) {
+                out.insert(out.end(), s, end);
+                continue;
+            }
+            auto length = [&](size_t v) {
+                if (v == 15) {
+                    uint8_t b;
+                    do {
+                        if (s >= end) fatal("LZ4 frames: truncated length");
+                        v += (b = *s++);
+                    } while (b == 255);
+                }
+                return v;
+            };
+            for (;;) {
+                if (s >= end) fatal("LZ4 frames: truncated block");
+                const uint8_t token = *s++;
+                const size_t lit = length(token >> 4);
+                if (lit > (size_t)(end - s) || out.size() - base + lit > 65536) fatal("LZ4 frames: literals run past the block");
+                out.insert(out.end(), s, s + lit);
+                s += lit;
+                if (s == end) break;
+                if (end - s < 2) fatal("LZ4 frames: truncated offset");
+                const size_t offset = (size_t)s[0] | (size_t)s[1] << 8;
+                s += 2;
+                const size_t mlen = length(token & 15) + 4;
+                if (!offset || offset > out.size() - base || out.size() - base + mlen > 65536) fatal("LZ4 frames: a match outside its block");
+                const size_t from = out.size() - offset;
+                out.resize(out.size() + mlen);
+                for (size_t i = 0; i < mlen; i++) out[from + offset + i] = out[from + i];  // (byte by byte: a match may overlap itself)
+            }
+        }
+    }
+}
 
 // one aggregation context per claimed partition (fa_ctx is not thread-safe; distinct ctxs are independent)
 struct Phases {  // seconds of one partition thread, by what it was doing
@@ -405,6 +479,7 @@ struct PartitionState {
     size_t pending = 0;             // messages in the batch
     std::vector<uint8_t> raw_bytes;  // -out.raw.native: the flush's parts on their way to the file
     std::vector<fa_raw_part> raw_parts;
+    std::vector<uint8_t> raw_plain;  // -out.raw.native beside -out.raw.native.lz4: what the flush's frames decode to
     ConsumerMessage last{};         // the newest of them: offsets of one partition are monotone, marking it commits the batch
     Phases ph;
     size_t bytes() const { return run ? run_len : buf.size(); }
@@ -616,6 +691,25 @@ public:
     // copy and are appended to the file; a too small buffer is told its size and asked again
     void takeRaw(PartitionState& p) {
         size_t bytes = 0, nparts = 0;
+        if (out_.wantsRawLz4()) {  // one take, as frames; the retry copies the frames the first call made
+            int rc = fa_raw_take_lz4(p.ctx, p.raw_bytes.data(), p.raw_bytes.size(), &bytes, p.raw_parts.data(), p.raw_parts.size(), &nparts);
+            if (rc == FA_ERR_CAPACITY) {
+                if (bytes > p.raw_bytes.size()) p.raw_bytes.resize(bytes + bytes / 4);
+                if (nparts > p.raw_parts.size()) p.raw_parts.resize(nparts + 8);
+                rc = fa_raw_take_lz4(p.ctx, p.raw_bytes.data(), p.raw_bytes.size(), &bytes, p.raw_parts.data(), p.raw_parts.size(), &nparts);
+            }
+            if (rc != 0) fatal("fa_raw_take_lz4: %d %s", rc, fa_last_error(p.ctx));
+            uint64_t rows = 0, plain = 0;
+            for (size_t i = 0; i < nparts; i++) rows += p.raw_parts[i].rows, plain += fa_raw_part_bytes(p.raw_parts[i].rows);
+            p.raw_plain.clear();
+            if (out_.wantsRawPlain()) {
+                p.raw_plain.reserve(plain);
+                lz4_frames_to_plain(p.raw_bytes.data(), bytes, p.raw_plain);
+                if (p.raw_plain.size() != plain) fatal("LZ4 frames: %zu bytes decoded where the parts hold %llu", p.raw_plain.size(), (unsigned long long)plain);
+            }
+            out_.writeRawLz4(p.raw_bytes.data(), bytes, p.raw_plain.data(), p.raw_plain.size(), rows);
+            return;
+        }
         int rc = fa_raw_take(p.ctx, p.raw_bytes.data(), p.raw_bytes.size(), &bytes, p.raw_parts.data(), p.raw_parts.size(), &nparts);
         if (rc == FA_ERR_CAPACITY) {
             if (bytes > p.raw_bytes.size()) p.raw_bytes.resize(bytes + bytes / 4);

@@ -105,10 +105,146 @@ def _read_varuint(b: np.ndarray, p: int):
             return v, p
 
 
+# ---- LZ4 frames of the parts (pure Python) ---------------------------------------------------------------------------------------
+# The library delivers a part as one LZ4 frame (fa_raw_take_lz4; format in include/flowagg.h, restated from the LZ4 frame and
+# block format specifications): magic, FLG, BD, header checksum, blocks of a 4-byte size + data, EndMark.  This is the reader
+# for offline checks; it reads what the library writes and says clearly what it does not.
+LZ4_MAGIC = b"\x04\x22\x4d\x18"
+_M32 = 0xFFFFFFFF
+
+
+def _xxh32(data: bytes, seed: int = 0) -> int:
+    """xxHash32 (restated from the xxHash specification)."""
+    P1, P2, P3, P4, P5 = 2654435761, 2246822519, 3266489917, 668265263, 374761393
+    rotl = lambda x, r: ((x << r) | (x >> (32 - r))) & _M32
+    n, p = len(data), 0
+    if n >= 16:
+        v = [(seed + P1 + P2) & _M32, (seed + P2) & _M32, seed, (seed - P1) & _M32]
+        while p + 16 <= n:
+            for i in range(4):
+                v[i] = rotl((v[i] + int.from_bytes(data[p + 4 * i:p + 4 * i + 4], "little") * P2) & _M32, 13) * P1 & _M32
+            p += 16
+        h = (rotl(v[0], 1) + rotl(v[1], 7) + rotl(v[2], 12) + rotl(v[3], 18)) & _M32
+    else:
+        h = (seed + P5) & _M32
+    h = (h + n) & _M32
+    while p + 4 <= n:
+        h = rotl((h + int.from_bytes(data[p:p + 4], "little") * P3) & _M32, 17) * P4 & _M32
+        p += 4
+    while p < n:
+        h = rotl((h + data[p] * P5) & _M32, 11) * P1 & _M32
+        p += 1
+    h ^= h >> 15
+    h = h * P2 & _M32
+    h ^= h >> 13
+    h = h * P3 & _M32
+    return h ^ (h >> 16)
+
+
+def _lz4_block_decode(src: bytes, limit: int) -> bytes:
+    """One LZ4 block, decoded alone (no history in front of it), to at most `limit` bytes."""
+    out, p, n = bytearray(), 0, len(src)
+    while True:
+        if p >= n:
+            raise ValueError("LZ4 block: truncated (a sequence's token is missing)")
+        token = src[p]
+        p += 1
+        lit = token >> 4
+        if lit == 15:
+            while True:
+                if p >= n:
+                    raise ValueError("LZ4 block: truncated literal length")
+                lit += src[p]
+                p += 1
+                if src[p - 1] != 255:
+                    break
+        if p + lit > n:
+            raise ValueError("LZ4 block: literals run past the block's end")
+        out += src[p:p + lit]
+        p += lit
+        if p == n:  # the last sequence has no match
+            break
+        if p + 2 > n:
+            raise ValueError("LZ4 block: truncated offset")
+        offset = src[p] | (src[p + 1] << 8)
+        p += 2
+        mlen = (token & 15) + 4
+        if token & 15 == 15:
+            while True:
+                if p >= n:
+                    raise ValueError("LZ4 block: truncated match length")
+                mlen += src[p]
+                p += 1
+                if src[p - 1] != 255:
+                    break
+        if offset == 0 or offset > len(out):
+            raise ValueError("LZ4 block: offset %d with %d bytes decoded (blocks must decode alone)" % (offset, len(out)))
+        if len(out) + mlen > limit:
+            raise ValueError("LZ4 block: decodes to more than %d bytes" % limit)
+        start = len(out) - offset
+        if offset >= mlen:
+            out += out[start:start + mlen]
+        else:  # an overlapping match repeats its last `offset` bytes
+            pattern = bytes(out[start:])
+            out += (pattern * (mlen // offset + 1))[:mlen]
+    if len(out) > limit:
+        raise ValueError("LZ4 block: decodes to more than %d bytes" % limit)
+    return bytes(out)
+
+
+def lz4_frames_decode(data) -> bytes:
+    """A concatenation of LZ4 frames as the library writes them -> the decoded bytes of all of them, in order.  The header
+    checksum is verified and every block is decoded alone.  ValueError, with a text that names the reason, on anything the
+    library does not write: linked blocks, block or content checksums, a content size, a dictionary id, a skippable or legacy
+    frame, a block larger than the frame's maximum, a truncated stream."""
+    b = bytes(data) if not isinstance(data, bytes) else data
+    out, p = [], 0
+    while p < len(b):
+        magic = b[p:p + 4]
+        if len(magic) == 4 and 0x184D2A50 <= int.from_bytes(magic, "little") <= 0x184D2A5F:
+            raise ValueError("LZ4 stream: a skippable frame at byte %d (the library writes none)" % p)
+        if magic != LZ4_MAGIC:
+            raise ValueError("LZ4 stream: no frame magic at byte %d" % p)
+        if p + 7 > len(b):
+            raise ValueError("LZ4 stream: truncated frame header at byte %d" % p)
+        flg, bd, hc = b[p + 4], b[p + 5], b[p + 6]
+        if flg >> 6 != 1:
+            raise ValueError("LZ4 frame: version %d (01 is the only one)" % (flg >> 6))
+        for bit, what in ((0x20, None), (0x10, "block checksums"), (0x08, "a content size"), (0x04, "a content checksum"), (0x01, "a dictionary id")):
+            if what is None:
+                if not flg & bit:
+                    raise ValueError("LZ4 frame: linked blocks (the library writes independent blocks, each decodes alone)")
+            elif flg & bit:
+                raise ValueError("LZ4 frame: %s (the library writes none)" % what)
+        if flg & 0x02 or bd & 0x8F or not 4 <= bd >> 4 <= 7:
+            raise ValueError("LZ4 frame: reserved bits set or an invalid block size id (FLG %#04x BD %#04x)" % (flg, bd))
+        if (_xxh32(b[p + 4:p + 6]) >> 8) & 0xFF != hc:
+            raise ValueError("LZ4 frame: header checksum %#04x does not match FLG / BD" % hc)
+        block_max = 1 << (8 + 2 * (bd >> 4))
+        p += 7
+        while True:
+            if p + 4 > len(b):
+                raise ValueError("LZ4 stream: truncated (no EndMark)")
+            word = int.from_bytes(b[p:p + 4], "little")
+            p += 4
+            if word == 0:
+                break
+            size = word & 0x7FFFFFFF
+            if size > block_max:
+                raise ValueError("LZ4 frame: a block of %d bytes, the frame's maximum is %d" % (size, block_max))
+            if p + size > len(b):
+                raise ValueError("LZ4 stream: truncated block")
+            out.append(b[p:p + size] if word >> 31 else _lz4_block_decode(b[p:p + size], block_max))
+            p += size
+    return b"".join(out)
+
+
 def read_native(data) -> list:
     """A concatenation of flows_raw Native blocks -> one {column: array} per block, in order (FixedString(16) columns as
     uint8[rows, 16]).  Anything that is not a whole number of blocks with the 16 columns and types of flows_raw - a trailing
-    byte included - raises ValueError."""
+    byte included - raises ValueError.  Input that starts with the LZ4 frame magic is decoded first (lz4_frames_decode)."""
+    if bytes(data[:4]) == LZ4_MAGIC:
+        data = lz4_frames_decode(data)
     b = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
     blocks, p = [], 0
     while p < len(b):

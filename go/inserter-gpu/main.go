@@ -95,6 +95,7 @@ var (
 	MarkAfter   = flag.Bool("mark.after.close", true, "Commit a batch's offsets only after every window it touched has been emitted")
 	GpuTransport = flag.String("gpu.transport", "peer", "Window-close exchange between the GPUs: peer (hipMemcpyPeer over xGMI) or rccl (sketches by ncclAllReduce)")
 	OutRawNative = flag.String("out.raw.native", "", "Append every flush's flows_raw parts to this file as ClickHouse Native blocks (one sorted block per chunk and Date)")
+	OutRawNativeLz4 = flag.String("out.raw.native.lz4", "", "Append the same parts to this file as LZ4 frames compressed on the GPU (one frame per part; a valid .lz4 stream of Native blocks); may be given together with -out.raw.native")
 	OutTopk      = flag.String("out.topk", "", "At the end of a session write the top -topk.k SrcAddr / DstAddr of the merged Count-Min sketches here (key.sets 2 / 4)")
 	TopkK        = flag.Int("topk.k", 100, "Rows of -out.topk per sketch")
 	TableLog2    = flag.Int("gpu.table.log2", 0, "log2 slots of a context's flows_5m table (0 = library default)")
@@ -184,7 +185,7 @@ func newPartition(partition int32, claims int) *partitionState {
 			log.Fatalf("fa_reserve_ingest: %d %s", int(rc), C.GoString(C.fa_last_error(ctx)))
 		}
 	}
-	if *OutRawNative != "" {
+	if *OutRawNative != "" || *OutRawNativeLz4 != "" {
 		if rc := C.fa_raw_enable(ctx, 0); rc != 0 {
 			log.Fatalf("fa_raw_enable: %d %s", int(rc), C.GoString(C.fa_last_error(ctx)))
 		}
@@ -194,8 +195,12 @@ func newPartition(partition int32, claims int) *partitionState {
 
 // takeRaw: the parts the flush built (fa_raw_enable) leave HBM with one copy; a too small buffer is told its size and asked
 // again.  Errors are RETURNED (the caller holds closeMu for reading, see openTimeslots).
-func (p *partitionState) takeRaw() ([]byte, error) {
+func (p *partitionState) takeRaw(lz4 bool) ([]byte, error) {
 	var nb, np C.size_t
+	name := "fa_raw_take"
+	if lz4 {
+		name = "fa_raw_take_lz4" // (one frame per part; the retry copies the frames the first call made)
+	}
 	take := func() C.int {
 		var b *C.uint8_t
 		var q *C.fa_raw_part
@@ -204,6 +209,9 @@ func (p *partitionState) takeRaw() ([]byte, error) {
 		}
 		if len(p.rawParts) > 0 {
 			q = &p.rawParts[0]
+		}
+		if lz4 {
+			return C.fa_raw_take_lz4(p.ctx, b, C.size_t(len(p.rawBytes)), &nb, q, C.size_t(len(p.rawParts)), &np)
 		}
 		return C.fa_raw_take(p.ctx, b, C.size_t(len(p.rawBytes)), &nb, q, C.size_t(len(p.rawParts)), &np)
 	}
@@ -218,9 +226,92 @@ func (p *partitionState) takeRaw() ([]byte, error) {
 		rc = take()
 	}
 	if rc != 0 {
-		return nil, fmt.Errorf("fa_raw_take: %d %s", int(rc), C.GoString(C.fa_last_error(p.ctx)))
+		return nil, fmt.Errorf("%s: %d %s", name, int(rc), C.GoString(C.fa_last_error(p.ctx)))
 	}
 	return p.rawBytes[:int(nb)], nil
+}
+
+// lz4FramesToPlain: the frames fa_raw_take_lz4 wrote (include/flowagg.h: independent blocks of at most 64 KiB, no checksums) ->
+// the bytes they decode to.  -out.raw.native beside -out.raw.native.lz4: the flush's parts are built once and taken once, as
+// frames, and the plain file receives what they decode to.
+func lz4FramesToPlain(in []byte) ([]byte, error) {
+	header := []byte{0x04, 0x22, 0x4D, 0x18, 0x60, 0x40, 0x82}
+	bad := fmt.Errorf("malformed LZ4 frames from fa_raw_take_lz4")
+	var out []byte
+	p := 0
+	for p < len(in) {
+		if len(in)-p < 7 || string(in[p:p+7]) != string(header) {
+			return nil, bad
+		}
+		p += 7
+		for {
+			if len(in)-p < 4 {
+				return nil, bad
+			}
+			word := uint32(in[p]) | uint32(in[p+1])<<8 | uint32(in[p+2])<<16 | uint32(in[p+3])<<24
+			p += 4
+			if word == 0 {
+				break
+			}
+			size := int(word & 0x7FFFFFFF)
+			if size > 65536 || size > len(in)-p {
+				return nil, bad
+			}
+			s := in[p : p+size]
+			p += size
+			if word>>31 != 0 {
+				out = append(out, s...)
+				continue
+			}
+			base, q := len(out), 0
+			length := func(v int) (int, bool) {
+				if v == 15 {
+					for {
+						if q >= len(s) {
+							return 0, false
+						}
+						b := s[q]
+						q++
+						v += int(b)
+						if b != 255 {
+							break
+						}
+					}
+				}
+				return v, true
+			}
+			for {
+				if q >= len(s) {
+					return nil, bad
+				}
+				token := s[q]
+				q++
+				lit, ok := length(int(token >> 4))
+				if !ok || lit > len(s)-q || len(out)-base+lit > 65536 {
+					return nil, bad
+				}
+				out = append(out, s[q:q+lit]...)
+				q += lit
+				if q == len(s) {
+					break
+				}
+				if len(s)-q < 2 {
+					return nil, bad
+				}
+				offset := int(s[q]) | int(s[q+1])<<8
+				q += 2
+				mlen, ok := length(int(token & 15))
+				mlen += 4
+				if !ok || offset == 0 || offset > len(out)-base || len(out)-base+mlen > 65536 {
+					return nil, bad
+				}
+				for i, from := 0, len(out)-offset; i < mlen; i++ { // (byte by byte: a match may overlap itself)
+					out = append(out, out[from+i])
+				}
+			}
+		}
+	}
+	return out, nil
 }
 
 // flush = inserter.go:90-111 with the per-row db.Exec loop replaced by one fa_ingest.
@@ -239,9 +330,14 @@ func (p *partitionState) flush(s *state, session sarama.ConsumerGroupSession) {
 	if rc == 0 && *MarkAfter {
 		open, openErr = p.openTimeslots() // the batch's records can only sit in timeslots that are open now
 	}
-	var raw []byte
-	if rc == 0 && openErr == nil && *OutRawNative != "" {
-		raw, openErr = p.takeRaw()
+	var raw, rawLz4 []byte
+	if rc == 0 && openErr == nil && *OutRawNativeLz4 != "" {
+		rawLz4, openErr = p.takeRaw(true)
+		if openErr == nil && *OutRawNative != "" {
+			raw, openErr = lz4FramesToPlain(rawLz4)
+		}
+	} else if rc == 0 && openErr == nil && *OutRawNative != "" {
+		raw, openErr = p.takeRaw(false)
 	}
 	s.closeMu.RUnlock() // (released before ANY fatal error: sinkFatal's last-resort close wants the write lock)
 	if rc != 0 {
@@ -250,9 +346,14 @@ func (p *partitionState) flush(s *state, session sarama.ConsumerGroupSession) {
 	if openErr != nil {
 		sinkFatal("%v", openErr)
 	}
-	if len(raw) > 0 {
-		s.rawMu.Lock()
-		appendFile(*OutRawNative, raw)
+	if len(raw) > 0 || len(rawLz4) > 0 {
+		s.rawMu.Lock() // (one hold for both files: they list the parts in the same order)
+		if len(rawLz4) > 0 {
+			appendFile(*OutRawNativeLz4, rawLz4)
+		}
+		if len(raw) > 0 {
+			appendFile(*OutRawNative, raw)
+		}
 		s.rawMu.Unlock()
 	}
 	Inserts.Add(float64(n))

@@ -592,6 +592,49 @@ int fa_raw_take_device(fa_ctx*, const void** d_bytes, size_t* bytes_out, fa_raw_
 int fa_raw_reset(fa_ctx*);
 int fa_raw_stats(fa_ctx*, fa_raw_stats_t* out);
 
+/* ---- ABI 8, addition: LZ4 frames of the flows_raw parts ---------------------------- */
+/* fa_raw_take moves 110 bytes per row and is the expensive step of the raw path; the columns are highly redundant (a constant
+ * Date, a sorted TimeReceived, address prefixes, a handful of AS / EType / Proto values).  fa_raw_take_lz4 compresses the
+ * pending parts in HBM - one wave per 64 KiB block, csrc/lz4.cuh - and copies the compressed bytes.  Each part becomes ONE frame
+ * of the LZ4 frame format (restated from the LZ4 frame format specification):
+ *   magic 04 22 4D 18 | FLG 0x60 (version 01, independent blocks, no block checksum, no content size, no content checksum, no
+ *   dictionary) | BD 0x40 (64 KiB maximum block size) | header checksum 0x82 = (xxHash32(FLG BD) >> 8) & 0xFF, computed |
+ *   data blocks: 4-byte little-endian size + data, at most 65536 input bytes each; a block whose LZ4 form would not be smaller
+ *   than its input is stored raw with bit 31 of the size set | EndMark 00 00 00 00.
+ * Frames stand back to back in build order; a concatenation of frames is a valid LZ4 stream and each frame alone decodes to one
+ * whole part.  ClickHouse takes the stream as `Content-Encoding: lz4` on an HTTP insert or as a .lz4 file for INSERT ... FROM
+ * INFILE [UNVERIFIED: no server was available, as for the Native part itself].  ClickHouse's own compressed-block framing is not
+ * produced.  The bytes are what this encoder finds, not what liblz4 would write; any conforming decoder reads them.
+ * Additive: a ctx that never calls these functions runs the code it ran.  Memory, allocated on first use and released by
+ * fa_raw_reset / fa_destroy: a 64 KiB slot per block (= the input's size), the frames (to the bound), 40 bytes per block. */
+typedef struct {
+    uint64_t frames, blocks, stored_blocks; /* compressed so far by this ctx (both doors); blocks stored raw among them */
+    uint64_t bytes_in, bytes_out;           /* input bytes; frame bytes (headers, size words and EndMarks included) */
+    uint64_t compress_launches;             /* launches queued by compressions (3 each: blocks, scan, pack); a retry adds none */
+    uint64_t device_ns;                     /* hipEvent time of the compressions = block_ns + pack_ns */
+    uint64_t block_ns, pack_ns;             /* ... of lz4_block_kernel; of the scan and lz4_pack_kernel */
+} fa_raw_lz4_stats_t;
+/* fa_raw_take with every part delivered as one frame: parts[i].offset / .bytes describe the FRAME inside the bytes returned,
+ * rows / date / t_min / t_max are unchanged, the part's raw size is fa_raw_part_bytes(rows).  FA_ERR_CAPACITY: the exact bytes
+ * and parts needed come back and nothing is consumed; the compressed bytes are KEPT, so the retry launches no compression unless
+ * a part was built in between - such parts are compressed in addition, in order.  fa_raw_take after a failed fa_raw_take_lz4
+ * delivers the plain bytes and clears both; after a successful take of either kind nothing is pending.  Synchronous.
+ * FA_ERR_ARG (text in fa_last_error) on a ctx without fa_raw_enable. */
+int fa_raw_take_lz4(fa_ctx*, uint8_t* out, size_t cap, size_t* bytes_out, fa_raw_part* parts, size_t parts_cap, size_t* n_parts);
+/* The same, the frames left in HBM (*d_bytes: DEVICE pointer, owned by the ctx, valid until its next ingest, raw or lz4 call). */
+int fa_raw_take_lz4_device(fa_ctx*, const void** d_bytes, size_t* bytes_out, fa_raw_part* parts, size_t parts_cap, size_t* n_parts);
+/* n bytes in HBM (d_in: DEVICE pointer) -> one frame in HBM (*d_out: owned by the ctx, valid until its next ingest, raw or lz4
+ * call); n == 0 gives header + EndMark, 11 bytes.  Synchronous.  Works on any ctx, fa_raw_enable is not needed: the door for
+ * callers that compress something else (RowBinary rows, for instance).  Pending parts and kept frames are not touched. */
+int fa_lz4_frame_device(fa_ctx*, const void* d_in, size_t n, const void** d_out, size_t* bytes_out);
+/* Host only, no ctx, the twin: a plain greedy encoder into the same frame format (not necessarily the device's bytes).
+ * FA_ERR_CAPACITY (and the size in *bytes_out) when cap is too small. */
+int fa_lz4_frame(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* bytes_out);
+/* Host only: the largest frame n bytes can give (n + 4 per block + 11). */
+size_t fa_lz4_frame_bound(size_t n);
+/* The counters of this ctx's compressions; works on any ctx (all zero before the first compression). */
+int fa_raw_lz4_stats(fa_ctx*, fa_raw_lz4_stats_t* out);
+
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
  *   if(EType = 0x800, IPv4NumToString(reinterpretAsUInt32(substring(reverse(Addr), 13, 4))), IPv6NumToString(Addr))
