@@ -113,6 +113,19 @@ class RawLz4Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RawLoadStats(C.Structure):
+    """fa_raw_load_stats_t: what the ctx's decodes and loads (lz4_decode_device, raw_columns, raw_load) have done so far."""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "calls", "frames", "blocks", "stored_blocks", "bytes_in", "bytes_decoded", "parts", "rows_loaded", "launches",
+        "decode_ns", "unpack_ns", "fold_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+LZ4_SPAN_DTYPE = np.dtype([("offset", "<u8"), ("bytes", "<u8")])  # fa_lz4_span
+
+
 class MockParams(C.Structure):
     _fields_ = [
         ("mode", C.c_uint32), ("framed", C.c_uint32), ("seed", C.c_uint64),
@@ -189,6 +202,7 @@ EXPORTS = [
     "fa_raw_part_bytes", "fa_flow_rows_to_native", "fa_raw_enable", "fa_raw_build_columns_device", "fa_raw_take", "fa_raw_take_device",
     "fa_raw_reset", "fa_raw_stats",
     "fa_raw_take_lz4", "fa_raw_take_lz4_device", "fa_lz4_frame_device", "fa_lz4_frame", "fa_lz4_frame_bound", "fa_raw_lz4_stats",
+    "fa_lz4_decode", "fa_lz4_decode_device", "fa_raw_columns_device", "fa_raw_load", "fa_raw_load_stats", "fa_raw_load_reset",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -387,6 +401,12 @@ def lib():
     L.fa_lz4_frame_bound.argtypes = [sz]
     L.fa_lz4_frame_bound.restype = sz
     L.fa_raw_lz4_stats.argtypes = [vp, C.POINTER(RawLz4Stats)]
+    L.fa_lz4_decode.argtypes = [vp, sz, vp, sz, szp]
+    L.fa_lz4_decode_device.argtypes = [vp, vp, sz, C.POINTER(vp), vp, sz, szp]
+    L.fa_raw_columns_device.argtypes = [vp, vp, sz, C.POINTER(Columns), szp]
+    L.fa_raw_load.argtypes = [vp, vp, sz]
+    L.fa_raw_load_stats.argtypes = [vp, C.POINTER(RawLoadStats)]
+    L.fa_raw_load_reset.argtypes = [vp]
     _LIB = L
     return L
 
@@ -447,6 +467,27 @@ def lz4_frame(data) -> bytes:
     if rc:
         raise FlowAggError(rc, "fa_lz4_frame")
     return out[:n.value].tobytes()
+
+
+def lz4_decode(data) -> bytes:
+    """A concatenation of LZ4 frames of the form the library writes -> their decoded bytes: fa_lz4_decode, the host twin of
+    lz4_decode_device (the same per-sequence step function) and the C twin of spill.lz4_frames_decode.  No GPU, no ctx."""
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = C.c_size_t()
+    rc = lib().fa_lz4_decode(a.ctypes.data if a.size else None, a.size, None, 0, C.byref(n))
+    if rc == 0:
+        return b""
+    if rc != -6:
+        raise FlowAggError(rc, "fa_lz4_decode: not a concatenation of LZ4 frames the library reads")
+    out = np.empty(n.value, dtype=np.uint8)
+    rc = lib().fa_lz4_decode(a.ctypes.data, a.size, out.ctypes.data, out.size, C.byref(n))
+    if rc:
+        raise FlowAggError(rc, "fa_lz4_decode")
+    return out[:n.value].tobytes()
+
+
+def _host_bytes(data):
+    return np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
 
 
 def format_addr(addr, etype: int) -> str:
@@ -910,6 +951,46 @@ class FlowAgg:
     def raw_lz4_stats(self) -> dict:
         s = RawLz4Stats()
         self._chk(self._L.fa_raw_lz4_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
+    # -- loading flows_raw parts back (include/flowagg.h "loading flows_raw parts") -------------
+    def lz4_decode_device(self, data):
+        """LZ4 frames in host memory -> (device pointer, spans): the decoded bytes in HBM (owned by the ctx, valid until its next
+        load, lz4 or raw call) and one (offset, bytes) per frame (LZ4_SPAN_DTYPE; every offset a multiple of 65536)."""
+        a = _host_bytes(data)
+        p, nf = C.c_void_p(), C.c_size_t()
+        cap = 16
+        while True:  # (too few spans: the library's host walk says how many before anything is copied or decoded)
+            spans = np.zeros(cap, dtype=LZ4_SPAN_DTYPE)
+            rc = self._L.fa_lz4_decode_device(self._h, a.ctypes.data if a.size else None, a.size, C.byref(p), spans.ctypes.data, cap, C.byref(nf))
+            if rc == -6:
+                cap = nf.value
+                continue
+            self._chk(rc)
+            return p.value or 0, spans[:nf.value]
+
+    def raw_columns(self, data):
+        """flows_raw parts (LZ4 frames, one part each, or plain Native blocks) -> (Columns, rows): every part unpacked into one
+        column block in HBM, parts in input order, status 0, the two times zero-extended.  Valid until the ctx's next decode or
+        load call.  No fold."""
+        a = _host_bytes(data)
+        cols, rows = Columns(), C.c_size_t()
+        self._chk(self._L.fa_raw_columns_device(self._h, a.ctypes.data if a.size else None, a.size, C.byref(cols), C.byref(rows)))
+        return cols, rows.value
+
+    def raw_load(self, data):
+        """Folds every part of `data` (what raw_take_lz4 or raw_take delivered) into every enabled fold of the ctx: the talkers,
+        plain or bucketed, and the bucketed ports.  A refused input (FlowAggError -7) folds nothing."""
+        a = _host_bytes(data)
+        self._chk(self._L.fa_raw_load(self._h, a.ctypes.data if a.size else None, a.size))
+
+    def raw_load_reset(self):
+        """Releases the buffers of lz4_decode_device / raw_columns / raw_load (and of the LZ4 compressions); works without raw_enable."""
+        self._chk(self._L.fa_raw_load_reset(self._h))
+
+    def raw_load_stats(self) -> dict:
+        s = RawLoadStats()
+        self._chk(self._L.fa_raw_load_stats(self._h, C.byref(s)))
         return s.as_dict()
 
     def raw_reset(self):

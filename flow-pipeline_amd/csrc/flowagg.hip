@@ -32,6 +32,7 @@
 #include "kernels.cuh"
 #include "launch_plan.h"
 #include "lz4.cuh"
+#include "lz4_decode.cuh"
 #include "raw.cuh"
 
 using namespace fa;
@@ -226,6 +227,7 @@ struct fa_ctx {
     struct PortState* ports = nullptr;  // bucketed port tables (fa_ports_enable_buckets; ports_host.inc), nullptr = not enabled
     struct RawState* raw = nullptr;     // flows_raw parts (fa_raw_enable; raw_host.inc), nullptr = not enabled
     struct Lz4State* lz4 = nullptr;     // LZ4 frames (lz4_host.inc), nullptr until the first fa_raw_take_lz4 / fa_lz4_frame_device
+    struct LoadState* load = nullptr;   // loading parts back (raw_load_host.inc), nullptr until the first decode / load call
 
     fa_stats_t stats{};
     uint64_t used_base = 0;  // groups created before the current counter epoch
@@ -265,6 +267,8 @@ static void port_destroy(fa_ctx* c);
 static void raw_destroy(fa_ctx* c);
 static void lz4_destroy(fa_ctx* c);
 static void lz4_release(fa_ctx* c);
+static void load_destroy(fa_ctx* c);
+static void load_release(fa_ctx* c);
 
 extern "C" uint32_t fa_abi_version(void) { return FA_ABI_VERSION; }
 
@@ -555,6 +559,7 @@ extern "C" void fa_destroy(fa_ctx* c) {
     port_destroy(c);
     raw_destroy(c);
     lz4_destroy(c);
+    load_destroy(c);
     const hipStream_t streams[3] = {c->copy_stream, c->cand_stream, c->stream};
     delete c;  // every buffer is released here (fa_ctx's members own them): before the streams go, as ever
     for (hipStream_t s : streams)
@@ -590,6 +595,7 @@ static bool bucket_range(const fa_ctx* c, uint32_t timeslot, uint32_t& lo, uint3
 #include "raw_host.inc"
 #include "lz4_host.inc"
 #include "second_pass.inc"
+#include "raw_load_host.inc"
 
 extern "C" int fa_stats(fa_ctx* c, fa_stats_t* out) {
     FA_ON_DEVICE(c);

@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "align16.cuh"
+
 namespace fa {
 
 constexpr uint32_t RAW_NCOLS = 16;
@@ -219,6 +221,151 @@ __global__ __launch_bounds__(RAW_BLOCK) void raw_gather_kernel(const RawGatherAr
 #pragma unroll
         for (int i = 0; i < 16; i++)
             if (b + i >= 0 && b + i < bytes) dst[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+    }
+}
+
+// ---- loading parts back: the header check and the unpack (host side: raw_load_host.inc) ------------------------------------------
+// A part's size fixes its rows: bytes = 110 rows + 284 + len(varuint(rows)) is strictly increasing in rows.  -> false: no row
+// count gives this size.
+__host__ __device__ inline bool raw_rows_from_bytes(const RawColDef* cols, uint64_t bytes, uint64_t* rows) {
+    const uint64_t fixed = raw_col_offset(cols, 0, RAW_NCOLS) - 1;  // the 16 column headers and the column count's byte: 284
+    for (uint32_t l = 1; l <= 10; l++) {
+        if (bytes < fixed + l || (bytes - fixed - l) % RAW_ROW_BYTES) continue;
+        const uint64_t r = (bytes - fixed - l) / RAW_ROW_BYTES;
+        if (raw_varuint_len(r) == l) {
+            *rows = r;
+            return true;
+        }
+    }
+    return false;
+}
+
+// why a part was refused (RawPartVerdict::code)
+enum { RAW_V_OK = 0, RAW_V_BLOCK = 1, RAW_V_SIZE = 2, RAW_V_NCOLS = 3, RAW_V_ROWS = 4, RAW_V_NAME = 5, RAW_V_TYPE = 6 };
+struct RawPartPlan {
+    uint64_t off, bytes;             // where the part starts in the image; its size when the host knows it (plain Native input)
+    uint32_t first_block, nblocks;   // an LZ4 frame's blocks (nblocks 0xFFFFFFFF: plain input, `bytes` holds): size = (nblocks - 1) * 65536 + the last one's
+};
+struct RawPartVerdict {
+    uint64_t rows, bytes;
+    uint32_t code, at;  // RAW_V_*, and the byte of the part it was found at
+};
+
+// One workgroup of 64 threads per part: its size -> rows, then thread c compares column c's header with the expected bytes at
+// their computed place and thread 0 the column count and varuint(rows).  Reads only the first bytes of the part's span that
+// the header places need, all inside [off, off + bytes).  block_size[4 * b + 2]: the decoded bytes of block b, [4 * b]: its error.
+__global__ __launch_bounds__(64) void raw_header_check_kernel(const RawPartPlan* __restrict__ plan, const uint32_t* __restrict__ block_status, const uint8_t* __restrict__ img,
+                                                              RawPartVerdict* __restrict__ verdict) {
+    __shared__ uint32_t worst;  // the smallest (byte position << 4 | code) any thread found
+    const RawPartPlan p = plan[blockIdx.x];
+    const uint32_t t = threadIdx.x;
+    uint64_t bytes = p.bytes;
+    bool blocks_ok = true;
+    if (p.nblocks != 0xFFFFFFFFu) {
+        bytes = 0;
+        for (uint32_t j = 0; j < p.nblocks; j++) {  // (every thread walks the few words: uniform)
+            blocks_ok = blocks_ok && block_status[4 * (size_t)(p.first_block + j)] == 0;
+            bytes += block_status[4 * (size_t)(p.first_block + j) + 2];
+        }
+    }
+    uint64_t rows = 0;
+    const bool fits = blocks_ok && raw_rows_from_bytes(RAW_COLS_D, bytes, &rows);
+    if (t == 0) worst = 0xFFFFFFFFu;
+    __syncthreads();
+    if (fits) {
+        const uint8_t* part = img + p.off;
+        auto bad = [&](uint64_t at, uint32_t code) { atomicMin(&worst, (uint32_t)(at << 4) | code); };  // (header places lie below 2^9)
+        if (t == 0) {
+            if (part[0] != RAW_NCOLS) bad(0, RAW_V_NCOLS);
+            uint64_t v = rows;
+            uint32_t i = 1;
+            for (; v >= 128; v >>= 7, i++)
+                if (part[i] != (uint8_t)(v | 128)) bad(i, RAW_V_ROWS);
+            if (part[i] != (uint8_t)v) bad(i, RAW_V_ROWS);
+        }
+        if (t < RAW_NCOLS) {
+            const RawColDef& d = RAW_COLS_D[t];
+            const uint8_t* h = part + raw_col_offset(RAW_COLS_D, rows, t);
+            // (a later column's header lies far up in the part: the COLUMN's index is reported as the place)
+            if (h[0] != d.name_len) bad(t, RAW_V_NAME);
+            else {
+                bool ok = true;
+                for (uint32_t i = 0; i < d.name_len; i++) ok = ok && h[1 + i] == (uint8_t)d.name[i];
+                if (!ok) bad(t, RAW_V_NAME);
+                else if (h[1 + d.name_len] != d.type_len) bad(t, RAW_V_TYPE);
+                else {
+                    for (uint32_t i = 0; i < d.type_len; i++) ok = ok && h[2 + d.name_len + i] == (uint8_t)d.type[i];
+                    if (!ok) bad(t, RAW_V_TYPE);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        RawPartVerdict v{rows, bytes, RAW_V_OK, 0};
+        if (!blocks_ok) v.code = RAW_V_BLOCK;
+        else if (!fits) v.code = RAW_V_SIZE;
+        else if (worst != 0xFFFFFFFFu) v.code = worst & 15, v.at = worst >> 4;
+        verdict[blockIdx.x] = v;
+    }
+}
+
+// raw_unpack_kernel: the inverse of raw_gather_kernel.  Rows [r0, r0 + m) of ONE part become fa_columns arrays (dst[c]: where
+// the range's first element of column c goes: naturally aligned, at any element of its array).  Date is skipped (the grid's y
+// runs over columns 1 .. 15), TimeReceived and TimeFlowStart widen from 4 to 8 bytes (t32 zero-extended); status is zeroed by the
+// host (a memset on the same stream).
+// A column's source starts at ANY byte phase of the image, and the phase changes with `rows`.  The kernel's wide accesses are all
+// naturally aligned: thread k of a column owns the k-th 16-byte-ALIGNED chunk of the destination range, loads the one or two
+// ALIGNED 16-byte words that cover the chunk's source bytes (16 of them; 8 for a widened column), shifts them by the source's byte
+// phase - the same for every chunk of the column (bytes16_at_phase) - and issues ONE aligned 16-byte store.  Only a chunk the
+// range covers partly (its first and last), and a chunk whose aligned loads would leave the part's span [lo, hi), go byte by byte:
+// single-byte loads in a loop that is not unrolled, so that the compiler cannot merge them into a wider load at the bytes' phase,
+// and byte stores (8-byte stores for a widened column, whose elements are 8-byte aligned).  Nothing is read outside [lo, hi),
+// nothing is written outside the m elements.
+struct RawUnpackArgs {
+    const uint8_t* part;     // the part's first byte
+    const uint8_t *lo, *hi;  // the part's span: part .. part + bytes
+    void* dst[RAW_NCOLS];
+    uint32_t rows, r0, m;
+};
+__global__ __launch_bounds__(RAW_BLOCK) void raw_unpack_kernel(const RawUnpackArgs a) {
+    const uint32_t c = blockIdx.y + 1;  // (Date is skipped)
+    const RawColDef& d = RAW_COLS_D[c];
+    const uint32_t w = d.width;
+    const bool widen = d.kind == RAW_K_KEY || d.kind == RAW_K_NARROW64;
+    uint8_t* const d0 = (uint8_t*)a.dst[c];
+    uint8_t* const d1 = d0 + (uint64_t)a.m * (widen ? 8 : w);  // the destination range [d0, d1)
+    uint8_t* const t = d0 - ((uintptr_t)d0 & 15) + 16 * ((uint64_t)blockIdx.x * RAW_BLOCK + threadIdx.x);  // this thread's aligned chunk
+    if (t >= d1) return;
+    const uint8_t* const s0 = a.part + raw_col_offset(RAW_COLS_D, a.rows, c) + raw_col_header_len(d) + (uint64_t)a.r0 * w;
+    const bool whole = t >= d0 && t + 16 <= d1;
+    // the chunk's source bytes: 16, or the 8 of its two elements ((t - d0) is a multiple of 8 there; in front of s0 where t < d0: not read)
+    const uint32_t nsrc = widen ? 8 : 16;
+    const uint8_t* s = s0 + (widen ? (t - d0) / 2 : (t - d0));
+    const uint32_t sh = (uint32_t)((uintptr_t)s & 15);
+    const uint8_t* al = s - sh;
+    const bool two = sh + nsrc > 16;  // the bytes reach into the next aligned word
+    if (whole && al >= a.lo && al + (two ? 32 : 16) <= a.hi) {
+        const uint4 x = *(const uint4*)al;
+        const uint4 y = two ? *(const uint4*)(al + 16) : make_uint4(0, 0, 0, 0);
+        const uint4 o = bytes16_at_phase(x, y, sh);
+        *(uint4*)t = widen ? make_uint4(o.x, 0u, o.y, 0u) : o;
+        return;
+    }
+    // (one single-byte load per trip of a loop that is NOT unrolled: unrolled, the compiler merges neighbouring byte loads into
+    // one wider load at the bytes' phase)
+    if (!widen) {
+#pragma nounroll
+        for (int i = 0; i < 16; i++)
+            if (t + i >= d0 && t + i < d1) t[i] = s[i];
+    } else {
+        uint32_t v = 0;
+#pragma nounroll
+        for (int i = 0; i < 8; i++)
+            if (t + 2 * (i & 4) >= d0 && t + 2 * (i & 4) < d1) {  // element i / 4 of the chunk lies in the range
+                v |= (uint32_t)s[i] << (8 * (i & 3));
+                if ((i & 3) == 3) *(uint64_t*)(t + 2 * (i & 4)) = v, v = 0;
+            }
     }
 }
 

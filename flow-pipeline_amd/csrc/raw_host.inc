@@ -338,6 +338,7 @@ extern "C" int fa_raw_reset(fa_ctx* c) {
     t->img.reset();
     t->scratch.reset();
     lz4_release(c);
+    load_release(c);
     return FA_OK;
 }
 

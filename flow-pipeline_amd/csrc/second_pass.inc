@@ -6,6 +6,23 @@
 // its columns handed to every enabled fold, all on the ctx stream behind the launches of the ingest itself (ingest_device_any).
 // A chunk is as long as the smallest cap of the enabled folds allows (and max_batch_records); a ctx with one fold runs what it
 // ran when that fold had the pass alone.  The raw builder comes last: it waits for the stream once per chunk (raw_host.inc).
+
+// One chunk's columns -> the enabled talker and port folds (m at most their chunk caps).  Shared by the second pass and by
+// fa_raw_load (raw_load_host.inc), whose columns come out of a loaded part instead of a decode.
+static int fold_chunk_cols(fa_ctx* c, const fa_columns& cols, size_t m) {
+    if (c->talk) {
+        const TalkCols p{cols.src_addr, cols.dst_addr, cols.etype, cols.bytes, cols.sampling_rate, cols.status, cols.time_flow_start};
+        int rc = talk_fold_cols(c, p, m);
+        if (rc) return rc;
+    }
+    if (c->ports) {
+        const PortCols p{cols.src_port, cols.dst_port, cols.bytes, cols.sampling_rate, cols.time_flow_start, cols.status};
+        int rc = port_fold_cols(c, p, m);
+        if (rc) return rc;
+    }
+    return FA_OK;
+}
+
 static int second_pass_records(fa_ctx* c, const void* d_buf, size_t len, const uint32_t* d_off, size_t n) {
     for (size_t i = 0; i < n;) {
         size_t m = std::min(n - i, (size_t)c->cfg.max_batch_records);
@@ -15,16 +32,8 @@ static int second_pass_records(fa_ctx* c, const void* d_buf, size_t len, const u
         fa_columns cols;
         int rc = decode_device_records(c, d_buf, len, (size_t)((double)len * (double)m / (double)n), d_off + i, m, &cols);
         if (rc) return rc;
-        if (c->talk) {
-            const TalkCols p{cols.src_addr, cols.dst_addr, cols.etype, cols.bytes, cols.sampling_rate, cols.status, cols.time_flow_start};
-            rc = talk_fold_cols(c, p, m);
-            if (rc) return rc;
-        }
-        if (c->ports) {
-            const PortCols p{cols.src_port, cols.dst_port, cols.bytes, cols.sampling_rate, cols.time_flow_start, cols.status};
-            rc = port_fold_cols(c, p, m);
-            if (rc) return rc;
-        }
+        rc = fold_chunk_cols(c, cols, m);
+        if (rc) return rc;
         if (c->raw) {
             rc = raw_build_cols(c, cols, m);
             if (rc) return rc;

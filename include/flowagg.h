@@ -635,6 +635,65 @@ size_t fa_lz4_frame_bound(size_t n);
 /* The counters of this ctx's compressions; works on any ctx (all zero before the first compression). */
 int fa_raw_lz4_stats(fa_ctx*, fa_raw_lz4_stats_t* out);
 
+/* ---- ABI 8, addition: loading flows_raw parts ------------------------------------- */
+/* The inverse of the two sections above: parts that fa_raw_take / fa_raw_take_lz4 delivered (a file written from them, say) are
+ * decoded and read ON THE DEVICE and folded into the ctx's talker and port tables - the state that answers the ranged panels and
+ * lives in HBM only - without re-consuming the wire bytes.  `bytes` (HOST memory) is either a concatenation of LZ4 frames of
+ * the form above, one part per frame, or a concatenation of plain Native parts; the two are told apart by the first four bytes
+ * (a flows_raw block starts with 0x10).  One call: the host walks the frames (one size word per 64 KiB block), ONE copy brings
+ * the bytes to HBM, lz4_decode_kernel (csrc/lz4_decode.cuh, one wave per block) decodes every block into a 64 KiB slot,
+ * raw_header_check_kernel derives every part's rows from its size and compares its 16 column headers, ONE copy and ONE
+ * synchronisation bring every block's and part's verdict back, and only then raw_unpack_kernel turns the parts into column
+ * arrays, a chunk at a time, which the folds read through the doors the ingest's second pass uses.
+ * Anything else is FA_ERR_FRAMING with the reason and the byte position in fa_last_error: what spill.lz4_frames_decode refuses
+ * (no magic, a skippable frame, a wrong version or header checksum, linked blocks, block or content checksums, a content size, a
+ * dictionary id, a block above the maximum, a missing EndMark, a truncated block), a block of more than 65536 bytes, a block
+ * that breaks the block format (a token, length byte or offset behind its end, literals past its end, offset 0 or past the
+ * bytes decoded, more than 65536 decoded bytes, a last sequence with a match length), a block that is not the last of its frame
+ * and does not decode to exactly 65536 bytes; a part whose size fits no row count, whose column count, names or types differ, or
+ * that is followed by bytes that are no part.  A REFUSED CALL FOLDS NOTHING - every frame, block and header of the call is
+ * validated before the first fold is launched - and the ctx stays usable.
+ * NOT inspected: the column VALUES (that Date matches TimeReceived, that TimeReceived is sorted).  NOT fed: loading never builds
+ * parts again (a ctx with fa_raw_enable gets no pending part from a load) and never touches flows_5m, the wide table or the
+ * sketches - those are fed from wire bytes only; the minute series from parts is a follow-up.
+ * Memory, allocated on first use, kept until fa_raw_load_reset / fa_raw_reset / fa_destroy: the compressed copy, 64 KiB per block of decoded image,
+ * one chunk of columns (117 bytes per row).  FA_ERR_NOMEM leaves the ctx usable; a caller with a large file loads it in
+ * pieces cut at frame boundaries. */
+typedef struct {
+    uint64_t offset, bytes; /* one frame's decoded bytes inside *d_out; offset is a multiple of 65536 */
+} fa_lz4_span;
+typedef struct {
+    uint64_t calls;                   /* fa_lz4_decode_device + fa_raw_columns_device + fa_raw_load calls that succeeded */
+    uint64_t frames, blocks, stored_blocks;
+    uint64_t bytes_in, bytes_decoded; /* input bytes (plain parts included); bytes that left lz4_decode_kernel */
+    uint64_t parts, rows_loaded;      /* parts unpacked; rows handed to the folds by fa_raw_load */
+    uint64_t launches;                /* kernel launches queued: decode, header check, unpack (the folds count their own) */
+    uint64_t decode_ns, unpack_ns, fold_ns; /* hipEvent times of lz4_decode_kernel, raw_unpack_kernel, the fold launches */
+} fa_raw_load_stats_t;
+/* Host only, no ctx: the C twin of spill.lz4_frames_decode over the step function the kernel runs (lz4_seq_parse).  A
+ * concatenation of frames -> their decoded bytes.  FA_ERR_FRAMING for what is listed above; FA_ERR_CAPACITY (and the size
+ * needed in *bytes_out) when cap is too small. */
+int fa_lz4_decode(const uint8_t* in, size_t n, uint8_t* out, size_t cap, size_t* bytes_out);
+/* Frames in HOST memory -> decoded bytes in HBM (*d_out: DEVICE pointer, owned by the ctx, valid until its next load, lz4 or raw
+ * call), spans[f] = where frame f's bytes lie.  FA_ERR_CAPACITY (*n_frames = needed) when spans_cap is too small: the host's
+ * frame walk finds that before anything is copied, decoded or counted.  n == 0
+ * gives zero frames.  Synchronous.  Works on any ctx. */
+int fa_lz4_decode_device(fa_ctx*, const uint8_t* in, size_t n, const void** d_out, fa_lz4_span* spans, size_t spans_cap, size_t* n_frames);
+/* Every part of the input unpacked into ONE column block (parts in input order, status 0 for every row, the two times
+ * zero-extended from 32 bits); no fold.  The block is owned by the ctx and valid until its next decode or load call.  More
+ * than 2^24 rows in total is FA_ERR_ARG.  Synchronous.  Works on any ctx. */
+int fa_raw_columns_device(fa_ctx*, const uint8_t* bytes, size_t n, fa_columns* out, size_t* rows_out);
+/* Every part of the input folded into every enabled fold of the ctx - the talkers, plain or bucketed, and the bucketed ports -
+ * in chunks of at most the folds' chunk caps.  FA_ERR_UNSUPPORTED if neither fold is enabled.  Sums commute: a load on top of
+ * ingested state adds to it.  Synchronous. */
+int fa_raw_load(fa_ctx*, const uint8_t* bytes, size_t n);
+/* The counters of this ctx's decodes and loads; works on any ctx (all zero before the first). */
+int fa_raw_load_stats(fa_ctx*, fa_raw_load_stats_t* out);
+/* Releases the buffers of the doors above (the input's copy, the decoded image, the column chunk) and of the LZ4 compressions; the
+ * counters go on counting.  Works on any ctx - fa_raw_reset does the same but needs fa_raw_enable, which a ctx that only loads
+ * does not have.  Pointers the doors returned are invalid afterwards. */
+int fa_raw_load_reset(fa_ctx*);
+
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
  *   if(EType = 0x800, IPv4NumToString(reinterpretAsUInt32(substring(reverse(Addr), 13, 4))), IPv6NumToString(Addr))
