@@ -34,6 +34,7 @@
 #include "lz4.cuh"
 #include "lz4_decode.cuh"
 #include "raw.cuh"
+#include "table_room.h"
 
 using namespace fa;
 
@@ -590,6 +591,7 @@ static bool bucket_range(const fa_ctx* c, uint32_t timeslot, uint32_t& lo, uint3
 
 #include "rows_host.inc"
 #include "group_host.inc"
+#include "keytab_host.inc"
 #include "talkers_host.inc"
 #include "ports_host.inc"
 #include "raw_host.inc"

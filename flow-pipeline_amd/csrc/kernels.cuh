@@ -21,6 +21,7 @@
 //   merge.cuh     window close in HBM: rows collected, sorted over the key bits that differ (rowplan.cuh), equal keys summed,
 //                 emit order; hash partition of a row set for the multi-GPU close (row_partition_kernel);
 //   talkers.cuh   exact GROUP BY SrcAddr / DstAddr (opt-in second pass): the decoded columns folded into two tables of their own;
+//   ports.cuh     exact GROUP BY SrcPort / DstPort per time bucket, the same way; keytab.cuh is the table core under both;
 //   maintenance.cuh  table scans, rebuilds, the wide log's reads / folds / drops (wdrop_kernel: a close zeroes sums in place).
 //
 // Roofline: HBM-bound integer/byte work; algorithmic bytes = wire bytes, read

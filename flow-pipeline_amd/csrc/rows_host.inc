@@ -30,7 +30,7 @@ static_assert(sizeof(RowOps<RK_PORT_SRC>::Row) == sizeof(RowW) && sizeof(RowOps<
 static_assert(sizeof(RowOps<RK_TOPK_SRC>::Row) == sizeof(TopkRow) && sizeof(TopkRow) == 24, "row layout");
 static_assert(sizeof(RowOps<RK_TALKERS_SRC>::Row) == sizeof(TalkRow) && sizeof(TalkRow) == sizeof(fa_talker_row) && sizeof(TalkRow) == 40, "row layout");
 static_assert(RowOps<RK_TALKERS_SRC>::NK2 <= RP_MAX_WORDS, "emit words");
-// The talker kinds' emit order: the first `need` of n rows (device memory) by fa_top_talkers' own four full-width sorts, in the
+// The talker kinds' emit order, and fa_top_talkers': the first `need` of n rows (device memory) by four full-width sorts, in the
 // talker state's scratch (talkers_host.inc).  The packed emit sort below returned rows out of order on sets of a million talker
 // rows (DESIGN.md 3.7); these four sorts never did.
 static int talk_order_rows(fa_ctx* c, hipStream_t stream, const TalkRow* rows, uint32_t n, size_t need, TalkRow* out);
@@ -423,7 +423,8 @@ static int rows_merge(fa_ctx* c, hipStream_t stream, ReadClock& clk, int kind, c
     return known ? rc : fail(c, FA_ERR_ARG, "unknown row kind");
 }
 
-// the talker kinds live in talkers_host.inc (TalkState): is the state there, its collector, and its row buffer
+// the talker kinds live in talkers_host.inc (TalkState, a TabPair of keytab_host.inc): is the state there, its collector, and its
+// row buffer
 static bool is_talker_kind(int kind) { return kind == RK_TALKERS_SRC || kind == RK_TALKERS_DST; }
 static const char TALK_OFF[] = "top talkers are not enabled on this ctx (fa_talkers_enable)";
 static const char TALK_NOT_CANONICAL[] = "fa_merge_talkers: a row is not canonical (etype 0 or 0x800; bytes 4..15 zero under 0x800)";

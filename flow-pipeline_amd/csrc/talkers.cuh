@@ -8,25 +8,13 @@
 // The same 16 bytes under the two families are two groups: a dotted quad is never an IPv6NumToString output.
 // value = sum(Bytes * SamplingRate) mod 2^64 and count(); a group of weight 0 is still a row.
 //
-// State: two open-addressed tables of their own (SrcAddr, DstAddr) - never the ctx's wide table.  Slot = one 64-byte line:
-// three key words + weight + count.  Every key word has bit 63 set, so 0 is EMPTY for each; a slot is claimed word by
-// word with 64-bit CAS in the order w0..w2 (the argument of wide.cuh: a word is written once, a contender that loses
-// word j leaves the slot, so the lane that wins w2 matched w0 and w1).  Probing is linear over the WHOLE table and has
-// no limit: the host keeps the load at or below 1/2 before every launch (talkers_host.inc), so a probe sequence ends
-// and no update is ever parked or lost.
+// State: two keyed tables of their own (SrcAddr, DstAddr) - never the ctx's wide table - under the traits TalkTab: the slot claim,
+// the LDS cache, growth, the buckets held and every invariant are keytab.cuh's, the capacity rule is table_room.h's.  Slot = one
+// 64-byte line: three key words + weight + count; every key word has bit 63 set, so 0 is EMPTY for each.
 //
 // talker_fold_kernel, the hot part: one lane per record of the decoded columns (six of them, 53 bytes per record), both
-// tables in one pass.  A workgroup-private LDS cache of (key, family) -> (weight, count) per direction absorbs repeats -
-// mocker-shaped and Zipf streams would otherwise put millions of same-address atomics on a handful of L2 lines (why the
-// ingest kernel has its hot-address cache and LdsMinutes).  An entry's key is three words too, claimed word by word with
-// LDS CAS; a lane that loses a word tries the next entry (TALK_LDS_PROBES of them), then goes straight to the global
-// table.  The cache is cleared at the start and flushed at the end, one global upsert per occupied entry.
-//
-// Invariants:
-//   - an LDS entry or a global slot only ever holds ONE key (write-once words, claimed in order);
-//   - every (record, direction) update is applied exactly once: to the cache (and from there once by the flush) or to
-//     the global table, never both;
-//   - u64 wrap-around adds commute: any order of updates, chunks, growths and merges gives bit-identical sums.
+// tables in one pass; mocker-shaped and Zipf streams are what the LDS cache is for (why the ingest kernel has its
+// hot-address cache and LdsMinutes).
 //
 // Sizes (reasoned, not yet measured on hardware - DESIGN.md 3.7): 512 threads and 512 entries per direction = 40 KiB of LDS per
 // workgroup, two workgroups per CU = 16 waves per CU behind the random-access latency of the global upserts, half of
@@ -37,6 +25,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "keytab.cuh"
 #include "table.cuh"
 
 namespace fa {
@@ -113,44 +102,6 @@ struct TalkRow {
 };
 static_assert(sizeof(TalkRow) == 40, "fa_talker_row");
 
-// Adds (w, cnt) to k's slot of table `d`, claiming one if the key is new.  Stale plain reads (per-XCD L2s are not
-// coherent) can only show EMPTY or the final word - never a false match; an EMPTY that is stale is settled by the CAS.
-// created: the lane's count of keys it created (talk_count_created adds the wave's sum to TalkCounters::used).
-__device__ __forceinline__ void talk_upsert(TSlot* tab, uint32_t mask, const TKey& k, uint32_t h, uint64_t w, uint64_t cnt, TalkCounters* ctr, uint32_t& created) {
-    uint32_t i = h & mask;
-    // (the bound is the table itself: with the load at or below 1/2 an EMPTY slot is met long before it)
-    for (uint32_t probe = 0; probe <= mask; probe++, i = (i + 1u) & mask) {
-        TSlot* s = &tab[i];
-        const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(&s->w[0]);
-        unsigned long long c[3] = {k01.x, k01.y, s->w[2]};
-        bool mine = true;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            if (!mine) break;
-            if (c[j] == 0) {
-                c[j] = atomicCAS(&s->w[j], 0ull, k.w[j]);
-                if (c[j] == 0) {
-                    c[j] = k.w[j];
-                    if (j == 2) created++;  // this lane created the group
-                }
-            }
-            mine = c[j] == k.w[j];
-        }
-        if (mine) {
-            if (w) atomicAdd(&s->weight, (unsigned long long)w);
-            atomicAdd(&s->count, (unsigned long long)cnt);
-            return;
-        }
-    }
-    atomicAdd(&ctr->lost, 1ull);
-}
-
-// (all lanes of the wave: after the kernel's loop)
-__device__ __forceinline__ void talk_count_created(unsigned long long* used, uint32_t created) {
-    const uint64_t s = wave_sum_u64(created);
-    if (__lane_id() == 0 && s) atomicAdd(used, (unsigned long long)s);
-}
-
 constexpr int TALK_BLOCK = 512;
 #ifndef FA_TALK_LDS_ENTRIES
 #define FA_TALK_LDS_ENTRIES 512
@@ -160,35 +111,18 @@ constexpr int TALK_LDS_PROBES = 4;
 constexpr int TALK_WG_PER_CU = 2;
 static_assert((TALK_LDS_ENTRIES & (TALK_LDS_ENTRIES - 1)) == 0, "the cache is indexed by hash bits");
 
-struct TalkLds {
-    unsigned long long k0[2][TALK_LDS_ENTRIES], k1[2][TALK_LDS_ENTRIES], k2[2][TALK_LDS_ENTRIES];
-    unsigned long long w[2][TALK_LDS_ENTRIES], c[2][TALK_LDS_ENTRIES];
-    unsigned long long absorbed, folded, created[2];
+struct TalkTab {
+    using Slot = TSlot;
+    using Key = TKey;
+    using Counters = TalkCounters;
+    static constexpr int NW = 3, NT = 1;
+    static constexpr int BLOCK = TALK_BLOCK, LDS_ENTRIES = TALK_LDS_ENTRIES, LDS_PROBES = TALK_LDS_PROBES;
+    static constexpr int WG_PER_CU = TALK_WG_PER_CU;
+    static constexpr char NOUN[] = "talker", FN[] = "fa_talkers", WGPC_ENV[] = "FA_TALK_WGPC";
+    __host__ __device__ static uint32_t hash(const TKey& k) { return tkey_hash(k); }
+    __host__ __device__ static uint32_t bucket(const unsigned long long w[3]) { return tkey_bucket(w); }
+    __device__ static void tally(const TKey&, uint32_t (&n)[1]) { n[0]++; }
 };
-
-// one key word of an entry: EMPTY is claimed, then it must be ours.  (A plain read that shows a word is final.)
-__device__ __forceinline__ bool talk_lds_word(unsigned long long* p, unsigned long long want) {
-    unsigned long long cur = *p;
-    if (cur == 0) {
-        cur = atomicCAS(p, 0ull, want);
-        if (cur == 0) cur = want;
-    }
-    return cur == want;
-}
-// true = absorbed by the workgroup's cache
-__device__ __forceinline__ bool talk_lds_add(TalkLds& L, int d, const TKey& k, uint32_t h, uint64_t w) {
-    uint32_t i = (h >> 9) & (TALK_LDS_ENTRIES - 1);
-#pragma unroll 1
-    for (int probe = 0; probe < TALK_LDS_PROBES; probe++, i = (i + 1u) & (TALK_LDS_ENTRIES - 1)) {
-        if (!talk_lds_word(&L.k0[d][i], k.w[0])) continue;
-        if (!talk_lds_word(&L.k1[d][i], k.w[1])) continue;
-        if (!talk_lds_word(&L.k2[d][i], k.w[2])) continue;
-        if (w) atomicAdd(&L.w[d][i], (unsigned long long)w);
-        atomicAdd(&L.c[d][i], 1ull);  // (count even when the weight is 0)
-        return true;
-    }
-    return false;
-}
 
 struct TalkFoldArgs {
     const uint4* src_addr;
@@ -211,17 +145,9 @@ struct TalkFoldArgs {
 // upserts bound this kernel, not its ALU.  Everything behind the pack works on the three key words and is shared.
 template <bool BUCKETED>
 __global__ __launch_bounds__(TALK_BLOCK) void talker_fold_kernel(TalkFoldArgs a) {
-    __shared__ TalkLds L;
-    for (int i = threadIdx.x; i < 2 * TALK_LDS_ENTRIES; i += TALK_BLOCK) {
-        (&L.k0[0][0])[i] = 0;
-        (&L.k1[0][0])[i] = 0;
-        (&L.k2[0][0])[i] = 0;
-        (&L.w[0][0])[i] = 0;
-        (&L.c[0][0])[i] = 0;
-    }
-    if (threadIdx.x == 0) L.absorbed = L.folded = L.created[0] = L.created[1] = 0;
-    __syncthreads();
-    uint32_t absorbed = 0, folded = 0, created[2] = {0, 0};
+    __shared__ TabLds<TalkTab> L;
+    tab_lds_clear(L);
+    uint32_t absorbed = 0, folded = 0, created[2][1] = {};
     for (uint64_t i = (uint64_t)blockIdx.x * TALK_BLOCK + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * TALK_BLOCK) {
         if (a.status[i]) continue;  // malformed: dropped, whatever the other columns hold
         folded++;
@@ -238,88 +164,30 @@ __global__ __launch_bounds__(TALK_BLOCK) void talker_fold_kernel(TalkFoldArgs a)
             if (BUCKETED) tkey_pack_bucket(lo, hi, fam, bidx, k);
             else tkey_pack(lo, hi, fam, k);
             const uint32_t h = tkey_hash(k);
-            if (talk_lds_add(L, d, k, h, w)) absorbed++;
-            else talk_upsert(a.tab[d], a.mask[d], k, h, w, 1, a.ctr, created[d]);
+            if (tab_lds_add(L, d, k, h, w)) absorbed++;
+            else tab_upsert<TalkTab>(a.tab[d], a.mask[d], k, h, w, 1, a.ctr, created[d]);
         }
     }
-    const uint64_t wa = wave_sum_u64(absorbed), wf = wave_sum_u64(folded);
-    if (__lane_id() == 0) {
-        if (wa) atomicAdd(&L.absorbed, (unsigned long long)wa);
-        if (wf) atomicAdd(&L.folded, (unsigned long long)wf);
-    }
-    __syncthreads();
-    // flush: every occupied entry is complete by now (the lane that claimed w0 went on to w1 and w2, or met them claimed)
-    for (int e = threadIdx.x; e < 2 * TALK_LDS_ENTRIES; e += TALK_BLOCK) {
-        const int d = e / TALK_LDS_ENTRIES, j = e % TALK_LDS_ENTRIES;
-        if (L.k0[d][j] == 0) continue;
-        TKey k;
-        k.w[0] = L.k0[d][j];
-        k.w[1] = L.k1[d][j];
-        k.w[2] = L.k2[d][j];
-        talk_upsert(a.tab[d], a.mask[d], k, tkey_hash(k), L.w[d][j], L.c[d][j], a.ctr, created[d]);
-    }
-#pragma unroll
-    for (int d = 0; d < 2; d++) {
-        const uint64_t wc = wave_sum_u64(created[d]);
-        if (__lane_id() == 0 && wc) atomicAdd(&L.created[d], (unsigned long long)wc);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {  // one atomic per workgroup and counter
-        if (L.absorbed) atomicAdd(&a.ctr->absorbed, L.absorbed);
-        if (L.folded) atomicAdd(&a.ctr->folded, L.folded);
-        if (L.created[0]) atomicAdd(&a.ctr->used[0], L.created[0]);
-        if (L.created[1]) atomicAdd(&a.ctr->used[1], L.created[1]);
-    }
-}
-
-// Growth: every occupied slot of the old table is inserted again (key, weight, count) - the sums stay exact.
-// floor_index (fa_talkers_drop_before; 0 = keep everything): slots of a bucket index below it are left behind.
-__global__ __launch_bounds__(256) void talker_rehash_kernel(const TSlot* old_tab, uint64_t old_slots, TSlot* tab, uint32_t mask, TalkCounters* ctr, int d, uint32_t floor_index) {
-    uint32_t created = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_slots; i += (uint64_t)gridDim.x * blockDim.x) {
-        const TSlot* s = &old_tab[i];
-        if (s->w[0] == 0) continue;
-        TKey k;
-        k.w[0] = s->w[0];
-        k.w[1] = s->w[1];
-        k.w[2] = s->w[2];
-        if (tkey_bucket(k.w) < floor_index) continue;
-        talk_upsert(tab, mask, k, tkey_hash(k), s->weight, s->count, ctr, created);
-    }
-    talk_count_created(&ctr->used[d], created);
+    tab_lds_flush(L, a.tab, a.mask, a.ctr, absorbed, folded, created);
 }
 
 // fa_merge_talkers: canonical rows of another ctx.
 __global__ __launch_bounds__(256) void talker_merge_kernel(const TalkRow* rows, uint32_t n, TSlot* tab, uint32_t mask, TalkCounters* ctr, int d) {
-    uint32_t created = 0;
+    uint32_t created[1] = {0};
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         TKey k;
         tkey_pack(rows[i].key[0], rows[i].key[1], rows[i].etype, k);
-        talk_upsert(tab, mask, k, tkey_hash(k), rows[i].weight, rows[i].count, ctr, created);
+        tab_upsert<TalkTab>(tab, mask, k, tkey_hash(k), rows[i].weight, rows[i].count, ctr, created);
     }
-    talk_count_created(&ctr->used[d], created);
+    tab_count_created<TalkTab>(ctr, d, created);
 }
 
 // ---- read side: compaction, sort keys, emit ---------------------------------------------------------------------
-__global__ __launch_bounds__(256) void talker_collect_kernel(const TSlot* tab, uint64_t slots, TalkRow* rows, uint32_t cap, unsigned int* cursor) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * blockDim.x) {
-        const TSlot* s = &tab[i];
-        if (s->w[0] == 0) continue;
-        const unsigned int j = atomicAdd(cursor, 1u);
-        if (j >= cap) continue;  // (cannot happen: cap = the table's own count of occupied slots)
-        TalkRow r;
-        tkey_unpack(s->w, r.key[0], r.key[1], r.etype);
-        r.pad = 0;
-        r.weight = s->weight;
-        r.count = s->count;
-        rows[j] = r;
-    }
-}
 // The occupied slots as rows for the device-resident close (rows_host.inc, collect_talkers), unordered.  Shaped like
 // wextract_kernel (maintenance.cuh): a workgroup of 16 waves looks at TR_U x 1024 slots per round - every lane its own 64-byte
 // slot, three 16-byte loads, so a wave reads 64 whole lines - ballot and popcount give each row its place among the wave's,
-// and the workgroup takes the places of the round's rows with ONE returning atomic (talker_collect_kernel above: one per row,
-// all on one word).  cap = the table's own count of occupied slots; *cursor ends at the rows there were.
+// and the workgroup takes the places of the round's rows with ONE returning atomic.  cap = the table's own count of occupied
+// slots; *cursor ends at the rows there were.
 // RANGED (fa_talkers_range_rows_device, bucketed tables): only the slots whose bucket index lies in [index_lo, index_last]
 // (both inclusive: the last index of the axis has no successor in 32 bits) are kept; the row carries no bucket, so a key
 // held in several buckets leaves as several rows, which the merge behind the read folds.  cap = the table's count of
@@ -391,46 +259,6 @@ __global__ __launch_bounds__(TR_BLOCK) void talker_rows_kernel(const TSlot* tab,
             }
         }
         __syncthreads();  // (wave_total and wg_rows are rewritten by the next round)
-    }
-}
-// fa_talkers_buckets, shaped like timeslots_kernel (maintenance.cuh).  bits == nullptr: the smallest and largest bucket index of
-// the occupied slots into range[0..1] (one atomic pair per wave); else one bit per index of [lo, lo + nbits).
-__global__ __launch_bounds__(256) void talker_buckets_kernel(const TSlot* tab, uint64_t nslots, uint32_t lo, uint32_t nbits, unsigned int* bits, unsigned int* range) {
-    uint32_t mn = 0xffffffffu, mx = 0u;
-    bool any = false;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * blockDim.x) {
-        const ulonglong2 k = *reinterpret_cast<const ulonglong2*>(&tab[i].w[2]);  // {w2, pad0}
-        if (k.x == 0) continue;  // (w2 is the last word claimed: a slot whose w2 is set holds a whole key)
-        const uint32_t b = (uint32_t)(k.x >> TKEY_BUCKET_SHIFT);
-        if (bits) {
-            if (b - lo < nbits) atomicOr(&bits[(b - lo) >> 5], 1u << ((b - lo) & 31u));
-        } else {
-            any = true;
-            mn = min(mn, b);
-            mx = max(mx, b);
-        }
-    }
-    if (!bits) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn = min(mn, (uint32_t)__shfl_xor((int)mn, o));
-            mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
-        }
-        const bool wave_any = __builtin_amdgcn_ballot_w64(any) != 0ull;
-        if (__lane_id() == 0 && wave_any) {
-            atomicMin(&range[0], mn);
-            atomicMax(&range[1], mx);
-            range[2] = 1u;  // (a bucket was seen: index 0xFFFFFFFF is a bucket like any other)
-        }
-    }
-}
-// The bucket index of every occupied slot, compacted (fa_talkers_buckets when the indices span more than its bitmap).
-__global__ __launch_bounds__(256) void talker_bucket_list_kernel(const TSlot* tab, uint64_t nslots, uint32_t* out, uint32_t cap, unsigned int* cursor) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * blockDim.x) {
-        const unsigned long long w2 = tab[i].w[2];
-        if (w2 == 0) continue;
-        const unsigned int j = atomicAdd(cursor, 1u);
-        if (j < cap) out[j] = (uint32_t)(w2 >> TKEY_BUCKET_SHIFT);
     }
 }
 __device__ __forceinline__ unsigned long long talk_bswap64(unsigned long long v) { return __builtin_bswap64(v); }
