@@ -1,9 +1,10 @@
 // agg.cuh - aggregation of the scattered tuples: one workgroup per key partition, LDS hash table, one device-table
-// update per group.
+// update per group.  How the tuples' segments are laid out and walked: segwalk.cuh.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "segwalk.cuh"
 #include "sinks.cuh"
 
 namespace fa {
@@ -36,47 +37,8 @@ __device__ __forceinline__ bool agg_lds_upsert(AggTable& lt, uint64_t k0, uint64
     return false;
 }
 
-constexpr int AGG_MAX_NWG = 1536;  // segments per partition: one per wave-tile workgroup (<= 2 per CU)
-#ifndef FA_AGG_SU
-#define FA_AGG_SU 4
-#endif
-constexpr int AGG_SU = FA_AGG_SU;  // segments a wave reads at a time (16-byte loads in flight per lane, x2 buffers)
-constexpr int AGG_PAD = AGG_SU * 8;  // zero counts behind the last segment (the back pass reads 8 segments per load)
 constexpr int AGG_CH = 4;  // tuples of a batch that are hashed / probed together
-
-// 16-byte loads a lane has in flight per batch: AGG_SU wide tuples
-struct AggBatch {
-    uint4 t[AGG_SU];
-    uint32_t v;  // bit s = t[s] is a tuple of this lane (not a dummy load)
-};
-
-// issue the loads of lanes [0,64) of AGG_SU consecutive segments starting at w0.  The segment counts
-// come from LDS (pc, zero padded): a count read from global memory would put a full vmcnt drain between
-// consecutive tuple loads.
-// Front parts: chunk level j = 16-byte pieces [64j, 64j+64) of a segment, one segment per 64 lanes.
-// Back parts (a handful of tuples each): level j = pieces [8j, 8j+8) of the c tuples that end at the segment's
-// last slot, EIGHT segments per 64 lanes.  Loads are unconditional (lanes without a tuple re-read piece 0 of a
-// valid segment): with predicated loads the compiler cannot count what is in flight and drains everything
-// (vmcnt(0)) before the previous batch is consumed.
-template <bool BACK>
-__device__ __forceinline__ void agg_fetch(const KArgs& a, const uint4* pbase, const uint32_t* pc, uint32_t w0, uint32_t lane,
-                                          uint32_t j, AggBatch& b) {
-    constexpr uint32_t SEGS = BACK ? 8u : 1u, PER = 64u / SEGS;  // segments per load, lanes per segment
-    uint32_t idx[AGG_SU], seg[AGG_SU];
-    b.v = 0;
-#pragma unroll
-    for (int s = 0; s < AGG_SU; s++) {
-        seg[s] = w0 + (uint32_t)s * SEGS + (BACK ? lane / PER : 0u);
-        const uint32_t c = pc[min(seg[s], (uint32_t)(AGG_MAX_NWG + AGG_PAD - 1))];  // 0 past nwg
-        const uint32_t first = BACK ? a.capq - c : 0u;                     // first tuple of the part
-        const uint32_t q = first + PER * j + (BACK ? lane % PER : lane);  // tuple index inside the segment
-        const bool valid = q >= first && q < first + c;
-        b.v |= (valid ? 1u : 0u) << s;
-        idx[s] = valid ? q : 0u;
-    }
-#pragma unroll
-    for (int s = 0; s < AGG_SU; s++) b.t[s] = pbase[(size_t)min(seg[s], a.nwg - 1u) * a.capq + idx[s]];
-}
+typedef SegBatch<AGG_SU> AggBatch;  // AGG_SU wide tuples per lane
 
 // slow path for one tuple (wide form): probing LDS upsert, then the device-wide table
 __device__ __forceinline__ void agg_tuple(const KArgs& a, AggTable& lt, uint32_t tb_base, const uint4& t) {
@@ -175,8 +137,11 @@ __device__ __forceinline__ void agg_consume(const KArgs& a, AggTable& lt, uint32
 
 // wide (16-byte) tuples; compact ones go through agg8_kernel
 __global__ __launch_bounds__(AGG_BLOCK) void agg_kernel(KArgs a) {
+    constexpr uint32_t WAVES = AGG_BLOCK / 64;
     __shared__ AggTable lt;
-    __shared__ uint32_t pc[AGG_MAX_NWG + AGG_PAD];  // this partition's segment counts, zero padded
+    __shared__ uint32_t pc[SEG_COUNTS], pcb[SEG_COUNTS];  // front / back counts of this partition's segments, zero padded
+    __shared__ uint16_t flv[seg_groups<false, AGG_SU>()], blv[seg_groups<true, AGG_SU>()];  // levels per group of segments
+    __shared__ uint4 queues[WAVES * 64];  // per wave: tuples that need the probing path
     const uint32_t part = blockIdx.x;
     for (int i = threadIdx.x; i < AGG_SLOTS; i += AGG_BLOCK) {
         lt.k0[i] = 0;
@@ -184,75 +149,17 @@ __global__ __launch_bounds__(AGG_BLOCK) void agg_kernel(KArgs a) {
         lt.s1[i] = 0;
         lt.s2[i] = 0;
     }
-    __shared__ uint32_t pcb[AGG_MAX_NWG + AGG_PAD];  // ... and the counts of the segments' back parts
-    __shared__ uint4 queues[(AGG_BLOCK / 64) * 64];  // per wave: tuples that need the probing path
-    __shared__ uint32_t maxc_s[2];
-    if (threadIdx.x < 3) maxc_s[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t mymax = 0, mymaxb = 0, mysum = 0;
-    for (uint32_t i = threadIdx.x; i < AGG_MAX_NWG + AGG_PAD; i += AGG_BLOCK) {
-        const uint32_t c = i < a.nwg ? a.seg_counts[(size_t)part * a.nwg + i] : 0u;
-        const uint32_t cb = i < a.nwg ? a.seg_counts[((size_t)NPART_MAX + part) * a.nwg + i] : 0u;
-        pc[i] = c;
-        pcb[i] = cb;
-        mymax = max(mymax, c);
-        mymaxb = max(mymaxb, cb);
-        mysum += c + cb;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        mymax = max(mymax, (uint32_t)__shfl_xor((int)mymax, o));
-        mymaxb = max(mymaxb, (uint32_t)__shfl_xor((int)mymaxb, o));
-        mysum += (uint32_t)__shfl_xor((int)mysum, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicMax(&maxc_s[0], mymax);
-        atomicMax(&maxc_s[1], mymaxb);
-        if (mysum) atomicAdd(&maxc_s[2], mysum);
-    }
+    seg_counts_stage<AGG_BLOCK, false>(a.seg_counts + (size_t)part * a.nwg, a.seg_counts + ((size_t)NPART_MAX + part) * a.nwg, a.nwg, pc, pcb);
+    seg_levels<AGG_BLOCK, AGG_SU, 1>(pc, pcb, flv, blv);
     const uint32_t tb_base = a.ctr->tb_base;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    // (compact tuples: region and capq are even, so every segment starts on a 16-byte boundary)
     const uint4* pbase = a.seg + (size_t)part * a.region;
-    constexpr uint32_t SU = AGG_SU;
-    constexpr uint32_t STEP = (AGG_BLOCK / 64) * SU;
-    __syncthreads();  // table cleared, counts staged
-    const uint32_t maxc = maxc_s[0], maxcb = maxc_s[1];
+    __syncthreads();  // table cleared, counts and levels staged
     uint4* queue = queues + wave * 64;
     uint32_t qn = 0;  // wave-uniform
-    // software pipeline over this wave's segment groups: the next group's loads fly during the LDS work
-    // (every fetch is unconditional - clamped addresses, zero counts past the end - so that the compiler
-    // can count the loads in flight and wait for the older batch only)
-    // chunk levels: level j covers the 16-byte pieces [64j, 64j+64) of every segment
-    const uint32_t levels = (__builtin_amdgcn_readfirstlane(maxc) + 63u) / 64u;
-    for (uint32_t j = 0; j < levels; j++) {
-        AggBatch b0, b1;
-        uint32_t w0 = wave * SU;
-        agg_fetch<false>(a, pbase, pc, w0, lane, j, b0);
-        while (true) {
-            agg_fetch<false>(a, pbase, pc, w0 + STEP, lane, j, b1);
-            agg_consume(a, lt, tb_base, lane, b0, queue, qn);
-            agg_fetch<false>(a, pbase, pc, w0 + 2 * STEP, lane, j, b0);
-            agg_consume(a, lt, tb_base, lane, b1, queue, qn);
-            w0 += 2 * STEP;
-            if (w0 >= a.nwg) break;
-        }
-    }
-    // back parts: 8 tuples per segment and level
-    const uint32_t levels_b = (__builtin_amdgcn_readfirstlane(maxcb) + 7u) >> 3;
-    constexpr uint32_t STEP_B = STEP * 8u;
-    for (uint32_t j = 0; j < (maxcb ? levels_b : 0u); j++) {  // the back parts (single tuples and bin leftovers of the wave-tile kernel)
-        AggBatch b0, b1;
-        uint32_t w0 = wave * SU * 8u;
-        agg_fetch<true>(a, pbase, pcb, w0, lane, j, b0);
-        while (true) {
-            agg_fetch<true>(a, pbase, pcb, w0 + STEP_B, lane, j, b1);
-            agg_consume(a, lt, tb_base, lane, b0, queue, qn);
-            agg_fetch<true>(a, pbase, pcb, w0 + 2 * STEP_B, lane, j, b0);
-            agg_consume(a, lt, tb_base, lane, b1, queue, qn);
-            w0 += 2 * STEP_B;
-            if (w0 >= a.nwg) break;
-        }
-    }
+    auto consume = [&](const AggBatch& b) { agg_consume(a, lt, tb_base, lane, b, queue, qn); };
+    seg_walk<false, AGG_SU, 1>(a.capq, a.nwg, pbase, pc, flv, lane, wave, WAVES, consume);
+    seg_walk<true, AGG_SU, 1>(a.capq, a.nwg, pbase, pcb, blv, lane, wave, WAVES, consume);  // (single tuples and bin leftovers of the wave-tile kernel)
     agg_drain(a, lt, tb_base, lane, queue, qn);
     __syncthreads();
     // every group of this partition goes to the device-wide table once; quad-grouped: one atomic line
@@ -358,43 +265,14 @@ __device__ __forceinline__ bool agg8_upsert_owned(const KArgs& a, uint64_t k0, u
     return false;
 }
 
-#ifndef FA_AGG8_SU
-#define FA_AGG8_SU 2
-#endif
-#ifndef FA_CMS_SU
-#define FA_CMS_SU 4
-#endif
-constexpr int AGG8_SU = FA_AGG8_SU;        // 16-byte loads per lane and batch (x 2 tuples)
-constexpr int AGG8_NT = AGG8_SU * 2;
-constexpr int CMS_SU = FA_CMS_SU;          // cms_agg_kernel: segments per batch (see cms_fetch)
-template <int SU>
-struct Agg8BatchT {
-    uint4 t[SU];
-    uint32_t v;  // bit e: tuple e of this lane is real (e >> 1 = load, e & 1 = half)
-};
-typedef Agg8BatchT<AGG8_SU> Agg8Batch;
-// Loads of one work item.  Front: pieces [64j, 64j+64) of segment w0 + s, one segment per load.  Back: pieces
-// [8j, 8j+8) of the c tuples that end at the segment's last slot, eight segments per load (lane / 8).  Unconditional
-// (clamped addresses, zero counts past the end: see agg_fetch).
-template <bool BACK, int SU>
-__device__ __forceinline__ void agg8_fetch(uint32_t capq, uint32_t nwg, const uint4* pbase, const uint32_t* pc, uint32_t w0, uint32_t lane, uint32_t j,
-                                           Agg8BatchT<SU>& b) {
-    constexpr uint32_t SEGS = BACK ? 8u : 1u, PER = 64u / SEGS;
-    uint32_t idx[SU], seg[SU];
-    b.v = 0;
-#pragma unroll
-    for (int s = 0; s < SU; s++) {
-        seg[s] = w0 + (uint32_t)s * SEGS + (BACK ? lane / PER : 0u);
-        const uint32_t c = pc[min(seg[s], (uint32_t)(AGG_MAX_NWG + AGG_PAD - 1))];
-        const uint32_t first = BACK ? capq - c : 0u;
-        const uint32_t piece = first / 2u + PER * j + (BACK ? lane % PER : lane);
-        const uint32_t q = piece * 2u;
-        const uint32_t valid = ((q >= first && q < first + c) ? 1u : 0u) | ((q + 1u >= first && q + 1u < first + c) ? 2u : 0u);
-        b.v |= valid << (2 * s);
-        idx[s] = valid ? piece : 0u;
+constexpr int AGG8_NT = AGG8_SU * 2;  // tuples per lane and batch: tuple e = half e & 1 of load e >> 1
+typedef SegBatch<AGG8_SU> Agg8Batch;
+__device__ __forceinline__ void agg8_table_clear(Agg8Table& lt) {
+    for (int i = threadIdx.x; i < AGG8_ALL; i += AGG_BLOCK) {
+        lt.key[i] = 0;
+        lt.s1[i] = 0;
+        lt.s2[i] = 0;
     }
-#pragma unroll
-    for (int s = 0; s < SU; s++) b.t[s] = pbase[(size_t)min(seg[s], nwg - 1u) * (capq / 2u) + idx[s]];
 }
 __device__ __forceinline__ void agg8_drain(const KArgs& a, Agg8Table& lt, uint32_t tb_base, uint32_t part, uint32_t lane, const uint2* queue, uint32_t qn) {
     if (lane < qn) agg8_tuple(a, lt, tb_base, part, queue[lane]);
@@ -511,37 +389,19 @@ __device__ __forceinline__ void agg8_consume(const KArgs& a, Agg8Table& lt, uint
 
 __global__ __launch_bounds__(AGG_BLOCK) void agg8_kernel(KArgs a) {
     constexpr uint32_t WAVES = AGG_BLOCK / 64;
-    constexpr uint32_t FGRP = AGG8_SU, BGRP = AGG8_SU * 8;  // segments per work item: front, back
-    constexpr uint32_t NFG = (AGG_MAX_NWG + AGG_PAD) / FGRP, NBG = (AGG_MAX_NWG + AGG_PAD) / BGRP;
     __shared__ Agg8Table lt;
-    __shared__ uint32_t pc[AGG_MAX_NWG + AGG_PAD], pcb[AGG_MAX_NWG + AGG_PAD];  // front / back counts of this partition's segments, zero padded
-    __shared__ uint16_t flv[NFG], blv[NBG];  // levels each group of segments needs (so that a wave never walks empty levels)
+    __shared__ uint32_t pc[SEG_COUNTS], pcb[SEG_COUNTS];  // front / back counts of this partition's segments, zero padded
+    __shared__ uint16_t flv[seg_groups<false, AGG8_SU>()], blv[seg_groups<true, AGG8_SU>()];  // levels per group of segments
     __shared__ uint2 queues[WAVES * 64];
     const uint32_t part = blockIdx.x;
     const unsigned long long tk_start = FA_DBG(a, DBG_AGG8_TIMING) ? wall_clock64() : 0ull;
-    for (int i = threadIdx.x; i < AGG8_ALL; i += AGG_BLOCK) {
-        lt.key[i] = 0;
-        lt.s1[i] = 0;
-        lt.s2[i] = 0;
-    }
-    for (uint32_t i = threadIdx.x; i < AGG_MAX_NWG + AGG_PAD; i += AGG_BLOCK) {
-        pc[i] = i < a.nwg ? a.seg_counts[(size_t)part * a.nwg + i] : 0u;
-        pcb[i] = i < a.nwg ? a.seg_counts[((size_t)NPART_MAX + part) * a.nwg + i] : 0u;
-    }
+    agg8_table_clear(lt);
     const uint32_t tb_base = a.ctr->tb_base;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    // (region and capq are even: every segment starts on a 16-byte boundary)
     const uint4* pbase = a.seg + (((size_t)part * a.region) >> 1);
-    __syncthreads();
-    for (uint32_t g = threadIdx.x; g < NFG; g += AGG_BLOCK) {
-        uint32_t m = 0;
-        for (uint32_t s = 0; s < FGRP; s++) m = max(m, pc[g * FGRP + s]);
-        flv[g] = (uint16_t)((m + 127u) >> 7);  // 64 lanes x 2 tuples per level
-    }
-    for (uint32_t g = threadIdx.x; g < NBG; g += AGG_BLOCK) {
-        uint32_t m = 0;
-        for (uint32_t s = 0; s < BGRP; s++) m = max(m, pcb[g * BGRP + s]);
-        blv[g] = (uint16_t)(m ? (m / 2u + 1u + 7u) >> 3 : 0u);  // 8 pieces per segment and level; c tuples span up to c / 2 + 1 pieces
-    }
+    seg_counts_stage<AGG_BLOCK, false>(a.seg_counts + (size_t)part * a.nwg, a.seg_counts + ((size_t)NPART_MAX + part) * a.nwg, a.nwg, pc, pcb);
+    seg_levels<AGG_BLOCK, AGG8_SU, 2>(pc, pcb, flv, blv);
     __syncthreads();
     uint2* queue = queues + wave * 64;
     // Multi-pass form (a.agg_passes > 1, chosen by the host from the groups the previous launches produced): when a
@@ -556,37 +416,9 @@ __global__ __launch_bounds__(AGG_BLOCK) void agg8_kernel(KArgs a) {
     const unsigned long long tm0 = (FA_DBG(a, DBG_TIMING | DBG_AGG8_TIMING)) ? (FA_DBG(a, DBG_AGG8_TIMING) ? wall_clock64() : clock64()) : 0ull;
     uint32_t qn = 0;
     unsigned long long hk = 0ull;  // this wave's heavy key, once it has met one (agg8_consume)
-    // Work items of a wave: (group g, level j), g = wave, wave + WAVES, ...; j < levels(g).  The loads of the next item
-    // fly while the current one is consumed (two register buffers; every fetch is unconditional - an item past the end
-    // reads clamped addresses with zero counts).
-#define FA_AGG8_PASS(BACK, LV, NG, GSEGS, PCNT)                                                           \
-    {                                                                                                       \
-        const uint32_t ngroups = (a.nwg + (GSEGS) - 1u) / (GSEGS);                                           \
-        uint32_t g = wave, j = 0;                                                                           \
-        auto settle_item = [&]() {                                                                          \
-            while (g < ngroups && j >= (uint32_t)__builtin_amdgcn_readfirstlane((int)LV[min(g, (uint32_t)(NG) - 1u)])) { \
-                g += WAVES;                                                                                 \
-                j = 0;                                                                                      \
-            }                                                                                               \
-        };                                                                                                  \
-        settle_item();                                                                                      \
-        Agg8Batch b0, b1;                                                                                   \
-        agg8_fetch<BACK, AGG8_SU>(a.capq, a.nwg, pbase, PCNT, g * (GSEGS), lane, j, b0);                                          \
-        while (g < ngroups) {                                                                               \
-            j++;                                                                                            \
-            settle_item();                                                                                  \
-            agg8_fetch<BACK, AGG8_SU>(a.capq, a.nwg, pbase, PCNT, g * (GSEGS), lane, j, b1);                                      \
-            agg8_consume(a, lt, tb_base, part, lane, b0, queue, qn, pmask, pass, hk);                                       \
-            if (g >= ngroups) break;                                                                        \
-            j++;                                                                                            \
-            settle_item();                                                                                  \
-            agg8_fetch<BACK, AGG8_SU>(a.capq, a.nwg, pbase, PCNT, g * (GSEGS), lane, j, b0);                                      \
-            agg8_consume(a, lt, tb_base, part, lane, b1, queue, qn, pmask, pass, hk);                                       \
-        }                                                                                                   \
-    }
-    FA_AGG8_PASS(false, flv, NFG, FGRP, pc)
-    FA_AGG8_PASS(true, blv, NBG, BGRP, pcb)
-#undef FA_AGG8_PASS
+    auto consume = [&](const Agg8Batch& b) { agg8_consume(a, lt, tb_base, part, lane, b, queue, qn, pmask, pass, hk); };
+    seg_walk<false, AGG8_SU, 2>(a.capq, a.nwg, pbase, pc, flv, lane, wave, WAVES, consume);
+    seg_walk<true, AGG8_SU, 2>(a.capq, a.nwg, pbase, pcb, blv, lane, wave, WAVES, consume);
     agg8_drain(a, lt, tb_base, part, lane, queue, qn);
     __syncthreads();
     const unsigned long long tm1 = (FA_DBG(a, DBG_TIMING | DBG_AGG8_TIMING)) ? (FA_DBG(a, DBG_AGG8_TIMING) ? wall_clock64() : clock64()) : 0ull;
@@ -716,11 +548,7 @@ __global__ __launch_bounds__(AGG_BLOCK) void agg8_kernel(KArgs a) {
     }
     if (pass + 1 < npass) {  // next pass: empty table
         __syncthreads();
-        for (int i = threadIdx.x; i < AGG8_ALL; i += AGG_BLOCK) {
-            lt.key[i] = 0;
-            lt.s1[i] = 0;
-            lt.s2[i] = 0;
-        }
+        agg8_table_clear(lt);
         __syncthreads();
     }
     }
@@ -745,40 +573,15 @@ __global__ __launch_bounds__(AGG_BLOCK) void agg8_kernel(KArgs a) {
 // LDS adds, and the array is folded into copy 0 of the sketch with plain, coalesced 64-bit read-modify-writes (the
 // partition's `depth` blocks of 2^sub counters belong to this unit alone; slices of one partition use atomics; the
 // atomic paths of other kernels use the other copies).  One persistent workgroup per CU takes units heaviest first.
-// Segment geometry and walk: those of the wide (16-byte) flows_5m tuples, agg_fetch<BACK, false>.
-// Batches of CMS_SU segments (round 3 measured 8 against 4 - twice the loads in flight per wave: the segment walk of a
-// workgroup went from 41.6 to 44.7 us; it is not the latency of the loads that bounds it).
-constexpr int CMS_PAD = CMS_SU * 8;  // zero counts behind the last segment (the back pass reads 8 segments per load)
-struct CmsBatch {
-    uint4 t[CMS_SU];
-    uint32_t v;  // bit s = t[s] is a tuple of this lane (not a dummy load)
-};
-// agg_fetch<BACK, false> for batches of CMS_SU segments (same geometry, same unconditional loads)
-template <bool BACK>
-__device__ __forceinline__ void cms_fetch(const KArgs& a, const uint4* pbase, const uint32_t* pc, uint32_t w0, uint32_t lane, uint32_t j, CmsBatch& b) {
-    constexpr uint32_t SEGS = BACK ? 8u : 1u, PER = 64u / SEGS;
-    uint32_t idx[CMS_SU], seg[CMS_SU];
-    b.v = 0;
-#pragma unroll
-    for (int s = 0; s < CMS_SU; s++) {
-        seg[s] = w0 + (uint32_t)s * SEGS + (BACK ? lane / PER : 0u);
-        const uint32_t c = pc[min(seg[s], (uint32_t)(AGG_MAX_NWG + CMS_PAD - 1))];  // 0 past nwg
-        const uint32_t first = BACK ? a.capq - c : 0u;
-        const uint32_t piece = first + PER * j + (BACK ? lane % PER : lane);
-        const uint32_t valid = piece < first + c ? 1u : 0u;
-        b.v |= valid << s;
-        idx[s] = valid ? piece : 0u;
-    }
-#pragma unroll
-    for (int s = 0; s < CMS_SU; s++) b.t[s] = pbase[(size_t)min(seg[s], a.nwg - 1u) * a.capq + idx[s]];
-}
+// The segments hold one 16-byte tuple per piece, as the wide flows_5m tuples do, and are walked in batches of CMS_SU
+// (round 3 measured 8 against 4 - twice the loads in flight per wave: the segment walk of a workgroup went from 41.6 to
+// 44.7 us; it is not the latency of the loads that bounds it).
+typedef SegBatch<CMS_SU> CmsBatch;
 
 __global__ __launch_bounds__(AGG_BLOCK) void cms_agg_kernel(KArgs a, uint32_t set_mask, uint32_t cpar) {
     __shared__ unsigned long long arr[1u << CMS_PART_LOG2_MAX];  // 128 KiB
-    __shared__ uint32_t pc[AGG_MAX_NWG + CMS_PAD], pcb[AGG_MAX_NWG + CMS_PAD];
-    __shared__ uint32_t maxc_s[3];
-    constexpr uint32_t CNFG = (AGG_MAX_NWG + CMS_PAD) / CMS_SU, CNBG = (AGG_MAX_NWG + CMS_PAD) / (CMS_SU * 8);
-    __shared__ uint16_t flv[CNFG], blv[CNBG + 1];  // levels each group of segments needs: front parts, back parts
+    __shared__ uint32_t pc[SEG_COUNTS], pcb[SEG_COUNTS];  // front / back counts of the unit's segments, zero padded
+    __shared__ uint16_t flv[seg_groups<false, CMS_SU>()], blv[seg_groups<true, CMS_SU>()];  // levels per group of segments
     __shared__ uint32_t fold_scr[(AGG_BLOCK / 64) * 192];  // 768 bytes per wave: wave_fold_lds
     // Which (sketch, partition) this workgroup takes: the HEAVIEST first, and the heavy ones in SLICES.  A partition that
     // holds a heavy hitter's key gets 3-4x the mean number of tuples (every wave tile of the chip that is not served by
@@ -862,44 +665,11 @@ __global__ __launch_bounds__(AGG_BLOCK) void cms_agg_kernel(KArgs a, uint32_t se
     const uint32_t prefix = logical % CMS_NPART, part = set * CMS_NPART + prefix;
     const uint32_t sub = a.cms_sub, ncnt = a.cms_depth << sub;
     for (uint32_t i = threadIdx.x; i < ncnt; i += AGG_BLOCK) arr[i] = 0;
-    if (threadIdx.x < 3) maxc_s[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t mymax = 0, mymaxb = 0, mysum = 0;
-    for (uint32_t i = threadIdx.x; i < AGG_MAX_NWG + CMS_PAD; i += AGG_BLOCK) {
-        const uint32_t c = i < a.nwg ? a.cseg_counts[(size_t)part * a.nwg + i] : 0u;
-        const uint32_t cb = i < a.nwg ? a.cseg_counts[((size_t)CMS_SETS * CMS_NPART + part) * a.nwg + i] : 0u;
-        pc[i] = c;
-        pcb[i] = cb;
-        mymax = max(mymax, c);
-        mymaxb = max(mymaxb, cb);
-        mysum += c + cb;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        mymax = max(mymax, (uint32_t)__shfl_xor((int)mymax, o));
-        mymaxb = max(mymaxb, (uint32_t)__shfl_xor((int)mymaxb, o));
-        mysum += (uint32_t)__shfl_xor((int)mysum, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicMax(&maxc_s[0], mymax);
-        atomicMax(&maxc_s[1], mymaxb);
-        if (mysum) atomicAdd(&maxc_s[2], mysum);
-    }
     const uint4* pbase = a.cseg + (size_t)part * a.cregion;
-    KArgs g = a;  // (cms_fetch reads the segment geometry from capq / nwg)
-    g.capq = a.ccapq;
-    __syncthreads();
-    const uint32_t maxcb = maxc_s[1];
-    if (threadIdx.x == 0 && slice == 0u) a.cms_psize[(cpar ^ 1u) * (CMS_SETS * CMS_NPART) + logical] = maxc_s[2];  // (the next launch's schedule)
-    for (uint32_t gq = threadIdx.x; gq < CNFG; gq += AGG_BLOCK) {
-        uint32_t m = 0;
-        for (uint32_t q = 0; q < (uint32_t)CMS_SU; q++) m = max(m, pc[gq * CMS_SU + q]);
-        flv[gq] = (uint16_t)((m + 63u) >> 6);  // level j: tuples [64j, 64j+64) of a segment
-    }
-    for (uint32_t gq = threadIdx.x; gq < CNBG; gq += AGG_BLOCK) {
-        uint32_t m = 0;
-        for (uint32_t q = 0; q < (uint32_t)CMS_SU * 8u; q++) m = max(m, pcb[gq * CMS_SU * 8u + q]);
-        blv[gq] = (uint16_t)((m + 7u) >> 3);   // back parts: 8 tuples per segment and level
-    }
+    const uint32_t ptotal = seg_counts_stage<AGG_BLOCK, true>(a.cseg_counts + (size_t)part * a.nwg,
+                                                              a.cseg_counts + ((size_t)CMS_SETS * CMS_NPART + part) * a.nwg, a.nwg, pc, pcb);
+    if (threadIdx.x == 0 && slice == 0u) a.cms_psize[(cpar ^ 1u) * (CMS_SETS * CMS_NPART) + logical] = ptotal;  // (the next launch's schedule)
+    seg_levels<AGG_BLOCK, CMS_SU, 1>(pc, pcb, flv, blv);
     __syncthreads();
     // A heavy hitter sends one tuple per wave tile: a good part of every 64 consecutive tuples of its partition carries the
     // SAME key, and LDS atomics on one address serialize - across the lanes of a wave and across the 16 waves of the
@@ -925,45 +695,16 @@ __global__ __launch_bounds__(AGG_BLOCK) void cms_agg_kernel(KArgs a, uint32_t se
                 for (uint32_t r = 0; r < a.cms_depth; r++) atomicAdd(&arr[(r << sub) + cms_low(q.x, q.y, r, sub)], (unsigned long long)w);
         }
     };
-    // Work items of a wave: (group g of CMS_SU segments, level j), g = the wave's share of this slice's groups; j <
-    // levels(g) - a wave never walks the empty levels of short segments up to the partition's longest one (a heavy
-    // hitter's workgroup fills its segment of the key's partition 4-5x beyond the mean: round 2 walked every segment to
-    // that length).  The loads of the next item fly while the current one is consumed (two register buffers; every fetch
-    // is unconditional - an item past the end reads clamped addresses with zero counts).
-    // (Round 3 measured: items drawn one at a time from an LDS counter even the waves out - the slowest wave of a
-    // workgroup walks 1.2x the mean here - and the walk takes as long as before; so does a walk with the LDS adds
-    // removed (47.7 vs 52.7 us per unit) and one with twice the loads in flight.  What bounds it is the CU's share of the
-    // memory system: ~0.7 MB of 1-KiB pieces per unit.)
+    // This slice's groups are those = slice (mod nslice), dealt to the waves in turn.  (A heavy hitter's workgroup fills
+    // its segment of the key's partition 4-5x beyond the mean: round 2 walked every segment to that length, hence the
+    // levels per group.  Round 3 measured: items drawn one at a time from an LDS counter even the waves out - the slowest
+    // wave of a workgroup walks 1.2x the mean here - and the walk takes as long as before; so does a walk with the LDS
+    // adds removed (47.7 vs 52.7 us per unit) and one with twice the loads in flight.  What bounds it is the CU's share
+    // of the memory system: ~0.7 MB of 1-KiB pieces per unit.)
     constexpr uint32_t WAVES = AGG_BLOCK / 64;
-#define FA_CMS_PASS(BACK, LV, GSEGS, PCNT)                                                       \
-    {                                                                                              \
-        const uint32_t ngroups = (a.nwg + (GSEGS) - 1u) / (GSEGS);                                  \
-        uint32_t gi = wave * nslice + slice, j = 0;  /* this slice: groups = slice (mod nslice) */   \
-        auto settle_item = [&]() {                                                                 \
-            while (gi < ngroups && j >= (uint32_t)__builtin_amdgcn_readfirstlane((int)LV[gi])) {   \
-                gi += WAVES * nslice;                                                              \
-                j = 0;                                                                             \
-            }                                                                                      \
-        };                                                                                         \
-        settle_item();                                                                             \
-        CmsBatch b0, b1;                                                                           \
-        cms_fetch<BACK>(g, pbase, PCNT, gi * (GSEGS), lane, j, b0);                                \
-        while (gi < ngroups) {                                                                     \
-            j++;                                                                                   \
-            settle_item();                                                                         \
-            cms_fetch<BACK>(g, pbase, PCNT, gi * (GSEGS), lane, j, b1);                            \
-            consume(b0);                                                                           \
-            if (gi >= ngroups) break;                                                              \
-            j++;                                                                                   \
-            settle_item();                                                                         \
-            cms_fetch<BACK>(g, pbase, PCNT, gi * (GSEGS), lane, j, b0);                            \
-            consume(b1);                                                                           \
-        }                                                                                          \
-    }
     const unsigned long long tk1 = FA_DBG(a, DBG_CMS_TIMING) ? wall_clock64() : 0ull;
-    FA_CMS_PASS(false, flv, (uint32_t)CMS_SU, pc)
-    if (maxcb) FA_CMS_PASS(true, blv, (uint32_t)CMS_SU * 8u, pcb)
-#undef FA_CMS_PASS
+    seg_walk<false, CMS_SU, 1>(a.ccapq, a.nwg, pbase, pc, flv, lane, wave * nslice + slice, WAVES * nslice, consume);
+    seg_walk<true, CMS_SU, 1>(a.ccapq, a.nwg, pbase, pcb, blv, lane, wave * nslice + slice, WAVES * nslice, consume);
     if (FA_DBG(a, DBG_CMS_TIMING) && lane == 0) {
         __builtin_amdgcn_s_waitcnt(0);
         atomicAdd(&a.ctr->t_total, wall_clock64() - tk1);  // (sum over the waves: mean wave vs the workgroup's walk = imbalance)

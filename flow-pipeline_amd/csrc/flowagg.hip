@@ -324,7 +324,7 @@ static int grid_for(fa_ctx* c, K kernel, uint32_t n, uint32_t tile_recs) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, BLOCK, 0) != hipSuccess || per_cu < 1)
         per_cu = 2;
     if (c->wgpc_cap && (int)c->wgpc_cap < per_cu) per_cu = (int)c->wgpc_cap;
-    uint32_t g = std::min<uint32_t>((uint32_t)c->num_cus * (uint32_t)per_cu, AGG_MAX_NWG);
+    uint32_t g = std::min<uint32_t>((uint32_t)c->num_cus * (uint32_t)per_cu, SEG_MAX_NWG);
     return (int)std::max(1u, std::min(tiles, g));
 }
 
@@ -512,7 +512,8 @@ extern "C" void fa_destroy(fa_ctx* c) {
         if (hipMemcpy(cnt.data(), c->seg_counts, cnt.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
             unsigned long long front = 0, back = 0;
             for (size_t i = 0; i < cnt.size() / 2; i++) front += cnt[i], back += cnt[cnt.size() / 2 + i];
-            fprintf(stderr, "[flowagg] last launch's tuples: %llu in whole store units, %llu single (%.2f %%)\n", front, back, 100.0 * (double)back / (double)std::max(1ull, front + back));
+            fprintf(stderr, "[flowagg] last launch's tuples: %llu in whole store units, %llu single (%.2f %%), %u segments per partition\n", front, back,
+                    100.0 * (double)back / (double)std::max(1ull, front + back), c->last_nwg);
             // (layout [2][NPART_MAX][nwg]: balance over the key partitions - agg8_kernel runs one workgroup per partition)
             unsigned long long mx = 0;
             for (size_t p = 0; p < (size_t)NPART_MAX; p++) {

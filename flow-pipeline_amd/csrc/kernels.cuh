@@ -13,6 +13,8 @@
 //      aggregates them in an LDS hash table (two packed 64-bit LDS atomics per tuple) and adds each group to the
 //      device-wide table once - agg8_kernel with plain loads and stores: the partition owns the key's table region.
 //   cms_agg_kernel: Count-Min tuples per (sketch, slice) folded in a dense LDS array, plain read-modify-write.
+//   segwalk.cuh: what those three share - the geometry of a partition's tuple segments (front / back parts, levels,
+//      the piece a lane reads) and the double-buffered walk over them; each kernel supplies what it does with a batch.
 //   wagg_kernel: (SrcAddr,DstPort,Proto) tuples per region of the wide table, LDS dedup, plain loads and stores.
 //   Records the in-place parsers are not sure about go to deferred_kernel (parse_generic, complete semantics); values
 //   that do not fit a tuple take the direct device-wide-table path (64-bit atomics).
