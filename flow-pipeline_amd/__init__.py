@@ -123,6 +123,15 @@ class RawLoadStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RawMergeStats(C.Structure):
+    """fa_raw_merge_stats_t: what the ctx's merges of pending parts (raw_merge) have done so far."""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "merges", "parts_in", "parts_out", "rows", "bytes_in", "bytes_out", "launches", "order_ns", "gather_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 LZ4_SPAN_DTYPE = np.dtype([("offset", "<u8"), ("bytes", "<u8")])  # fa_lz4_span
 
 
@@ -200,7 +209,7 @@ EXPORTS = [
     "fa_ports_enable_buckets", "fa_ports_fold_columns_device", "fa_top_ports_range", "fa_ports_range_rows_device", "fa_ports_buckets",
     "fa_ports_drop_before", "fa_ports_reset", "fa_ports_stats", "fa_group_top_ports_range",
     "fa_raw_part_bytes", "fa_flow_rows_to_native", "fa_raw_enable", "fa_raw_build_columns_device", "fa_raw_take", "fa_raw_take_device",
-    "fa_raw_reset", "fa_raw_stats",
+    "fa_raw_reset", "fa_raw_stats", "fa_raw_merge", "fa_raw_merge_stats",
     "fa_raw_take_lz4", "fa_raw_take_lz4_device", "fa_lz4_frame_device", "fa_lz4_frame", "fa_lz4_frame_bound", "fa_raw_lz4_stats",
     "fa_lz4_decode", "fa_lz4_decode_device", "fa_raw_columns_device", "fa_raw_load", "fa_raw_load_stats", "fa_raw_load_reset",
 ]
@@ -407,6 +416,8 @@ def lib():
     L.fa_raw_load.argtypes = [vp, vp, sz]
     L.fa_raw_load_stats.argtypes = [vp, C.POINTER(RawLoadStats)]
     L.fa_raw_load_reset.argtypes = [vp]
+    L.fa_raw_merge.argtypes = [vp]
+    L.fa_raw_merge_stats.argtypes = [vp, C.POINTER(RawMergeStats)]
     _LIB = L
     return L
 
@@ -999,6 +1010,17 @@ class FlowAgg:
     def raw_stats(self) -> dict:
         s = RawStats()
         self._chk(self._L.fa_raw_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
+    # -- merging the pending parts (include/flowagg.h "merging the pending flows_raw parts") ----
+    def raw_merge(self):
+        """Replaces the pending parts by one part per Date, rows in stable t32 order over the parts laid end to end: the bytes
+        ONE chunk holding all those records would have built.  The takes deliver the merged parts."""
+        self._chk(self._L.fa_raw_merge(self._h))
+
+    def raw_merge_stats(self) -> dict:
+        s = RawMergeStats()
+        self._chk(self._L.fa_raw_merge_stats(self._h, C.byref(s)))
         return s.as_dict()
 
     # -- sketches -------------------------------------------------------------------

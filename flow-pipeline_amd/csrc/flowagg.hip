@@ -17,6 +17,7 @@
 #include <cmath>
 #include <condition_variable>
 #include <functional>
+#include <map>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,6 +35,7 @@
 #include "lz4.cuh"
 #include "lz4_decode.cuh"
 #include "raw.cuh"
+#include "raw_merge.cuh"
 #include "table_room.h"
 
 using namespace fa;
@@ -227,6 +229,7 @@ struct fa_ctx {
     struct TalkState* talk = nullptr;  // exact top talkers (fa_talkers_enable; talkers_host.inc), nullptr = not enabled
     struct PortState* ports = nullptr;  // bucketed port tables (fa_ports_enable_buckets; ports_host.inc), nullptr = not enabled
     struct RawState* raw = nullptr;     // flows_raw parts (fa_raw_enable; raw_host.inc), nullptr = not enabled
+    struct RawMergeState* raw_merge = nullptr;  // fa_raw_merge (raw_merge_host.inc), nullptr until the first merge that has work
     struct Lz4State* lz4 = nullptr;     // LZ4 frames (lz4_host.inc), nullptr until the first fa_raw_take_lz4 / fa_lz4_frame_device
     struct LoadState* load = nullptr;   // loading parts back (raw_load_host.inc), nullptr until the first decode / load call
 
@@ -266,6 +269,8 @@ static int second_pass_records(fa_ctx* c, const void* d_buf, size_t len, const u
 static void talk_destroy(fa_ctx* c);
 static void port_destroy(fa_ctx* c);
 static void raw_destroy(fa_ctx* c);
+static void raw_merge_destroy(fa_ctx* c);
+static void raw_merge_release(fa_ctx* c);
 static void lz4_destroy(fa_ctx* c);
 static void lz4_release(fa_ctx* c);
 static void load_destroy(fa_ctx* c);
@@ -560,6 +565,7 @@ extern "C" void fa_destroy(fa_ctx* c) {
     talk_destroy(c);
     port_destroy(c);
     raw_destroy(c);
+    raw_merge_destroy(c);
     lz4_destroy(c);
     load_destroy(c);
     const hipStream_t streams[3] = {c->copy_stream, c->cand_stream, c->stream};
@@ -596,6 +602,7 @@ static bool bucket_range(const fa_ctx* c, uint32_t timeslot, uint32_t& lo, uint3
 #include "talkers_host.inc"
 #include "ports_host.inc"
 #include "raw_host.inc"
+#include "raw_merge_host.inc"
 #include "lz4_host.inc"
 #include "second_pass.inc"
 #include "raw_load_host.inc"

@@ -20,7 +20,7 @@ struct RawState {
     bool ev_pending = false;
     uint64_t records_in = 0, records_bad = 0, rows_out = 0, parts_out = 0, bytes_out = 0, chunks = 0;
     uint64_t order_ns = 0, gather_ns = 0, launches = 0;
-    uint64_t takes = 0;    // times the pending parts were cleared (a take, a reset): frames made of them before are stale (lz4_host.inc)
+    uint64_t takes = 0;    // times the pending parts were cleared (a take, a reset) or replaced (a merge): frames made of them before are stale (lz4_host.inc)
 };
 static constexpr size_t RAW_LIST_FIRST = 4096;  // header + 255 entries: what one small copy brings
 
@@ -337,6 +337,7 @@ extern "C" int fa_raw_reset(fa_ctx* c) {
     raw_clear(t, nullptr);
     t->img.reset();
     t->scratch.reset();
+    raw_merge_release(c);
     lz4_release(c);
     load_release(c);
     return FA_OK;

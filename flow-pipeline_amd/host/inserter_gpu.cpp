@@ -42,6 +42,9 @@
 //     insert with Content-Encoding: lz4).  May be given together with -out.raw.native: the flush's parts are built once and
 //     taken once, as frames; the plain file receives the bytes the frames decode to (lz4_frames_to_plain below - the library
 //     clears the parts with a successful take of either kind, and decoding costs less than a second, four times larger copy).
+//   - -out.raw.merge (boolean, off by default; only together with -out.raw.native and / or -out.raw.native.lz4, alone it is a
+//     usage error): every flush calls fa_raw_merge on each partition's ctx before the take, so the files receive ONE part per
+//     Date per partition per flush instead of one per (chunk, Date).
 #include <atomic>
 #include <chrono>
 #include <cstdarg>
@@ -83,6 +86,7 @@ struct Flags {
     std::string OutRowBinary, OutTsv, OffsetsOut, MetricsDump;
     std::string OutRawNative;  // flows_raw parts of every flush, appended: ClickHouse Native blocks (fa_raw_take)
     std::string OutRawNativeLz4;  // ... the same parts as LZ4 frames (fa_raw_take_lz4)
+    bool OutRawMerge = false;     // ... merged to one part per Date before the take (fa_raw_merge)
     std::string OutApp, OutTopk, GpuTransport = "peer";  // raw fa_row_app records / "src|dst <hex key> <weight>" lines; peer | rccl
     long TopkK = 100;
     long TableLog2 = 0, KeysetLog2 = 0, WideLog2 = 0;  // fa_config capacities (0 = the library's defaults)
@@ -170,7 +174,8 @@ static Flags parse_flags(int argc, char** argv) {
         {"key.sets", &f.KeySets}, {"topk.k", &f.TopkK}, {"gpu.table.log2", &f.TableLog2}, {"gpu.keyset.log2", &f.KeysetLog2},
         {"gpu.wide.log2", &f.WideLog2}, {"gpu.batch.bytes", &f.BatchBytes}, {"topk.track", &f.TopkTrack}};
     std::map<std::string, bool*> bools = {{"proto.fixedlen", &f.ProtoFixed}, {"sink.dryrun", &f.DryRun},
-                                          {"window.closeall", &f.CloseAllAtEnd}, {"input.prefault", &f.Prefault}};
+                                          {"window.closeall", &f.CloseAllAtEnd}, {"input.prefault", &f.Prefault},
+                                          {"out.raw.merge", &f.OutRawMerge}};
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a.size() < 2 || a[0] != '-') fatal("unexpected argument %s", a.c_str());
@@ -196,6 +201,10 @@ static Flags parse_flags(int argc, char** argv) {
         else if (name == "flush.dur") {
             if (!parse_duration(val, f.FlushTime)) fatal("invalid value \"%s\" for flag -flush.dur", val.c_str());
         } else usage_and_exit(name);
+    }
+    if (f.OutRawMerge && f.OutRawNative.empty() && f.OutRawNativeLz4.empty()) {
+        fprintf(stderr, "flag -out.raw.merge needs -out.raw.native and/or -out.raw.native.lz4\n");
+        exit(2);
     }
     return f;
 }
@@ -691,6 +700,10 @@ public:
     // copy and are appended to the file; a too small buffer is told its size and asked again
     void takeRaw(PartitionState& p) {
         size_t bytes = 0, nparts = 0;
+        if (f_.OutRawMerge) {  // one part per Date instead of one per (chunk, Date)
+            const int rc = fa_raw_merge(p.ctx);
+            if (rc != 0) fatal("fa_raw_merge: %d %s", rc, fa_last_error(p.ctx));
+        }
         if (out_.wantsRawLz4()) {  // one take, as frames; the retry copies the frames the first call made
             int rc = fa_raw_take_lz4(p.ctx, p.raw_bytes.data(), p.raw_bytes.size(), &bytes, p.raw_parts.data(), p.raw_parts.size(), &nparts);
             if (rc == FA_ERR_CAPACITY) {

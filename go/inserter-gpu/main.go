@@ -96,6 +96,7 @@ var (
 	GpuTransport = flag.String("gpu.transport", "peer", "Window-close exchange between the GPUs: peer (hipMemcpyPeer over xGMI) or rccl (sketches by ncclAllReduce)")
 	OutRawNative = flag.String("out.raw.native", "", "Append every flush's flows_raw parts to this file as ClickHouse Native blocks (one sorted block per chunk and Date)")
 	OutRawNativeLz4 = flag.String("out.raw.native.lz4", "", "Append the same parts to this file as LZ4 frames compressed on the GPU (one frame per part; a valid .lz4 stream of Native blocks); may be given together with -out.raw.native")
+	OutRawMerge  = flag.Bool("out.raw.merge", false, "Merge every flush's flows_raw parts to one part per Date before they are taken (fa_raw_merge); only together with -out.raw.native and/or -out.raw.native.lz4")
 	OutTopk      = flag.String("out.topk", "", "At the end of a session write the top -topk.k SrcAddr / DstAddr of the merged Count-Min sketches here (key.sets 2 / 4)")
 	TopkK        = flag.Int("topk.k", 100, "Rows of -out.topk per sketch")
 	TableLog2    = flag.Int("gpu.table.log2", 0, "log2 slots of a context's flows_5m table (0 = library default)")
@@ -197,6 +198,11 @@ func newPartition(partition int32, claims int) *partitionState {
 // again.  Errors are RETURNED (the caller holds closeMu for reading, see openTimeslots).
 func (p *partitionState) takeRaw(lz4 bool) ([]byte, error) {
 	var nb, np C.size_t
+	if *OutRawMerge { // one part per Date instead of one per (chunk, Date)
+		if rc := C.fa_raw_merge(p.ctx); rc != 0 {
+			return nil, fmt.Errorf("fa_raw_merge: %d %s", int(rc), C.GoString(C.fa_last_error(p.ctx)))
+		}
+	}
 	name := "fa_raw_take"
 	if lz4 {
 		name = "fa_raw_take_lz4" // (one frame per part; the retry copies the frames the first call made)
@@ -678,6 +684,10 @@ func (s *state) ConsumeClaim(session sarama.ConsumerGroupSession, claim sarama.C
 
 func main() {
 	flag.Parse()
+	if *OutRawMerge && *OutRawNative == "" && *OutRawNativeLz4 == "" {
+		fmt.Fprintln(os.Stderr, "flag -out.raw.merge needs -out.raw.native and/or -out.raw.native.lz4")
+		os.Exit(2)
+	}
 	lvl, _ := log.ParseLevel(*LogLevel)
 	log.SetLevel(lvl)
 

@@ -694,6 +694,34 @@ int fa_raw_load_stats(fa_ctx*, fa_raw_load_stats_t* out);
  * does not have.  Pointers the doors returned are invalid afterwards. */
 int fa_raw_load_reset(fa_ctx*);
 
+/* ---- ABI 8, addition: merging the pending flows_raw parts --------------------------- */
+/* What a MergeTree does to its parts after every insert, done to the pending parts before they leave: a ctx emits one part per
+ * (chunk, Date), and fa_raw_merge replaces the pending parts by ONE part per Date that has rows, in ascending Date.  Inside a
+ * part the rows stand in ascending t32; ties keep the order (build order of the source part, then row order inside it): a
+ * stable sort over the parts laid end to end.  If nothing was taken in between, the merged bytes are bit for bit what ONE chunk
+ * holding all those records would have built.  The sources are read where they lie (csrc/raw_merge.cuh).
+ * Afterwards fa_raw_take, fa_raw_take_device, fa_raw_take_lz4 and fa_raw_take_lz4_device deliver the merged parts; frames kept
+ * from a refused fa_raw_take_lz4 are dropped and the next LZ4 take compresses the merged parts; fa_raw_stats shows the merged
+ * state in pending_parts / pending_bytes, and rows_out, parts_out, bytes_out and chunks (built so far) do not move.
+ * Nothing to do - no pending part, or one part per Date in ascending Date already - is FA_OK without a launch, and `merges`
+ * does not move.  A Date with a single source part is moved with a device copy.
+ * Memory: the merged image is a second image as large as the pending bytes, allocated before anything changes; the old image is
+ * KEPT as the next merge's spare (fa_raw_reset releases it).  Scratch: 16 bytes per pending row (keys and indices in and out),
+ * 16 bytes per pending part, the Date list and hipcub's storage.  FA_ERR_NOMEM leaves the pending parts exactly as they were and
+ * the ctx usable.  More than 2^31 - 1 pending rows is FA_ERR_ARG (the number in fa_last_error) before anything changes.
+ * Synchronous: the ctx stream has drained when the call returns (one synchronisation for the Date list, one at the end).
+ * FA_ERR_ARG (text in fa_last_error) on a ctx without fa_raw_enable. */
+typedef struct {
+    uint64_t merges;               /* calls that changed the pending list */
+    uint64_t parts_in, parts_out;  /* pending parts before / after, summed over those calls */
+    uint64_t rows, bytes_in, bytes_out;
+    uint64_t launches;             /* kernel launches queued by merges (3 for the order + 1 per Date with several sources) */
+    uint64_t order_ns, gather_ns;  /* hipEvent time: key extraction + sort + Date list; the gather launches */
+} fa_raw_merge_stats_t;
+int fa_raw_merge(fa_ctx*);
+/* All zero before the first merge; fa_raw_reset releases the merge's buffers, the counters go on counting. */
+int fa_raw_merge_stats(fa_ctx*, fa_raw_merge_stats_t* out);
+
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
  *   if(EType = 0x800, IPv4NumToString(reinterpretAsUInt32(substring(reverse(Addr), 13, 4))), IPv6NumToString(Addr))
