@@ -16,13 +16,17 @@
 // records in stable t32 order - also when a good record's own t32 is 0xFFFFFFFF.  No 33-bit key, no count on the host before
 // the sort.  raw_parts_kernel marks the positions where the Date changes; the host reads that list with one small copy.
 //
-// Gather (raw_gather_kernel), the hot part.  Headers have odd lengths and the first column is 2 bytes wide, so a 4-, 8- or
-// 16-byte column starts at ANY byte offset of the image, and the offset changes with `rows`.  The kernel never issues a store
-// that is off its natural alignment: a workgroup owns RAW_TILE_CHUNKS consecutive 16-byte-ALIGNED chunks of one column's byte
-// range, stages the column's dwords that cover them in LDS (natural-width, coalesced-where-sorted loads through the sort's
-// index), and every lane then reads five LDS dwords, shifts them by the column's byte phase (v_alignbyte) and issues ONE aligned
+// The part writer (raw_write_tile), the hot part, shared by every kernel that writes a part (raw_gather_kernel here,
+// raw_merge_gather_kernel of raw_merge.cuh): they differ in where an element's dwords come from, the `load` they hand in.
+// Headers have odd lengths and the first column is 2 bytes wide, so a 4-, 8- or 16-byte column starts at ANY byte offset of the
+// image, and the offset changes with `rows`.  The writer never issues a store that is off its natural alignment: a workgroup owns
+// RAW_TILE_CHUNKS consecutive 16-byte-ALIGNED chunks of one column's byte range, stages the column's dwords that cover them in
+// LDS, and every lane then reads five LDS dwords, shifts them by the column's byte phase (v_alignbyte) and issues ONE aligned
 // 16-byte store.  The first and last chunk of a column, which the column only partly covers, leave as byte stores; so do the
-// headers.  Every byte of the part is written exactly once, by exactly one lane.
+// headers.  Every byte of the part is written exactly once, by exactly one lane.  The geometry - workgroup -> (column, tile),
+// tile -> byte phase, lane -> chunk, element -> LDS slot - is plain __host__ __device__ text that the host calls too: to size the
+// grid (raw_part_tiles) and to enumerate the walk (tests/host_raw_merge.hip).
+// raw_gather_kernel's load: natural-width, coalesced-where-sorted reads of the decoded columns through the sort's index.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -77,6 +81,83 @@ __host__ __device__ __forceinline__ uint64_t raw_col_tiles(uint64_t at, uint64_t
     return (chunks + RAW_TILE_CHUNKS - 1) / RAW_TILE_CHUNKS;
 }
 
+// ---- the part writer's geometry: a part of `rows` rows whose first byte has the address `base` (its low 4 bits matter) ---------
+// the tiles of column d, whose header stands at `off`; next: where the following column's header stands
+__host__ __device__ __forceinline__ uint64_t raw_col_step(const RawColDef& d, uint64_t base, uint64_t rows, uint64_t off, uint64_t* next) {
+    const uint64_t data = off + raw_col_header_len(d), bytes = rows * d.width;
+    *next = data + bytes;
+    return raw_col_tiles(base + data, bytes);
+}
+// the workgroups one part takes: every column's tiles
+__host__ __device__ inline uint64_t raw_part_tiles(const RawColDef* cols, uint64_t base, uint64_t rows) {
+    uint64_t tiles = 0, off = 1 + raw_varuint_len(rows);
+    for (uint32_t c = 0; c < RAW_NCOLS; c++) tiles += raw_col_step(cols[c], base, rows, off, &off);
+    return tiles;
+}
+struct RawTile {
+    uint32_t c;          // the column
+    uint64_t tile, off;  // the tile inside the column; the column header's offset in the part (== raw_col_offset)
+};
+// workgroup wg -> its tile: a few uniform steps over the 16 columns.  false: the part has no such tile.  (Every workgroup runs
+// this in front of 4 KiB of work.  The loop leaves from its body and has no bound in its head: the compiler unrolls that shape by
+// two; written as `for (c = 0; c < RAW_NCOLS; ...)` both gathers measured 0.006 ns per row slower, 6 % of the build's.)
+__host__ __device__ __forceinline__ bool raw_tile_locate(const RawColDef* cols, uint64_t base, uint64_t rows, uint64_t wg, RawTile* t) {
+    uint64_t off = 1 + raw_varuint_len(rows), next;
+    uint32_t c = 0;
+    for (;; c++, off = next) {
+        if (c == RAW_NCOLS) return false;
+        const uint64_t tiles = raw_col_step(cols[c], base, rows, off, &next);
+        if (wg < tiles) break;
+        wg -= tiles;
+    }
+    *t = RawTile{c, wg, off};
+    return true;
+}
+struct RawTilePhase {
+    long long s, k0;  // the column byte the tile's first aligned chunk starts at (negative in the first tile unless the column is
+                      // aligned); the first staged dword (floor: s may be negative)
+    uint32_t sh;      // the byte phase, the same for every chunk of the column
+};
+// col: the address of the column's first data byte
+__host__ __device__ __forceinline__ RawTilePhase raw_tile_phase(uint64_t col, uint64_t tile) {
+    const long long s = (long long)tile * (RAW_TILE_CHUNKS * 16) - (long long)(col & 15);
+    return RawTilePhase{s, s >> 2, (uint32_t)(s & 3)};
+}
+// the column byte lane tid's chunk starts at; what the chunk is to a column of `bytes` bytes: outside it (no store), whole (one
+// aligned 16-byte store), or neither - the column's first or last chunk, partly covered: byte stores for the bytes that are the
+// column's.  b > -16 always (raw_tile_phase: s >= -15), so a chunk is outside only behind the column; the byte test is ONE unsigned
+// compare, 0 <= b + i < bytes.  (Spelled so, the store tail compiles to the instructions it had when it stood in the kernels: behind
+// the function boundary the compiler no longer folds `b + 16 <= 0` away nor the signed pair `b + i >= 0 && b + i < bytes` into one.)
+__host__ __device__ __forceinline__ long long raw_lane_byte(long long s, uint32_t tid) { return s + 16ll * tid; }
+__host__ __device__ __forceinline__ bool raw_chunk_outside(long long b, long long bytes) { return b >= bytes; }
+__host__ __device__ __forceinline__ bool raw_chunk_whole(long long b, long long bytes) { return b >= 0 && b + 16 <= bytes; }
+__host__ __device__ __forceinline__ bool raw_chunk_byte_in(long long b, int i, long long bytes) { return (unsigned long long)(b + i) < (unsigned long long)bytes; }
+// Staging, for elements of dpe = 1, 2, 4 dwords: LDS slot l holds the column's dword k0 + l, lane tid reads the slots
+// 4 tid .. 4 tid + 4, so the slots 0 .. RAW_TILE_DWORDS are staged.  They belong to at most (RAW_TILE_DWORDS + 1) / dpe + 2
+// consecutive elements from raw_stage_first on (the run may begin and end inside an element); an element outside [0, rows) stages
+// zeroes into slots no byte of the column lies in.
+__host__ __device__ __forceinline__ long long raw_stage_first(long long k0, uint32_t dpe) { return k0 >> (dpe >> 1); }  // (floor)
+__host__ __device__ __forceinline__ uint32_t raw_stage_count(uint32_t dpe) { return (RAW_TILE_DWORDS + 1) / dpe + 2; }
+// the slot of dword q of element e, and whether it is one of the staged ones
+__host__ __device__ __forceinline__ long long raw_stage_slot(long long e, uint32_t dpe, uint32_t q, long long k0) { return e * dpe + q - k0; }
+__host__ __device__ __forceinline__ bool raw_stage_holds(long long l) { return l >= 0 && l <= (long long)RAW_TILE_DWORDS; }
+
+// ---- header bytes ------------------------------------------------------------------------------------------------------------
+// varuint(v) at p -> its length
+__host__ __device__ inline uint32_t raw_put_varuint(uint8_t* p, uint64_t v) {
+    uint32_t n = 0;
+    while (v >= 128) p[n++] = (uint8_t)(v | 128), v >>= 7;
+    p[n++] = (uint8_t)v;
+    return n;
+}
+// byte i of a column's header: varuint(name_len) name varuint(type_len) type (both lengths are below 128: one byte each)
+__host__ __device__ __forceinline__ uint8_t raw_col_header_byte(const RawColDef& d, uint32_t i) {
+    if (i == 0) return d.name_len;
+    if (i <= d.name_len) return (uint8_t)d.name[i - 1];
+    if (i == 1u + d.name_len) return d.type_len;
+    return (uint8_t)d.type[i - 2 - d.name_len];
+}
+
 // ---- order -----------------------------------------------------------------------------------------------------------------
 // flag[i] = the record is good; flag[n] = 0, so that the exclusive scan over n + 1 words leaves the good count in pos[n]
 __global__ __launch_bounds__(256) void raw_flag_kernel(const uint8_t* __restrict__ status, uint32_t n, uint32_t* __restrict__ flag) {
@@ -125,10 +206,9 @@ struct RawGatherArgs {
     uint32_t rows, date;
 };
 
-// dwords [e * dpe, (e + 1) * dpe) of a column's byte stream: element e in sorted order (0 <= e < rows)
+// dwords [e * dpe, (e + 1) * dpe) of a column's byte stream: element e in sorted order (0 <= e < rows) of a decoded column
 __device__ __forceinline__ void raw_load_element(const RawGatherArgs& a, uint32_t kind, const void* src, uint32_t e, uint32_t v[4]) {
     switch (kind) {
-    case RAW_K_KEY: v[0] = a.key[e]; break;
     case RAW_K_NARROW64: v[0] = (uint32_t)((const uint64_t*)src)[a.idx[e]]; break;
     case RAW_K_U32: v[0] = ((const uint32_t*)src)[a.idx[e]]; break;
     case RAW_K_U64: {
@@ -143,85 +223,68 @@ __device__ __forceinline__ void raw_load_element(const RawGatherArgs& a, uint32_
     }
 }
 
-__global__ __launch_bounds__(RAW_BLOCK) void raw_gather_kernel(const RawGatherArgs a) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[RAW_TILE_DWORDS + 4];
+// One tile of a part, by one workgroup of RAW_BLOCK threads: the headers (tile 0), the column's dwords into lds[RAW_TILE_DWORDS + 4]
+// (16-byte aligned) - the Date constant, key[e] for TimeReceived, load(e, v) for every other column -, then one store per lane.
+// `key`: the part's sorted keys.  load(e, v): the dwords of sorted element e (0 <= e < rows) of column t.c into v[0 .. width / 4).
+template <class Load>
+__device__ __forceinline__ void raw_write_tile(uint32_t* lds, uint8_t* part, uint32_t rows, uint32_t date, const uint32_t* key, const RawTile& t, Load load) {
     const uint32_t tid = threadIdx.x;
-    const uint64_t rows = a.rows;
-    // which column, which tile of it: a few uniform steps over the 16 columns
-    uint64_t tile = blockIdx.x, off = 1 + raw_varuint_len(rows);
-    uint32_t c = 0;
-    for (;; c++) {
-        if (c == RAW_NCOLS) return;  // (the host launches exactly the tiles there are)
-        const RawColDef& d = RAW_COLS_D[c];
-        const uint64_t data = off + raw_col_header_len(d), bytes = rows * d.width;
-        const uint64_t tiles = raw_col_tiles((uint64_t)(uintptr_t)(a.part + data), bytes);
-        if (tile < tiles) break;
-        tile -= tiles;
-        off = data + bytes;
-    }
-    const RawColDef& d = RAW_COLS_D[c];
-    const uint32_t kind = d.kind;
+    const RawColDef& d = RAW_COLS_D[t.c];
     const uint32_t hl = raw_col_header_len(d);
-    uint8_t* const col = a.part + off + hl;  // the column's first data byte
-    const long long bytes = (long long)(rows * d.width);
-    if (tile == 0) {  // the column's header, and in front of the first column the block's
-        uint8_t* h = a.part + off;
-        if (tid < hl) {
-            uint8_t b;
-            if (tid == 0) b = d.name_len;
-            else if (tid <= d.name_len) b = (uint8_t)d.name[tid - 1];
-            else if (tid == 1u + d.name_len) b = d.type_len;
-            else b = (uint8_t)d.type[tid - 2 - d.name_len];
-            h[tid] = b;
-        }
-        if (c == 0 && tid == 0) {
-            a.part[0] = (uint8_t)RAW_NCOLS;
-            uint64_t v = rows;
-            uint8_t* p = a.part + 1;
-            while (v >= 128) *p++ = (uint8_t)(v | 128), v >>= 7;
-            *p = (uint8_t)v;
-        }
+    uint8_t* const col = part + t.off + hl;  // the column's first data byte
+    const long long bytes = (long long)((uint64_t)rows * d.width);
+    if (t.tile == 0) {  // the column's header, and in front of the first column the block's
+        if (tid < hl) part[t.off + tid] = raw_col_header_byte(d, tid);
+        if (t.c == 0 && tid == 0) part[0] = (uint8_t)RAW_NCOLS, raw_put_varuint(part + 1, rows);
     }
-    // s: the column byte the tile's first aligned chunk starts at (negative in the first tile unless the column is aligned)
-    const long long s = (long long)tile * (RAW_TILE_CHUNKS * 16) - (long long)((uintptr_t)col & 15);
-    const long long k0 = s >> 2;             // first staged dword (floor: s may be negative)
-    const uint32_t sh = (uint32_t)(s & 3);   // the byte phase, the same for every chunk of the column
-    if (kind == RAW_K_DATE) {                // one Date per part: nothing to gather
-        const uint32_t v = a.date | (a.date << 16);
+    const RawTilePhase ph = raw_tile_phase((uint64_t)(uintptr_t)col, t.tile);
+    if (d.kind == RAW_K_DATE) {  // one Date per part: nothing to gather
+        const uint32_t v = date | (date << 16);
         for (uint32_t j = tid; j < RAW_TILE_DWORDS + 4; j += RAW_BLOCK) lds[j] = v;
     } else {
         const uint32_t dpe = d.width >> 2;  // dwords per element: 1, 2, 4
-        const long long e0 = k0 >> (dpe >> 1);  // first element that touches the staged dwords (floor)
-        const uint32_t nelem = (RAW_TILE_DWORDS + 1) / dpe + 2;
-        for (uint32_t j = tid; j < nelem; j += RAW_BLOCK) {
+        const long long e0 = raw_stage_first(ph.k0, dpe);
+        for (uint32_t j = tid; j < raw_stage_count(dpe); j += RAW_BLOCK) {
             const long long e = e0 + j;
             uint32_t v[4] = {0u, 0u, 0u, 0u};
-            if (e >= 0 && e < (long long)rows) raw_load_element(a, kind, a.src[c], (uint32_t)e, v);
+            if (e >= 0 && e < (long long)rows) {
+                if (d.kind == RAW_K_KEY) v[0] = key[e];
+                else load((uint32_t)e, v);
+            }
             for (uint32_t q = 0; q < dpe; q++) {
-                const long long l = e * dpe + q - k0;  // where the dword stands in the staged run
-                if (l >= 0 && l <= (long long)RAW_TILE_DWORDS) lds[l] = v[q];
+                const long long l = raw_stage_slot(e, dpe, q, ph.k0);
+                if (raw_stage_holds(l)) lds[l] = v[q];
             }
         }
     }
     __syncthreads();
-    const long long b = s + 16ll * tid;  // the column byte this lane's chunk starts at
-    if (b >= bytes || b + 16 <= 0) return;
+    const long long b = raw_lane_byte(ph.s, tid);
+    if (raw_chunk_outside(b, bytes)) return;
     const uint4 lo = *(const uint4*)&lds[4 * tid];
     const uint32_t hi = lds[4 * tid + 4];
     uint4 o;
-    o.x = __builtin_amdgcn_alignbyte(lo.y, lo.x, sh);
-    o.y = __builtin_amdgcn_alignbyte(lo.z, lo.y, sh);
-    o.z = __builtin_amdgcn_alignbyte(lo.w, lo.z, sh);
-    o.w = __builtin_amdgcn_alignbyte(hi, lo.w, sh);
+    o.x = __builtin_amdgcn_alignbyte(lo.y, lo.x, ph.sh);
+    o.y = __builtin_amdgcn_alignbyte(lo.z, lo.y, ph.sh);
+    o.z = __builtin_amdgcn_alignbyte(lo.w, lo.z, ph.sh);
+    o.w = __builtin_amdgcn_alignbyte(hi, lo.w, ph.sh);
     uint8_t* const dst = col + b;  // 16-byte aligned by construction
-    if (b >= 0 && b + 16 <= bytes) {
+    if (raw_chunk_whole(b, bytes)) {
         *(uint4*)dst = o;
     } else {  // the column's first or last chunk: only the bytes that are the column's
         const uint32_t w[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
         for (int i = 0; i < 16; i++)
-            if (b + i >= 0 && b + i < bytes) dst[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+            if (raw_chunk_byte_in(b, i, bytes)) dst[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
     }
+}
+
+__global__ __launch_bounds__(RAW_BLOCK) void raw_gather_kernel(const RawGatherArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[RAW_TILE_DWORDS + 4];
+    RawTile t;
+    if (!raw_tile_locate(RAW_COLS_D, (uint64_t)(uintptr_t)a.part, a.rows, blockIdx.x, &t)) return;  // (the host launches exactly the tiles there are)
+    const uint32_t kind = RAW_COLS_D[t.c].kind;
+    const void* const src = a.src[t.c];
+    raw_write_tile(lds, a.part, a.rows, a.date, a.key, t, [&](uint32_t e, uint32_t* v) { raw_load_element(a, kind, src, e, v); });
 }
 
 // ---- loading parts back: the header check and the unpack (host side: raw_load_host.inc) ------------------------------------------

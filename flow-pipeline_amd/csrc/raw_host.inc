@@ -59,18 +59,11 @@ extern "C" int fa_flow_rows_to_native(const fa_flow_row* rows, size_t n, uint8_t
     auto put = [&](uint64_t v, int bytes) {
         for (int i = 0; i < bytes; i++) *p++ = (uint8_t)(v >> (8 * i));
     };
-    auto varuint = [&](uint64_t v) {
-        while (v >= 128) *p++ = (uint8_t)(v | 128), v >>= 7;
-        *p++ = (uint8_t)v;
-    };
-    varuint(RAW_NCOLS);
-    varuint(n);
+    p += raw_put_varuint(p, RAW_NCOLS);
+    p += raw_put_varuint(p, n);
     for (uint32_t c = 0; c < RAW_NCOLS; c++) {
         const RawColDef& d = RAW_COLS_H[c];
-        varuint(d.name_len);
-        memcpy(p, d.name, d.name_len), p += d.name_len;
-        varuint(d.type_len);
-        memcpy(p, d.type, d.type_len), p += d.type_len;
+        for (uint32_t i = 0; i < raw_col_header_len(d); i++) *p++ = raw_col_header_byte(d, i);
         for (size_t i = 0; i < n; i++) {
             const fa_flow_row& r = rows[i];
             switch (c) {
@@ -143,56 +136,107 @@ static int raw_reserve_image(fa_ctx* c, size_t more) {
     return FA_OK;
 }
 
+// ---- order and layout, shared by the build of a chunk and the merge (raw_merge_host.inc) ------------------------------------------
+// The scratch of one order step over n keys, behind whatever the caller keeps in front of it: keys and indices in and out
+// (n + 1 words each), the part list, hipcub's storage (tmp_min: what the caller's own hipcub calls need of it).
+struct RawOrder {
+    uint32_t n = 0;
+    size_t words = 0, list_bytes = 0, tmp_bytes = 0;
+    uint32_t *key_in = nullptr, *key = nullptr, *idx_in = nullptr, *idx = nullptr;
+    RawPartsHeader* hdr = nullptr;
+    RawPartEntry* list = nullptr;
+    void* tmp = nullptr;
+    RawOrder(fa_ctx* c, uint32_t n_, size_t tmp_min = 0) : n(n_) {
+        size_t tmp_sort = 0;
+        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 32, c->stream);
+        words = align256(((size_t)n + 1) * 4), tmp_bytes = align256(std::max(tmp_min, tmp_sort));
+        list_bytes = align256(sizeof(RawPartsHeader) + (size_t)RAW_MAX_DATES * sizeof(RawPartEntry));
+    }
+    size_t bytes() const { return 4 * words + list_bytes + tmp_bytes; }
+    void carve(uint8_t* sb) {
+        key_in = (uint32_t*)sb, key = (uint32_t*)(sb + words), idx_in = (uint32_t*)(sb + 2 * words), idx = (uint32_t*)(sb + 3 * words);
+        hdr = (RawPartsHeader*)(sb + 4 * words), list = (RawPartEntry*)(hdr + 1);
+        tmp = sb + 4 * words + list_bytes;
+    }
+};
+
+// key_in / idx_in -> key / idx in stable key order, the positions where the Date changes (pos[n]: the count of good rows in
+// front), `done` recorded behind the last kernel and *launches += launched, then ONE small copy and one synchronisation: the
+// list's header and its entries in ascending `start`.  A header whose nparts exceeds the list comes back without entries: the
+// caller's consistency check fails.
+static int raw_order_and_list(fa_ctx* c, const RawOrder& o, const uint32_t* pos, hipEvent_t done, uint64_t* launches, uint64_t launched, RawPartsHeader* h,
+                              std::vector<RawPartEntry>* ent) {
+    RawState* t = c->raw;
+    HIPCHK(c, hipMemsetAsync(o.hdr, 0, sizeof(RawPartsHeader), c->stream));
+    size_t tb = o.tmp_bytes;
+    if (hipcub::DeviceRadixSort::SortPairs(o.tmp, tb, (const uint32_t*)o.key_in, o.key, (const uint32_t*)o.idx_in, o.idx, (int)o.n, 0, 32, c->stream) != hipSuccess)
+        return fail(c, FA_ERR_HIP, "sort failed");
+    hipLaunchKernelGGL(raw_parts_kernel, dim3((o.n + 1 + 255) / 256), dim3(256), 0, c->stream, (const uint32_t*)o.key, pos, o.n, o.hdr, o.list, RAW_MAX_DATES);
+    (void)hipEventRecord(done, c->stream);
+    HIPCHK(c, hipGetLastError());
+    *launches += launched;  // (the caller's kernels in front and the two here: counted once they are launched, before the readback)
+    HIPCHK(c, hipMemcpyAsync(t->h_list, o.hdr, RAW_LIST_FIRST, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *h = *(const RawPartsHeader*)t->h_list.get();
+    ent->assign(h->nparts <= RAW_MAX_DATES ? h->nparts : 0, RawPartEntry{});
+    const size_t first = std::min<size_t>(ent->size(), (RAW_LIST_FIRST - sizeof(RawPartsHeader)) / sizeof(RawPartEntry));
+    if (first) memcpy(ent->data(), t->h_list.get() + sizeof(RawPartsHeader), first * sizeof(RawPartEntry));
+    if (ent->size() > first) HIPCHK(c, hipMemcpy(ent->data() + first, o.list + first, (ent->size() - first) * sizeof(RawPartEntry), hipMemcpyDeviceToHost));
+    std::sort(ent->begin(), ent->end(), [](const RawPartEntry& x, const RawPartEntry& y) { return x.start < y.start; });
+    return FA_OK;
+}
+
+// the sorted entries -> the parts' descriptions, laid back to back from `offset` on
+static std::vector<fa_raw_part> raw_lay_out(const RawPartsHeader& h, const std::vector<RawPartEntry>& ent, size_t offset) {
+    std::vector<fa_raw_part> parts(ent.size());
+    for (size_t i = 0; i < ent.size(); i++) {
+        const bool last = i + 1 == ent.size();
+        fa_raw_part& p = parts[i];
+        p.date = ent[i].t_min / 86400u;
+        p.t_min = ent[i].t_min;
+        p.t_max = last ? h.last_t_max : ent[i + 1].prev_t_max;
+        p.rows = (last ? h.good : ent[i + 1].start) - ent[i].start;
+        p.offset = offset;
+        p.bytes = fa_raw_part_bytes(p.rows);
+        offset += p.bytes;
+    }
+    return parts;
+}
+// the workgroups that write a part of `rows` rows at `part`
+static dim3 raw_part_grid(const uint8_t* part, uint64_t rows) { return dim3((unsigned)raw_part_tiles(RAW_COLS_H, (uint64_t)(uintptr_t)part, rows)); }
+
 // One chunk of m <= raw_chunk_cap decoded records -> its parts appended to the image.
 static int raw_build_chunk(fa_ctx* c, const fa_columns& cols, size_t m) {
     RawState* t = c->raw;
     if (m == 0) return FA_OK;
     raw_read_events(t);
-    // scratch: flags, positions (m + 1 words each), keys and indices in and out (m words each), the part list, hipcub storage
+    // scratch: flags and positions (m + 1 words each) in front of the order step's
     const uint32_t n = (uint32_t)m;
-    size_t tmp_scan = 0, tmp_sort = 0;
+    size_t tmp_scan = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n + 1), c->stream);
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 32, c->stream);
-    const size_t words = align256(((size_t)n + 1) * 4), tmp_bytes = align256(std::max(tmp_scan, tmp_sort));
-    const size_t list_bytes = align256(sizeof(RawPartsHeader) + (size_t)RAW_MAX_DATES * sizeof(RawPartEntry));
-    int rc = ensure_dev(c, t->scratch, 6 * words + list_bytes + tmp_bytes, "raw part scratch");
+    RawOrder o(c, n, tmp_scan);
+    int rc = ensure_dev(c, t->scratch, 2 * o.words + o.bytes(), "raw part scratch");
     if (rc) return rc;
     uint8_t* sb = (uint8_t*)t->scratch.get();
-    uint32_t *flag = (uint32_t*)sb, *pos = (uint32_t*)(sb + words), *key_in = (uint32_t*)(sb + 2 * words), *key = (uint32_t*)(sb + 3 * words);
-    uint32_t *idx_in = (uint32_t*)(sb + 4 * words), *idx = (uint32_t*)(sb + 5 * words);
-    RawPartsHeader* hdr = (RawPartsHeader*)(sb + 6 * words);
-    RawPartEntry* list = (RawPartEntry*)(hdr + 1);
-    void* tmp = sb + 6 * words + list_bytes;
+    uint32_t *flag = (uint32_t*)sb, *pos = (uint32_t*)(sb + o.words);
+    o.carve(sb + 2 * o.words);
 
     // ---- order
     const dim3 grid((n + 1 + 255) / 256), block(256);
     (void)hipEventRecord(t->ev[0], c->stream);
-    HIPCHK(c, hipMemsetAsync(hdr, 0, sizeof(RawPartsHeader), c->stream));
     hipLaunchKernelGGL(raw_flag_kernel, grid, block, 0, c->stream, cols.status, n, flag);
-    size_t tb = tmp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum(tmp, tb, (const uint32_t*)flag, pos, (int)(n + 1), c->stream) != hipSuccess) return fail(c, FA_ERR_HIP, "scan failed");
-    hipLaunchKernelGGL(raw_key_kernel, grid, block, 0, c->stream, cols.status, cols.time_received, n, (const uint32_t*)pos, key_in, idx_in);
-    tb = tmp_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint32_t*)key_in, key, (const uint32_t*)idx_in, idx, (int)n, 0, 32, c->stream) != hipSuccess)
-        return fail(c, FA_ERR_HIP, "sort failed");
-    hipLaunchKernelGGL(raw_parts_kernel, grid, block, 0, c->stream, (const uint32_t*)key, (const uint32_t*)pos, n, hdr, list, RAW_MAX_DATES);
-    (void)hipEventRecord(t->ev[1], c->stream);
-    HIPCHK(c, hipGetLastError());
-    t->launches += 5;
-    // ---- the part list: one small copy
-    HIPCHK(c, hipMemcpyAsync(t->h_list, hdr, RAW_LIST_FIRST, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    size_t tb = o.tmp_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum(o.tmp, tb, (const uint32_t*)flag, pos, (int)(n + 1), c->stream) != hipSuccess) return fail(c, FA_ERR_HIP, "scan failed");
+    hipLaunchKernelGGL(raw_key_kernel, grid, block, 0, c->stream, cols.status, cols.time_received, n, (const uint32_t*)pos, o.key_in, o.idx_in);
+    RawPartsHeader h;
+    std::vector<RawPartEntry> ent;
+    rc = raw_order_and_list(c, o, pos, t->ev[1], &t->launches, 5, &h, &ent);
+    if (rc) return rc;
     {
         float ms = 0;
         if (hipEventElapsedTime(&ms, t->ev[0], t->ev[1]) == hipSuccess) t->order_ns += (uint64_t)((double)ms * 1e6);
     }
-    const RawPartsHeader h = *(const RawPartsHeader*)t->h_list.get();
     if (h.good > n || h.nparts > RAW_MAX_DATES || (h.good != 0) != (h.nparts != 0)) return fail(c, FA_ERR_HIP, "internal: the raw part list is inconsistent");
-    std::vector<RawPartEntry> ent(h.nparts);
-    const size_t first = std::min<size_t>(h.nparts, (RAW_LIST_FIRST - sizeof(RawPartsHeader)) / sizeof(RawPartEntry));
-    if (first) memcpy(ent.data(), t->h_list.get() + sizeof(RawPartsHeader), first * sizeof(RawPartEntry));
-    if (h.nparts > first) HIPCHK(c, hipMemcpy(ent.data() + first, list + first, (h.nparts - first) * sizeof(RawPartEntry), hipMemcpyDeviceToHost));
-    std::sort(ent.begin(), ent.end(), [](const RawPartEntry& x, const RawPartEntry& y) { return x.start < y.start; });
     // (the counters move only once the chunk's parts are certain to be built: rows_out + records_bad == records_in always holds)
     auto count_chunk = [&] {
         t->records_in += n;
@@ -204,34 +248,23 @@ static int raw_build_chunk(fa_ctx* c, const fa_columns& cols, size_t m) {
         return FA_OK;
     }
     // ---- the image's layout, then the gather: one launch per part
-    size_t bytes = 0;
-    for (size_t i = 0; i < ent.size(); i++) bytes += fa_raw_part_bytes((i + 1 < ent.size() ? ent[i + 1].start : h.good) - ent[i].start);
-    rc = raw_reserve_image(c, bytes);
+    const std::vector<fa_raw_part> parts = raw_lay_out(h, ent, t->used);
+    rc = raw_reserve_image(c, parts.back().offset + parts.back().bytes - t->used);
     if (rc) return rc;
     count_chunk();
     (void)hipEventRecord(t->ev[2], c->stream);  // (behind the part list's round trip and the image's growth: the gather launches alone)
-    for (size_t i = 0; i < ent.size(); i++) {
-        const uint32_t end = i + 1 < ent.size() ? ent[i + 1].start : h.good;
-        fa_raw_part p{};
-        p.date = ent[i].t_min / 86400u;
-        p.t_min = ent[i].t_min;
-        p.t_max = i + 1 < ent.size() ? ent[i + 1].prev_t_max : h.last_t_max;
-        p.rows = end - ent[i].start;
-        p.offset = t->used;
-        p.bytes = fa_raw_part_bytes(p.rows);
+    for (size_t i = 0; i < parts.size(); i++) {
+        const fa_raw_part& p = parts[i];
         RawGatherArgs a{};
-        a.part = t->img + t->used;
-        a.key = key + ent[i].start;
-        a.idx = idx + ent[i].start;
+        a.part = t->img + p.offset;
+        a.key = o.key + ent[i].start;
+        a.idx = o.idx + ent[i].start;
         const void* src[RAW_NCOLS] = {nullptr, nullptr, cols.time_flow_start, cols.sequence_num, cols.sampling_rate, cols.sampler_address, cols.src_addr, cols.dst_addr,
                                       cols.src_as, cols.dst_as, cols.etype, cols.proto, cols.src_port, cols.dst_port, cols.bytes, cols.packets};
         memcpy(a.src, src, sizeof src);
         a.rows = (uint32_t)p.rows;
         a.date = p.date;
-        uint64_t tiles = 0;
-        for (uint32_t col = 0; col < RAW_NCOLS; col++)
-            tiles += raw_col_tiles((uint64_t)(uintptr_t)(a.part + raw_col_offset(RAW_COLS_H, p.rows, col) + raw_col_header_len(RAW_COLS_H[col])), p.rows * RAW_COLS_H[col].width);
-        hipLaunchKernelGGL(raw_gather_kernel, dim3((unsigned)tiles), dim3(RAW_BLOCK), 0, c->stream, a);
+        hipLaunchKernelGGL(raw_gather_kernel, raw_part_grid(a.part, p.rows), dim3(RAW_BLOCK), 0, c->stream, a);
         HIPCHK(c, hipGetLastError());
         t->launches++;
         t->used += p.bytes;

@@ -8,12 +8,10 @@
 // keys keep (source in build order, row in the source) - the order ONE chunk holding all those records would have given them.
 // Date is monotone in the key: one sort serves every Date, and raw_parts_kernel lists the boundaries as it does for a chunk.
 //
-// Gather (raw_merge_gather_kernel), the hot part: raw_gather_kernel with another source.  The store side is the same - a
-// workgroup owns RAW_TILE_CHUNKS 16-byte-ALIGNED chunks of one column of the merged part, stages the dwords that cover them in
-// LDS, shifts by the destination's byte phase and issues one aligned 16-byte store per lane; first and last chunk of a column
-// and the headers leave as byte stores; every byte is written exactly once, by one lane.  The load side: sorted element e is
-// global row g = idx[e]; a bounded binary search over `first` (staged in LDS when the call has at most RAW_MERGE_LDS_SRCS
-// sources, read from global memory otherwise) gives the source p, and the element lies at
+// Gather (raw_merge_gather_kernel), the hot part: the part writer of raw.cuh (raw_write_tile - the tiles, the LDS staging, the
+// aligned stores and the headers are described there) over another load.  Sorted element e is global row g = idx[e]; a bounded
+// binary search over `first` (staged in LDS when the call has at most RAW_MERGE_LDS_SRCS sources, read from global memory
+// otherwise) gives the source p, and the element lies at
 //   src[p].part + raw_col_offset(rows_p, c) + header_len(c) + (g - first[p]) * width.
 // That address has ANY byte phase, and the phase differs from source to source: it is per lane, not wave-uniform.  The load is
 // an element-width read at the element's own address (raw_load_unaligned): gfx950 serves a global load at any byte address,
@@ -109,99 +107,25 @@ struct RawMergeArgs {
 __global__ __launch_bounds__(RAW_BLOCK) void raw_merge_gather_kernel(const RawMergeArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[RAW_TILE_DWORDS + 4];
     __shared__ uint32_t first_lds[RAW_MERGE_LDS_SRCS];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t rows = a.rows;
-    // which column, which tile of it: a few uniform steps over the 16 columns
-    uint64_t tile = blockIdx.x, off = 1 + raw_varuint_len(rows);
-    uint32_t c = 0;
-    for (;; c++) {
-        if (c == RAW_NCOLS) return;  // (the host launches exactly the tiles there are)
-        const RawColDef& d = RAW_COLS_D[c];
-        const uint64_t data = off + raw_col_header_len(d), bytes = rows * d.width;
-        const uint64_t tiles = raw_col_tiles((uint64_t)(uintptr_t)(a.part + data), bytes);
-        if (tile < tiles) break;
-        tile -= tiles;
-        off = data + bytes;
-    }
-    const RawColDef& d = RAW_COLS_D[c];
-    const uint32_t kind = d.kind;
-    const uint32_t hl = raw_col_header_len(d);
-    uint8_t* const col = a.part + off + hl;  // the column's first data byte
-    const long long bytes = (long long)(rows * d.width);
-    const bool from_src = kind != RAW_K_DATE && kind != RAW_K_KEY;
+    RawTile t;
+    if (!raw_tile_locate(RAW_COLS_D, (uint64_t)(uintptr_t)a.part, a.rows, blockIdx.x, &t)) return;  // (the host launches exactly the tiles there are)
+    const uint32_t kind = RAW_COLS_D[t.c].kind;
     const bool in_lds = a.nsrc <= RAW_MERGE_LDS_SRCS;
-    if (from_src && in_lds)
-        for (uint32_t j = tid; j < a.nsrc; j += RAW_BLOCK) first_lds[j] = a.src[j].first;
-    if (tile == 0) {  // the column's header, and in front of the first column the block's
-        uint8_t* h = a.part + off;
-        if (tid < hl) {
-            uint8_t b;
-            if (tid == 0) b = d.name_len;
-            else if (tid <= d.name_len) b = (uint8_t)d.name[tid - 1];
-            else if (tid == 1u + d.name_len) b = d.type_len;
-            else b = (uint8_t)d.type[tid - 2 - d.name_len];
-            h[tid] = b;
-        }
-        if (c == 0 && tid == 0) {
-            a.part[0] = (uint8_t)RAW_NCOLS;
-            uint64_t v = rows;
-            uint8_t* p = a.part + 1;
-            while (v >= 128) *p++ = (uint8_t)(v | 128), v >>= 7;
-            *p = (uint8_t)v;
+    RawMergeCol mc{};
+    if (kind != RAW_K_DATE && kind != RAW_K_KEY) {  // a column that comes from the sources: where it lies in them, the table of first rows
+        mc = raw_merge_col(RAW_COLS_D, t.c);
+        if (in_lds) {
+            for (uint32_t j = threadIdx.x; j < a.nsrc; j += RAW_BLOCK) first_lds[j] = a.src[j].first;
+            __syncthreads();
         }
     }
-    __syncthreads();  // (the table of first rows is complete)
-    // s: the column byte the tile's first aligned chunk starts at (negative in the first tile unless the column is aligned)
-    const long long s = (long long)tile * (RAW_TILE_CHUNKS * 16) - (long long)((uintptr_t)col & 15);
-    const long long k0 = s >> 2;            // first staged dword (floor: s may be negative)
-    const uint32_t sh = (uint32_t)(s & 3);  // the byte phase, the same for every chunk of the column
-    if (kind == RAW_K_DATE) {               // one Date per part: nothing to gather
-        const uint32_t v = a.date | (a.date << 16);
-        for (uint32_t j = tid; j < RAW_TILE_DWORDS + 4; j += RAW_BLOCK) lds[j] = v;
-    } else {
-        const RawMergeCol mc = raw_merge_col(RAW_COLS_D, c);
-        const uint32_t dpe = d.width >> 2;      // dwords per element: 1, 2, 4
-        const long long e0 = k0 >> (dpe >> 1);  // first element that touches the staged dwords (floor)
-        const uint32_t nelem = (RAW_TILE_DWORDS + 1) / dpe + 2;
-        for (uint32_t j = tid; j < nelem; j += RAW_BLOCK) {
-            const long long e = e0 + j;
-            uint32_t v[4] = {0u, 0u, 0u, 0u};
-            if (e >= 0 && e < (long long)rows) {
-                if (kind == RAW_K_KEY) {
-                    v[0] = a.key[e];
-                } else {
-                    const uint32_t g = a.idx[e];
-                    const uint32_t p = in_lds ? raw_merge_find([&](uint32_t i) { return first_lds[i]; }, a.nsrc, g)
-                                              : raw_merge_find([&](uint32_t i) { return a.src[i].first; }, a.nsrc, g);
-                    const RawMergeSrc sp = a.src[p];
-                    raw_load_unaligned(sp.part + raw_merge_src_offset(mc, sp.rows, g - sp.first), dpe, v);
-                }
-            }
-            for (uint32_t q = 0; q < dpe; q++) {
-                const long long l = e * dpe + q - k0;  // where the dword stands in the staged run
-                if (l >= 0 && l <= (long long)RAW_TILE_DWORDS) lds[l] = v[q];
-            }
-        }
-    }
-    __syncthreads();
-    const long long b = s + 16ll * tid;  // the column byte this lane's chunk starts at
-    if (b >= bytes || b + 16 <= 0) return;
-    const uint4 lo = *(const uint4*)&lds[4 * tid];
-    const uint32_t hi = lds[4 * tid + 4];
-    uint4 o;
-    o.x = __builtin_amdgcn_alignbyte(lo.y, lo.x, sh);
-    o.y = __builtin_amdgcn_alignbyte(lo.z, lo.y, sh);
-    o.z = __builtin_amdgcn_alignbyte(lo.w, lo.z, sh);
-    o.w = __builtin_amdgcn_alignbyte(hi, lo.w, sh);
-    uint8_t* const dst = col + b;  // 16-byte aligned by construction
-    if (b >= 0 && b + 16 <= bytes) {
-        *(uint4*)dst = o;
-    } else {  // the column's first or last chunk: only the bytes that are the column's
-        const uint32_t w[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-        for (int i = 0; i < 16; i++)
-            if (b + i >= 0 && b + i < bytes) dst[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-    }
+    raw_write_tile(lds, a.part, a.rows, a.date, a.key, t, [&](uint32_t e, uint32_t* v) {
+        const uint32_t g = a.idx[e];
+        const uint32_t p = in_lds ? raw_merge_find([&](uint32_t i) { return first_lds[i]; }, a.nsrc, g)
+                                  : raw_merge_find([&](uint32_t i) { return a.src[i].first; }, a.nsrc, g);
+        const RawMergeSrc sp = a.src[p];
+        raw_load_unaligned(sp.part + raw_merge_src_offset(mc, sp.rows, g - sp.first), mc.width >> 2, v);
+    });
 }
 
 }  // namespace fa

@@ -5,8 +5,8 @@
 // One merge: everything it needs is allocated first - the second image (as large as the pending bytes: a merged part is never
 // larger than its sources, it has fewer headers and a row count's varuint is no longer than its terms' together), the scratch and
 // the descriptors' staging; a failure there is FA_ERR_NOMEM with nothing changed.  Then the sources' descriptors are copied in,
-// raw_merge_key_kernel reads the keys, one radix sort orders them, raw_parts_kernel lists the Dates, ONE synchronisation brings
-// that list, the host lays the merged parts out and launches one gather per Date (a Date with a single source part is that part:
+// raw_merge_key_kernel reads the keys, the build's order step (raw_order_and_list of raw_host.inc: one radix sort, raw_parts_kernel,
+// ONE synchronisation that brings the Date list) orders them, the host lays the merged parts out and launches one gather per Date (a Date with a single source part is that part:
 // a device copy), and ONE synchronisation ends the call.  Only then the images change places and the pending list is replaced.
 // Memory, kept until fa_raw_reset / fa_destroy: the image that is NOT in use (the old image is KEPT as the next merge's spare,
 // not released), 16 bytes per pending row of keys and indices in and out, 16 bytes per source, the Date list and hipcub's storage.
@@ -83,10 +83,8 @@ extern "C" int fa_raw_merge(fa_ctx* c) {
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));  // (the last build's gather has written the image)
     raw_read_events(t);
-    size_t tmp_sort = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 32, c->stream);
-    const size_t words = align256(((size_t)n + 1) * 4), src_bytes = align256(nsrc * sizeof(RawMergeSrc)), tmp_bytes = align256(tmp_sort);
-    const size_t list_bytes = align256(sizeof(RawPartsHeader) + (size_t)RAW_MAX_DATES * sizeof(RawPartEntry));
+    RawOrder o(c, n);
+    const size_t src_bytes = align256(nsrc * sizeof(RawMergeSrc));
     if (m->spare.bytes() < t->used) {
         DevBuf<uint8_t> image;
         if (!image.grow(std::max(t->used, t->img.bytes()))) {
@@ -95,18 +93,14 @@ extern "C" int fa_raw_merge(fa_ctx* c) {
         }
         m->spare = std::move(image);
     }
-    rc = ensure_dev(c, m->scratch, 4 * words + src_bytes + list_bytes + tmp_bytes, "raw merge scratch");
+    rc = ensure_dev(c, m->scratch, src_bytes + o.bytes(), "raw merge scratch");
     if (rc) return rc;
     if (!m->h_src.grow(src_bytes, src_bytes + src_bytes / 2)) {
         (void)hipGetLastError();
         return fail(c, FA_ERR_NOMEM, "hipHostMalloc(raw merge descriptors) failed; the pending parts are unchanged");
     }
-    uint8_t* sb = (uint8_t*)m->scratch.get();
-    uint32_t *key_in = (uint32_t*)sb, *key = (uint32_t*)(sb + words), *idx_in = (uint32_t*)(sb + 2 * words), *idx = (uint32_t*)(sb + 3 * words);
-    RawMergeSrc* d_src = (RawMergeSrc*)(sb + 4 * words);
-    RawPartsHeader* hdr = (RawPartsHeader*)(sb + 4 * words + src_bytes);
-    RawPartEntry* list = (RawPartEntry*)(hdr + 1);
-    void* tmp = sb + 4 * words + src_bytes + list_bytes;
+    RawMergeSrc* d_src = (RawMergeSrc*)m->scratch.get();  // the descriptors, in front of the order step's scratch
+    o.carve((uint8_t*)m->scratch.get() + src_bytes);
 
     // ---- order
     RawMergeSrc* h_src = (RawMergeSrc*)m->h_src.get();
@@ -115,46 +109,24 @@ extern "C" int fa_raw_merge(fa_ctx* c) {
         h_src[i] = RawMergeSrc{t->img.get() + t->pending[i].offset, (uint32_t)t->pending[i].rows, first};
         first += (uint32_t)t->pending[i].rows;
     }
-    const dim3 grid((n + 1 + 255) / 256), block(256);
     (void)hipEventRecord(m->ev[0], c->stream);
     HIPCHK(c, hipMemcpyAsync(d_src, h_src, nsrc * sizeof(RawMergeSrc), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(hdr, 0, sizeof(RawPartsHeader), c->stream));
-    hipLaunchKernelGGL(raw_merge_key_kernel, grid, block, 0, c->stream, (const RawMergeSrc*)d_src, (uint32_t)nsrc, n, key_in, idx_in);
-    size_t tb = tmp_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint32_t*)key_in, key, (const uint32_t*)idx_in, idx, (int)n, 0, 32, c->stream) != hipSuccess)
-        return fail(c, FA_ERR_HIP, "sort failed");
+    hipLaunchKernelGGL(raw_merge_key_kernel, dim3((n + 1 + 255) / 256), dim3(256), 0, c->stream, (const RawMergeSrc*)d_src, (uint32_t)nsrc, n, o.key_in, o.idx_in);
     // (raw_parts_kernel reads pos[n] alone, the count of good rows: idx_in[n] holds n, every row of a part is good)
-    hipLaunchKernelGGL(raw_parts_kernel, grid, block, 0, c->stream, (const uint32_t*)key, (const uint32_t*)idx_in, n, hdr, list, RAW_MAX_DATES);
-    (void)hipEventRecord(m->ev[1], c->stream);
-    HIPCHK(c, hipGetLastError());
-    uint64_t launches = 3;
-    // ---- the Date list: one small copy, one synchronisation
-    HIPCHK(c, hipMemcpyAsync(t->h_list, hdr, RAW_LIST_FIRST, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const RawPartsHeader h = *(const RawPartsHeader*)t->h_list.get();
+    RawPartsHeader h;
+    std::vector<RawPartEntry> ent;
+    uint64_t launches = 0;
+    rc = raw_order_and_list(c, o, o.idx_in, m->ev[1], &launches, 3, &h, &ent);
+    if (rc) return rc;
     if (h.good != n || h.nparts != dates.size()) return fail(c, FA_ERR_HIP, "internal: the merged Date list does not match the pending parts");
-    std::vector<RawPartEntry> ent(h.nparts);
-    const size_t head = std::min<size_t>(h.nparts, (RAW_LIST_FIRST - sizeof(RawPartsHeader)) / sizeof(RawPartEntry));
-    memcpy(ent.data(), t->h_list.get() + sizeof(RawPartsHeader), head * sizeof(RawPartEntry));
-    if (h.nparts > head) HIPCHK(c, hipMemcpy(ent.data() + head, list + head, (h.nparts - head) * sizeof(RawPartEntry), hipMemcpyDeviceToHost));
-    std::sort(ent.begin(), ent.end(), [](const RawPartEntry& x, const RawPartEntry& y) { return x.start < y.start; });
     // ---- the merged image's layout, then one gather (or one copy) per Date
-    std::vector<fa_raw_part> out;
-    out.reserve(ent.size());
+    std::vector<fa_raw_part> out = raw_lay_out(h, ent, 0);
     size_t used = 0, i = 0;
     for (const auto& d : dates) {  // (ascending Date, as the sorted list is)
-        const uint32_t end = i + 1 < ent.size() ? ent[i + 1].start : n;
-        fa_raw_part p{};
-        p.date = ent[i].t_min / 86400u;
-        p.t_min = ent[i].t_min;
-        p.t_max = i + 1 < ent.size() ? ent[i + 1].prev_t_max : h.last_t_max;
-        p.rows = end - ent[i].start;
-        p.offset = used;
-        p.bytes = fa_raw_part_bytes(p.rows);
+        const fa_raw_part& p = out[i++];
         if (p.date != d.first || p.rows != d.second.rows || p.t_min != d.second.t_min || p.t_max != d.second.t_max)
             return fail(c, FA_ERR_HIP, "internal: the merged Date list does not match the pending parts");
-        out.push_back(p);
-        used += p.bytes, i++;
+        used += p.bytes;
     }
     (void)hipEventRecord(m->ev[2], c->stream);
     for (i = 0; i < out.size(); i++) {
@@ -166,14 +138,11 @@ extern "C" int fa_raw_merge(fa_ctx* c) {
         }
         RawMergeArgs a{};
         a.part = m->spare.get() + p.offset;
-        a.key = key + ent[i].start;
-        a.idx = idx + ent[i].start;
+        a.key = o.key + ent[i].start;
+        a.idx = o.idx + ent[i].start;
         a.src = d_src;
         a.nsrc = (uint32_t)nsrc, a.rows = (uint32_t)p.rows, a.date = p.date;
-        uint64_t tiles = 0;
-        for (uint32_t col = 0; col < RAW_NCOLS; col++)
-            tiles += raw_col_tiles((uint64_t)(uintptr_t)(a.part + raw_col_offset(RAW_COLS_H, p.rows, col) + raw_col_header_len(RAW_COLS_H[col])), p.rows * RAW_COLS_H[col].width);
-        hipLaunchKernelGGL(raw_merge_gather_kernel, dim3((unsigned)tiles), dim3(RAW_BLOCK), 0, c->stream, a);
+        hipLaunchKernelGGL(raw_merge_gather_kernel, raw_part_grid(a.part, p.rows), dim3(RAW_BLOCK), 0, c->stream, a);
         HIPCHK(c, hipGetLastError());
         launches++;
     }

@@ -1,9 +1,11 @@
 // host_raw_merge.hip - host instantiation of the two __host__ __device__ lookups of csrc/raw_merge.cuh (raw_merge_find: global row
 // -> source; raw_merge_col / raw_merge_src_offset: (source rows, column, row) -> byte offset in the source), the text
-// raw_merge_key_kernel and raw_merge_gather_kernel run, and a host model of the gather's tile walk.  TEST INFRASTRUCTURE
+// raw_merge_key_kernel and raw_merge_gather_kernel run, and of the part writer's geometry of csrc/raw.cuh (the tile walk and the
+// LDS staging, enumerated with the functions raw_write_tile computes them by).  TEST INFRASTRUCTURE
 // (tests/test_raw_merge_cpu.py).  No GPU call.  Prints "OK <checks>" or the first failure and exits 1.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -52,9 +54,10 @@ static void check_offsets(uint64_t rows) {
     }
 }
 
-// The gather's tile walk: workgroup -> (column, tile) as the kernel finds them, lane -> its aligned 16-byte chunk, whole chunks
-// as one store and a column's first and last chunk as byte stores, the headers from the column's first tile.  A part of `rows`
-// rows whose first byte has the address phase `base` (mod 16): every byte is written exactly once, every wide store is aligned.
+// The part writer's tile walk, enumerated with the geometry functions the kernels run (csrc/raw.cuh): workgroup -> (column, tile),
+// lane -> its aligned 16-byte chunk, whole chunks as one store and a column's first and last chunk as byte stores, the headers
+// from the column's first tile.  A part of `rows` rows whose first byte has the address phase `base` (mod 16): every byte is
+// written exactly once, every wide store is aligned.
 static void check_tiles(uint64_t rows, uint32_t base) {
     const uint64_t size = raw_col_offset(RAW_COLS_H, rows, RAW_NCOLS);
     std::vector<uint8_t> hits(size, 0);
@@ -62,44 +65,73 @@ static void check_tiles(uint64_t rows, uint32_t base) {
         CHECK(at >= 0 && (uint64_t)at < size, "rows %llu base %u: %s outside the part at %lld", (unsigned long long)rows, base, what, at);
         hits[at]++;
     };
-    uint64_t blocks = 0;
-    for (uint32_t c = 0; c < RAW_NCOLS; c++)
-        blocks += raw_col_tiles(base + raw_col_offset(RAW_COLS_H, rows, c) + raw_col_header_len(RAW_COLS_H[c]), rows * RAW_COLS_H[c].width);
+    const uint64_t blocks = raw_part_tiles(RAW_COLS_H, base, rows);
+    RawTile t;
+    CHECK(!raw_tile_locate(RAW_COLS_H, base, rows, blocks, &t), "rows %llu base %u: a tile behind the last one", (unsigned long long)rows, base);
     for (uint64_t block = 0; block < blocks; block++) {
-        uint64_t tile = block, off = 1 + raw_varuint_len(rows);
-        uint32_t c = 0;
-        for (;; c++) {
-            CHECK(c < RAW_NCOLS, "rows %llu base %u: block %llu has no column", (unsigned long long)rows, base, (unsigned long long)block);
-            const RawColDef& d = RAW_COLS_H[c];
-            const uint64_t data = off + raw_col_header_len(d), bytes = rows * d.width;
-            const uint64_t tiles = raw_col_tiles(base + data, bytes);
-            if (tile < tiles) break;
-            tile -= tiles;
-            off = data + bytes;
-        }
-        const RawColDef& d = RAW_COLS_H[c];
+        CHECK(raw_tile_locate(RAW_COLS_H, base, rows, block, &t), "rows %llu base %u: block %llu has no column", (unsigned long long)rows, base, (unsigned long long)block);
+        const RawColDef& d = RAW_COLS_H[t.c];
         const uint32_t hl = raw_col_header_len(d);
-        CHECK(off == raw_col_offset(RAW_COLS_H, rows, c), "rows %llu: column %u found at %llu", (unsigned long long)rows, c, (unsigned long long)off);
-        const long long col = (long long)(off + hl), bytes = (long long)(rows * d.width);
-        if (tile == 0) {
-            for (uint32_t t = 0; t < hl; t++) hit((long long)off + t, "a column header byte");
-            if (c == 0)
-                for (uint32_t t = 0; t < 1 + raw_varuint_len(rows); t++) hit(t, "a block header byte");
+        CHECK(t.off == raw_col_offset(RAW_COLS_H, rows, t.c), "rows %llu: column %u found at %llu", (unsigned long long)rows, t.c, (unsigned long long)t.off);
+        const long long col = (long long)(t.off + hl), bytes = (long long)(rows * d.width);
+        if (t.tile == 0) {
+            for (uint32_t i = 0; i < hl; i++) hit((long long)t.off + i, "a column header byte");
+            if (t.c == 0)
+                for (uint32_t i = 0; i < 1 + raw_varuint_len(rows); i++) hit(i, "a block header byte");
         }
-        const long long s = (long long)tile * (RAW_TILE_CHUNKS * 16) - (long long)((base + col) & 15);
+        const RawTilePhase ph = raw_tile_phase(base + col, t.tile);
         for (uint32_t tid = 0; tid < RAW_BLOCK; tid++) {
-            const long long b = s + 16ll * tid;
-            if (b >= bytes || b + 16 <= 0) continue;
-            if (b >= 0 && b + 16 <= bytes) {
-                CHECK(((base + col + b) & 15) == 0, "rows %llu base %u column %u: a 16-byte store at phase %lld", (unsigned long long)rows, base, c, (base + col + b) & 15);
+            const long long b = raw_lane_byte(ph.s, tid);
+            if (raw_chunk_outside(b, bytes)) continue;
+            if (raw_chunk_whole(b, bytes)) {
+                CHECK(((base + col + b) & 15) == 0, "rows %llu base %u column %u: a 16-byte store at phase %lld", (unsigned long long)rows, base, t.c, (base + col + b) & 15);
                 for (int i = 0; i < 16; i++) hit(col + b + i, "a whole chunk");
             } else {
                 for (int i = 0; i < 16; i++)
-                    if (b + i >= 0 && b + i < bytes) hit(col + b + i, "a partial chunk");
+                    if (raw_chunk_byte_in(b, i, bytes)) hit(col + b + i, "a partial chunk");
             }
         }
     }
     for (uint64_t i = 0; i < size; i++) CHECK(hits[i] == 1, "rows %llu base %u: byte %llu written %u times", (unsigned long long)rows, base, (unsigned long long)i, hits[i]);
+}
+
+// The staging of every tile of every column but Date, with the functions the writer stages by: the (element, dword) pairs it
+// writes to LDS slots.  Every slot that a lane with a chunk inside the column reads (4 tid .. 4 tid + 4) and that holds a byte of
+// the column is written exactly once, by the (e, q) with 0 <= e < rows that the column's byte stream puts there.  (That
+// nothing is staged outside the slots 0 .. RAW_TILE_DWORDS is raw_stage_holds' own bound, the writer's guard; here it is only held
+// against the vectors' size.)
+static void check_staging(uint64_t rows, uint32_t base) {
+    const uint64_t blocks = raw_part_tiles(RAW_COLS_H, base, rows);
+    std::vector<uint32_t> writes(RAW_TILE_DWORDS + 1);
+    std::vector<long long> dword(RAW_TILE_DWORDS + 1);  // e * dpe + q of the slot's writer
+    for (uint64_t block = 0; block < blocks; block++) {
+        RawTile t;
+        CHECK(raw_tile_locate(RAW_COLS_H, base, rows, block, &t), "rows %llu base %u: block %llu has no column", (unsigned long long)rows, base, (unsigned long long)block);
+        const RawColDef& d = RAW_COLS_H[t.c];
+        if (d.kind == RAW_K_DATE) continue;
+        const uint32_t dpe = d.width >> 2;
+        const long long bytes = (long long)(rows * d.width);
+        const RawTilePhase ph = raw_tile_phase(base + t.off + raw_col_header_len(d), t.tile);
+        std::fill(writes.begin(), writes.end(), 0u);
+        const long long e0 = raw_stage_first(ph.k0, dpe);
+        for (uint32_t j = 0; j < raw_stage_count(dpe); j++)
+            for (uint32_t q = 0; q < dpe; q++) {
+                const long long e = e0 + j, l = raw_stage_slot(e, dpe, q, ph.k0);
+                if (!raw_stage_holds(l)) continue;  // (the writer's own guard: what it lets through must fit the vectors here)
+                CHECK(l >= 0 && (size_t)l < writes.size(), "rows %llu base %u column %u tile %llu: slot %lld", (unsigned long long)rows, base, t.c, (unsigned long long)t.tile, l);
+                writes[l]++;
+                dword[l] = e >= 0 && e < (long long)rows ? e * dpe + q : -1;  // (an element outside the column stages zeroes)
+            }
+        for (uint32_t tid = 0; tid < RAW_BLOCK; tid++) {
+            if (raw_chunk_outside(raw_lane_byte(ph.s, tid), bytes)) continue;
+            for (uint32_t l = 4 * tid; l <= 4 * tid + 4; l++) {
+                const long long k = ph.k0 + l;  // the column's dword the slot stands for: bytes 4 k .. 4 k + 3
+                if (4 * k + 3 < 0 || 4 * k >= bytes) continue;
+                CHECK(writes[l] == 1 && dword[l] == k, "rows %llu base %u column %u tile %llu: slot %u written %u times, by dword %lld, the column's is %lld", (unsigned long long)rows,
+                      base, t.c, (unsigned long long)t.tile, l, writes[l], dword[l], k);
+            }
+        }
+    }
 }
 
 int main() {
@@ -121,9 +153,9 @@ int main() {
     }
     // ---- (rows, column, row) -> offset
     for (uint32_t r : all) check_offsets(r);
-    // ---- the tile walk over the merged row counts of the GPU test, at every address phase of the part's first byte
+    // ---- the tile walk and the staging over the merged row counts of the GPU test, at every address phase of the part's first byte
     for (uint32_t rows : {1u, 2u, 127u, 128u, 129u, 255u, 256u, 257u, 1023u, 1024u, 1025u, 16383u, 16384u})
-        for (uint32_t base = 0; base < 16; base++) check_tiles(rows, base);
+        for (uint32_t base = 0; base < 16; base++) check_tiles(rows, base), check_staging(rows, base);
     printf("OK %llu\n", checks);
     return 0;
 }

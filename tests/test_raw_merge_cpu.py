@@ -1,8 +1,9 @@
 """CPU tests of the merge of pending flows_raw parts (include/flowagg.h "merging the pending flows_raw parts").
 
 tests/host_raw_merge.hip instantiates the two __host__ __device__ lookups of csrc/raw_merge.cuh on the host - the text the
-kernels run - against a linear scan and against raw_col_offset arithmetic, and walks a host model of the gather's tiles over the
-merged row counts of the GPU test.  It is built plain and with the host's AddressSanitizer + UBSan and run as a program.  The
+kernels run - against a linear scan and against raw_col_offset arithmetic, and enumerates the part writer's tile walk and LDS
+staging with the geometry functions of csrc/raw.cuh (again the kernels' text) over the merged row counts of the GPU test.  It is
+built plain and with the host's AddressSanitizer + UBSan and run as a program.  The
 library's part: the two new symbols are exported and the ABI is still 8.  No GPU needed."""
 import os
 import re
