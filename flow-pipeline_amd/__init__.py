@@ -123,6 +123,14 @@ class RawLoadStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RollupStats(C.Structure):
+    """fa_rollup_stats_t: what the ctx's rollup folds (rollup_fold_columns, raw_load_rollup) have done so far."""
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "records_in", "records_bad", "records_folded", "launches", "fold_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class RawMergeStats(C.Structure):
     """fa_raw_merge_stats_t: what the ctx's merges of pending parts (raw_merge) have done so far."""
     _fields_ = [(n, C.c_uint64) for n in (
@@ -212,6 +220,7 @@ EXPORTS = [
     "fa_raw_reset", "fa_raw_stats", "fa_raw_merge", "fa_raw_merge_stats",
     "fa_raw_take_lz4", "fa_raw_take_lz4_device", "fa_lz4_frame_device", "fa_lz4_frame", "fa_lz4_frame_bound", "fa_raw_lz4_stats",
     "fa_lz4_decode", "fa_lz4_decode_device", "fa_raw_columns_device", "fa_raw_load", "fa_raw_load_stats", "fa_raw_load_reset",
+    "fa_rollup_fold_columns_device", "fa_raw_load_rollup", "fa_rollup_stats",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -416,6 +425,9 @@ def lib():
     L.fa_raw_load.argtypes = [vp, vp, sz]
     L.fa_raw_load_stats.argtypes = [vp, C.POINTER(RawLoadStats)]
     L.fa_raw_load_reset.argtypes = [vp]
+    L.fa_rollup_fold_columns_device.argtypes = [vp, C.POINTER(Columns), sz, u32]
+    L.fa_raw_load_rollup.argtypes = [vp, vp, sz, u32, C.c_int]
+    L.fa_rollup_stats.argtypes = [vp, C.POINTER(RollupStats)]
     L.fa_raw_merge.argtypes = [vp]
     L.fa_raw_merge_stats.argtypes = [vp, C.POINTER(RawMergeStats)]
     _LIB = L
@@ -1002,6 +1014,23 @@ class FlowAgg:
     def raw_load_stats(self) -> dict:
         s = RawLoadStats()
         self._chk(self._L.fa_raw_load_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
+    # -- the rollups from columns and from parts (include/flowagg.h, the section of that name) ----
+    def rollup_fold_columns(self, cols: Columns, n: int, key_sets: int = 0):
+        """n decoded records (device pointers) into flows_5m and the exact dashboard key sets: what an ingest of the same records
+        leaves.  key_sets: 0 = every exact key set of the ctx, or a subset of them (a sketch bit: FlowAggError -8).  Synchronous."""
+        self._chk(self._L.fa_rollup_fold_columns_device(self._h, C.byref(cols) if cols is not None else None, n, key_sets))
+
+    def raw_load_rollup(self, data, key_sets: int = 0, folds: bool = False):
+        """Every part of `data` (what raw_take_lz4 or raw_take delivered) into flows_5m and the exact dashboard key sets;
+        folds=True: also into the enabled talker and port folds, as raw_load does.  A refused input (FlowAggError -7) folds nothing."""
+        a = _host_bytes(data)
+        self._chk(self._L.fa_raw_load_rollup(self._h, a.ctypes.data if a.size else None, a.size, key_sets, 1 if folds else 0))
+
+    def rollup_stats(self) -> dict:
+        s = RollupStats()
+        self._chk(self._L.fa_rollup_stats(self._h, C.byref(s)))
         return s.as_dict()
 
     def raw_reset(self):

@@ -24,6 +24,8 @@
 //                 emit order; hash partition of a row set for the multi-GPU close (row_partition_kernel);
 //   talkers.cuh   exact GROUP BY SrcAddr / DstAddr (opt-in second pass): the decoded columns folded into two tables of their own;
 //   ports.cuh     exact GROUP BY SrcPort / DstPort per time bucket, the same way; keytab.cuh is the table core under both;
+//   rollup.cuh    decoded columns -> flows_5m and the dashboard key sets (a loaded flows_raw part, a decode): the view of create.sh:92-110
+//                 run again over flows_raw, into the tables the ingest feeds;
 //   maintenance.cuh  table scans, rebuilds, the wide log's reads / folds / drops (wdrop_kernel: a close zeroes sums in place).
 //
 // Roofline: HBM-bound integer/byte work; algorithmic bytes = wire bytes, read
@@ -38,3 +40,4 @@
 #include "framing.cuh"
 #include "talkers.cuh"
 #include "ports.cuh"
+#include "rollup.cuh"

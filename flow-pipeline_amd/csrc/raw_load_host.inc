@@ -6,8 +6,9 @@
 // rows and verdict; ONE copy brings every block's status and every part's verdict back and the stream is waited for ONCE.
 // Everything is validated there, before the first unpack or fold launch: a refused call folds nothing.  Then, per part and in
 // chunks of at most the enabled folds' caps: raw_unpack_kernel into the ctx's column chunk, fold_chunk_cols (second_pass.inc).
-// raw_build_cols is never called: loading parts does not produce parts, and flows_5m, the wide table and the sketches are fed
-// from wire bytes only.
+// raw_build_cols is never called: loading parts does not produce parts.  fa_raw_load touches neither flows_5m nor the wide table;
+// the door that feeds them from the same front half (load_prepare, load_columns, load_unpack) is fa_raw_load_rollup
+// (rollup_host.inc).  The sketches are fed from wire bytes only.
 // Memory (LoadState, kept until fa_raw_reset / fa_destroy): the input's copy, 64 KiB per block of decoded image, 40 bytes per
 // block and 48 per part of plan and verdicts, one chunk of columns.
 

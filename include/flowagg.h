@@ -655,7 +655,8 @@ int fa_raw_lz4_stats(fa_ctx*, fa_raw_lz4_stats_t* out);
  * validated before the first fold is launched - and the ctx stays usable.
  * NOT inspected: the column VALUES (that Date matches TimeReceived, that TimeReceived is sorted).  NOT fed: loading never builds
  * parts again (a ctx with fa_raw_enable gets no pending part from a load) and never touches flows_5m, the wide table or the
- * sketches - those are fed from wire bytes only; the minute series from parts is a follow-up.
+ * sketches - fa_raw_load_rollup below ("the rollups from columns and from parts") is the door that feeds flows_5m and the exact
+ * dashboard key sets, the minute series among them, from parts; the sketches are fed from wire bytes only.
  * Memory, allocated on first use, kept until fa_raw_load_reset / fa_raw_reset / fa_destroy: the compressed copy, 64 KiB per block of decoded image,
  * one chunk of columns (117 bytes per row).  FA_ERR_NOMEM leaves the ctx usable; a caller with a large file loads it in
  * pieces cut at frame boundaries. */
@@ -663,7 +664,7 @@ typedef struct {
     uint64_t offset, bytes; /* one frame's decoded bytes inside *d_out; offset is a multiple of 65536 */
 } fa_lz4_span;
 typedef struct {
-    uint64_t calls;                   /* fa_lz4_decode_device + fa_raw_columns_device + fa_raw_load calls that succeeded */
+    uint64_t calls;                   /* fa_lz4_decode_device + fa_raw_columns_device + fa_raw_load (+ fa_raw_load_rollup) calls whose input was accepted */
     uint64_t frames, blocks, stored_blocks;
     uint64_t bytes_in, bytes_decoded; /* input bytes (plain parts included); bytes that left lz4_decode_kernel */
     uint64_t parts, rows_loaded;      /* parts unpacked; rows handed to the folds by fa_raw_load */
@@ -721,6 +722,47 @@ typedef struct {
 int fa_raw_merge(fa_ctx*);
 /* All zero before the first merge; fa_raw_reset releases the merge's buffers, the counters go on counting. */
 int fa_raw_merge_stats(fa_ctx*, fa_raw_merge_stats_t* out);
+
+/* ---- ABI 8, addition: the rollups from columns and from parts ---------------------- */
+/* In the reference flows_5m is fed by a materialized view that fires on every block inserted into flows_raw
+ * (compose/clickhouse/create.sh:92-110): whoever holds flows_raw can get the rollup back (INSERT INTO flows_5m SELECT ... FROM
+ * flows_raw), at another granularity too, and the per-minute panel and both port panels read flows_raw itself
+ * (viz-ch.json:74,358,604).  These doors are that step: decoded columns - already in HBM, or unpacked from flows_raw parts - are
+ * folded into the ctx's flows_5m table and its exact dashboard key sets (FA_KEYS_AS_PAIR, FA_KEYS_ADDR_PORT_PROTO,
+ * FA_KEYS_PORT_HIST, FA_KEYS_MINUTE_SERIES) by rollup_fold_kernel (csrc/rollup.cuh), through the table helpers the ingest kernels
+ * use: every selected key set's state is what an ingest of the same records leaves, bit for bit, under the ctx's own
+ * window_secs / subwindow_secs (parts written by a 300 s ctx re-roll at 3600 s).  Sums commute: a fold on top of ingested state
+ * adds to it.  Records with status != 0 are skipped (inserter.go:125-126); a record below a closed flows_5m window is folded
+ * and counted in fa_stats.records_late, as an ingested one is.
+ * key_sets: 0 = every exact key set the ctx was created with; otherwise a subset of those - a bit the ctx was not created with
+ * is FA_ERR_ARG, a sketch bit (FA_KEYS_SRCADDR_CMS, FA_KEYS_DSTADDR_CMS) FA_ERR_UNSUPPORTED: the sketches and the
+ * distinct-address sets are fed from wire bytes only.
+ * Both doors are synchronous and end in the settle every read starts with: table growth and the replay of parked updates have
+ * happened and fa_last_error is meaningful when they return.  fa_stats.records_ok / records_bad / bytes_in do not move (they
+ * count wire records); table_used, wide_used, table_capacity, wide_capacity and records_late do, as after any settle.
+ * Additive: a ctx that never calls these functions runs the code it ran.  NOT built: sketches from columns, a group door (a
+ * loaded ctx is a group member like any other), a consumer flag. */
+typedef struct {
+    uint64_t calls;                   /* fa_rollup_fold_columns_device + fa_raw_load_rollup calls that succeeded */
+    uint64_t records_in, records_bad; /* records handed to fold launches; of them status != 0, skipped */
+    uint64_t records_folded;          /* records_in - records_bad */
+    uint64_t launches;                /* rollup_fold_kernel launches (one per chunk) */
+    uint64_t fold_ns;                 /* hipEvent time of those launches */
+} fa_rollup_stats_t;
+/* n records of `cols` - DEVICE pointers; status and every column the key sets read are needed, and every pointer given must be
+ * naturally aligned (8 / 4 / 16 / 1 bytes): FA_ERR_ARG otherwise.  Read: TimeReceived, Bytes, status always; Packets, SrcAS,
+ * DstAS, EType (flows_5m); SrcAddr, DstPort, Proto, Packets ((SrcAddr,DstPort,Proto)); SrcPort, DstPort, SamplingRate (ports);
+ * TimeFlowStart, SamplingRate (minutes).  n == 0 is FA_OK without a launch.  Chunks of at most max_batch_records and of what the
+ * spill buffers hold if every update of a chunk parks.  The columns are not referenced after the call. */
+int fa_rollup_fold_columns_device(fa_ctx*, const fa_columns* cols, size_t n, uint32_t key_sets);
+/* fa_raw_load's input contract and front half - LZ4 frames or plain Native parts in HOST memory, everything validated before
+ * the first fold, FA_ERR_FRAMING with the reason and the byte position, A REFUSED CALL FOLDS NOTHING - and then every chunk of
+ * every part through the fold above.  folds != 0: each chunk also goes to the enabled talker and port folds, as fa_raw_load sends
+ * it (chunks then also keep to those folds' caps); FA_ERR_UNSUPPORTED if neither fold is enabled.  Counted in fa_raw_load_stats
+ * (calls, parts, rows_loaded, unpack_ns; fold_ns there covers every fold of a chunk) and in fa_rollup_stats. */
+int fa_raw_load_rollup(fa_ctx*, const uint8_t* bytes, size_t n, uint32_t key_sets, int folds);
+/* The counters of this ctx's rollup folds; works on any ctx (all zero before the first call). */
+int fa_rollup_stats(fa_ctx*, fa_rollup_stats_t* out);
 
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):

@@ -1,0 +1,45 @@
+"""CPU tests of the rollups from columns and from parts (include/flowagg.h "the rollups from columns and from parts").
+
+tests/host_rollup.hip instantiates on the host what the fold decides without a GPU: the slice geometry of rollup_fold_kernel
+(csrc/rollup.cuh, the text the kernel runs) - every record of a chunk visited exactly once, one trip count for the whole grid -,
+the chunk bound and the key-set mask check of csrc/rollup_plan.h.  It is built plain and with the host's AddressSanitizer +
+UBSan and run as a program.  The library's part: the three new symbols are exported and the ABI is still 8.  No GPU needed."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SANITIZE = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-Xarch_host", "-g"]
+
+
+def _program(sanitize):
+    out = os.path.join(ROOT, "tests", "_build")
+    os.makedirs(out, exist_ok=True)
+    exe = os.path.join(out, "host_rollup" + ("_san" if sanitize else ""))
+    src = os.path.join(ROOT, "tests", "host_rollup.hip")
+    deps = [src] + [os.path.join(ROOT, "flow-pipeline_amd", "csrc", f) for f in ("rollup.cuh", "rollup_plan.h", "sinks.cuh", "table.cuh", "wide.cuh")]
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1" if sanitize else "-O2", "-std=c++17"] + (SANITIZE if sanitize else []) + ["-o", exe, src])
+    return exe
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan+ubsan"])
+def test_slices_chunks_masks(sanitize):
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")  # (the process loads the HIP runtime, which keeps its allocations)
+    res = subprocess.run([_program(sanitize)], capture_output=True, text=True, timeout=900, env=env)
+    assert res.returncode == 0 and res.stdout.startswith("OK "), res.stdout + res.stderr[-4000:]
+    assert int(re.findall(r"\d+", res.stdout)[0]) > 10 ** 6  # the slice, chunk and mask checks all ran
+
+
+def test_library_exports_the_rollup_doors(fa):
+    if not os.path.exists(fa.LIB_PATH):
+        fa.build()
+    L = fa.lib()
+    assert L.fa_abi_version() == 8
+    for name in ("fa_rollup_fold_columns_device", "fa_raw_load_rollup", "fa_rollup_stats"):
+        assert getattr(L, name) is not None
+    assert [n for n, _ in fa.RollupStats._fields_] == ["calls", "records_in", "records_bad", "records_folded", "launches", "fold_ns"]
+    assert C.sizeof(fa.RollupStats) == 48
