@@ -131,6 +131,14 @@ class RollupStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class SketchFoldStats(C.Structure):
+    """fa_sketch_fold_stats_t: what the ctx's sketch folds (sketch_fold_columns, raw_restore) have done so far."""
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "records_in", "records_bad", "records_folded", "batches", "launches", "fold_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class RawMergeStats(C.Structure):
     """fa_raw_merge_stats_t: what the ctx's merges of pending parts (raw_merge) have done so far."""
     _fields_ = [(n, C.c_uint64) for n in (
@@ -221,6 +229,7 @@ EXPORTS = [
     "fa_raw_take_lz4", "fa_raw_take_lz4_device", "fa_lz4_frame_device", "fa_lz4_frame", "fa_lz4_frame_bound", "fa_raw_lz4_stats",
     "fa_lz4_decode", "fa_lz4_decode_device", "fa_raw_columns_device", "fa_raw_load", "fa_raw_load_stats", "fa_raw_load_reset",
     "fa_rollup_fold_columns_device", "fa_raw_load_rollup", "fa_rollup_stats",
+    "fa_sketch_fold_columns_device", "fa_raw_restore", "fa_sketch_fold_stats",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -428,6 +437,9 @@ def lib():
     L.fa_rollup_fold_columns_device.argtypes = [vp, C.POINTER(Columns), sz, u32]
     L.fa_raw_load_rollup.argtypes = [vp, vp, sz, u32, C.c_int]
     L.fa_rollup_stats.argtypes = [vp, C.POINTER(RollupStats)]
+    L.fa_sketch_fold_columns_device.argtypes = [vp, C.POINTER(Columns), sz, u32]
+    L.fa_raw_restore.argtypes = [vp, vp, sz, u32, C.c_int]
+    L.fa_sketch_fold_stats.argtypes = [vp, C.POINTER(SketchFoldStats)]
     L.fa_raw_merge.argtypes = [vp]
     L.fa_raw_merge_stats.argtypes = [vp, C.POINTER(RawMergeStats)]
     _LIB = L
@@ -1031,6 +1043,25 @@ class FlowAgg:
     def rollup_stats(self) -> dict:
         s = RollupStats()
         self._chk(self._L.fa_rollup_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
+    # -- the sketches from columns and from parts (include/flowagg.h, the section of that name) ----
+    def sketch_fold_columns(self, cols: Columns, n: int, key_sets: int = 0):
+        """n decoded records (device pointers) into the address sketches and the distinct-address sets behind topk: what an ingest
+        of the same records leaves.  key_sets: 0 = every sketch of the ctx, or a subset of them (any other bit: FlowAggError -1).
+        In the candidates mode every chunk of at most max_batch_records is one batch.  Synchronous."""
+        self._chk(self._L.fa_sketch_fold_columns_device(self._h, C.byref(cols) if cols is not None else None, n, key_sets))
+
+    def raw_restore(self, data, key_sets: int = 0, folds: bool = False):
+        """Every part of `data` (what raw_take_lz4 or raw_take delivered) into everything selected: key_sets = 0 is every key set
+        of the ctx, exact ones and sketches alike, or a subset; folds=True: also the enabled talker and port folds.  Each chunk
+        is unpacked once.  A refused input (FlowAggError -7) folds nothing."""
+        a = _host_bytes(data)
+        self._chk(self._L.fa_raw_restore(self._h, a.ctypes.data if a.size else None, a.size, key_sets, 1 if folds else 0))
+
+    def sketch_fold_stats(self) -> dict:
+        s = SketchFoldStats()
+        self._chk(self._L.fa_sketch_fold_stats(self._h, C.byref(s)))
         return s.as_dict()
 
     def raw_reset(self):

@@ -37,6 +37,7 @@
 #include "raw.cuh"
 #include "raw_merge.cuh"
 #include "rollup_plan.h"
+#include "sketch_plan.h"
 #include "table_room.h"
 
 using namespace fa;
@@ -234,6 +235,7 @@ struct fa_ctx {
     struct Lz4State* lz4 = nullptr;     // LZ4 frames (lz4_host.inc), nullptr until the first fa_raw_take_lz4 / fa_lz4_frame_device
     struct LoadState* load = nullptr;   // loading parts back (raw_load_host.inc), nullptr until the first decode / load call
     struct RollupState* rollup = nullptr;  // the rollups from columns and from parts (rollup_host.inc), nullptr until the first fold
+    struct SketchFoldState* sketch_fold = nullptr;  // the sketches from columns and from parts (sketch_fold_host.inc), nullptr until the first fold
 
     fa_stats_t stats{};
     uint64_t used_base = 0;  // groups created before the current counter epoch
@@ -278,6 +280,7 @@ static void lz4_release(fa_ctx* c);
 static void load_destroy(fa_ctx* c);
 static void load_release(fa_ctx* c);
 static void rollup_destroy(fa_ctx* c);
+static void sketch_fold_destroy(fa_ctx* c);
 
 extern "C" uint32_t fa_abi_version(void) { return FA_ABI_VERSION; }
 
@@ -572,6 +575,7 @@ extern "C" void fa_destroy(fa_ctx* c) {
     lz4_destroy(c);
     load_destroy(c);
     rollup_destroy(c);
+    sketch_fold_destroy(c);
     const hipStream_t streams[3] = {c->copy_stream, c->cand_stream, c->stream};
     delete c;  // every buffer is released here (fa_ctx's members own them): before the streams go, as ever
     for (hipStream_t s : streams)
@@ -611,6 +615,7 @@ static bool bucket_range(const fa_ctx* c, uint32_t timeslot, uint32_t& lo, uint3
 #include "second_pass.inc"
 #include "raw_load_host.inc"
 #include "rollup_host.inc"
+#include "sketch_fold_host.inc"
 
 extern "C" int fa_stats(fa_ctx* c, fa_stats_t* out) {
     FA_ON_DEVICE(c);

@@ -19,6 +19,19 @@ static void launch_wave_tiles(fa_ctx* c, const KArgs& a, const LaunchPlan& p) {
         if (p.seq_variant) return launch_wtile<1u, true>(c, a, p);
     launch_wtile<KS>(c, a, p);
 }
+// candidates mode: the boundary behind a batch - an ingest launch or a chunk of a sketch fold from columns (sketch_fold_host.inc) -
+// on the ctx stream, behind every kernel of the batch that adds to a sketch: theta of this boundary and the bits the NEXT batch
+// tests its addresses against.
+static int cand_boundary(fa_ctx* c) {
+    HIPCHK(c, hipMemsetAsync(c->cand_state, 0, 2 * sizeof(CandState), c->stream));
+    const dim3 gs(CAND_SCAN_BLOCKS, 2), gb(256, 2);
+    hipLaunchKernelGGL(cand_scan_kernel, gs, dim3(256), 0, c->stream, c->ks_src, c->ks_dst, 1u << c->ks_log2, (const unsigned long long*)c->cms_src,
+                       (const unsigned long long*)c->cms_dst, c->cfg.cms_depth, c->cfg.cms_width_log2, c->cfg.cms_seed, c->cand_state, c->cand_chunkmax);
+    hipLaunchKernelGGL(cand_bits_kernel, gb, dim3(256), 0, c->stream, (const KeySlot*)c->ks_src, (const KeySlot*)c->ks_dst, (const unsigned long long*)c->cms_src,
+                       (const unsigned long long*)c->cms_dst, c->cfg.cms_depth, c->cfg.cms_width_log2, c->cfg.topk_track, std::max(c->ks_log2, 8u) - 2u, c->cand_state,
+                       c->cand_bits[0], c->cand_bits[1]);
+    return FA_OK;
+}
 // Launch order on the ctx stream: tile -> deferred -> [agg]   (the wave-tile kernel finds the batch's time base itself).
 template <int MODE>
 static int launch_tiles(fa_ctx* c, KArgs& a, const LaunchPlan& p, fa_ctx::LaunchEvents* ev) {
@@ -78,13 +91,8 @@ static int launch_tiles(fa_ctx* c, KArgs& a, const LaunchPlan& p, fa_ctx::Launch
         // candidates mode: the launch boundary - theta of this boundary and the bits the NEXT launch tests its addresses against
         // (behind every kernel of the launch that adds to a sketch: hot-address flushes, the atomic paths, cms_agg_kernel)
         if (MODE == MODE_INGEST && c->cand_state) {
-            HIPCHK(c, hipMemsetAsync(c->cand_state, 0, 2 * sizeof(CandState), c->stream));
-            const dim3 gs(CAND_SCAN_BLOCKS, 2), gb(256, 2);
-            hipLaunchKernelGGL(cand_scan_kernel, gs, dim3(256), 0, c->stream, c->ks_src, c->ks_dst, 1u << c->ks_log2, (const unsigned long long*)c->cms_src,
-                               (const unsigned long long*)c->cms_dst, c->cfg.cms_depth, c->cfg.cms_width_log2, c->cfg.cms_seed, c->cand_state, c->cand_chunkmax);
-            hipLaunchKernelGGL(cand_bits_kernel, gb, dim3(256), 0, c->stream, (const KeySlot*)c->ks_src, (const KeySlot*)c->ks_dst, (const unsigned long long*)c->cms_src,
-                               (const unsigned long long*)c->cms_dst, c->cfg.cms_depth, c->cfg.cms_width_log2, c->cfg.topk_track, std::max(c->ks_log2, 8u) - 2u, c->cand_state,
-                               c->cand_bits[0], c->cand_bits[1]);
+            const int brc = cand_boundary(c);
+            if (brc) return brc;
         }
         // fold the (SrcAddr,DstPort,Proto) tuples: one workgroup per table region, plain loads and stores - behind every
         // dispatch of this launch that updates the wide table with atomics (wagg.cuh)

@@ -26,6 +26,7 @@
 //   ports.cuh     exact GROUP BY SrcPort / DstPort per time bucket, the same way; keytab.cuh is the table core under both;
 //   rollup.cuh    decoded columns -> flows_5m and the dashboard key sets (a loaded flows_raw part, a decode): the view of create.sh:92-110
 //                 run again over flows_raw, into the tables the ingest feeds;
+//   sketch_fold.cuh  decoded columns -> the two address sketches and the distinct-address sets behind fa_topk (the same sources);
 //   maintenance.cuh  table scans, rebuilds, the wide log's reads / folds / drops (wdrop_kernel: a close zeroes sums in place).
 //
 // Roofline: HBM-bound integer/byte work; algorithmic bytes = wire bytes, read
@@ -41,3 +42,4 @@
 #include "talkers.cuh"
 #include "ports.cuh"
 #include "rollup.cuh"
+#include "sketch_fold.cuh"

@@ -8,7 +8,7 @@
 // chunks of at most the enabled folds' caps: raw_unpack_kernel into the ctx's column chunk, fold_chunk_cols (second_pass.inc).
 // raw_build_cols is never called: loading parts does not produce parts.  fa_raw_load touches neither flows_5m nor the wide table;
 // the door that feeds them from the same front half (load_prepare, load_columns, load_unpack) is fa_raw_load_rollup
-// (rollup_host.inc).  The sketches are fed from wire bytes only.
+// (rollup_host.inc); fa_raw_restore (sketch_fold_host.inc) feeds those, the sketches and the folds from it in one pass.
 // Memory (LoadState, kept until fa_raw_reset / fa_destroy): the input's copy, 64 KiB per block of decoded image, 40 bytes per
 // block and 48 per part of plan and verdicts, one chunk of columns.
 

@@ -6,7 +6,8 @@
 // step for columns in HBM - a loaded part (raw_load_host.inc) or a decode - into the SAME device-wide tables the ingest kernels
 // feed, through the same helpers: pack_key / key_hash / as_home (table.cuh), table_find_or_claim + quad_atomic_update, and
 // wide_sink_wave's atomic form for the wide key sets (sinks.cuh).  u64 sums commute, so the state is what an ingest of the same
-// records leaves, bit for bit.  No tuple segments, no wide log, no sketches (those are fed from wire bytes only).
+// records leaves, bit for bit.  No tuple segments, no wide log; the sketches and the distinct-address sets have a fold of their own
+// (sketch_fold.cuh).
 //
 // Shape: a persistent grid of 256-thread workgroups.  In round r, wave w of the grid (w = workgroup * 4 + wave of the workgroup)
 // takes the 64 records from (r * waves + w) * 64 on: consecutive waves read consecutive 64-record runs of every column, and the

@@ -116,7 +116,7 @@ static int rollup_finish(fa_ctx* c) {
 static int rollup_mask(fa_ctx* c, const char* fn, uint32_t asked, uint32_t* ks) {
     const int rc = rollup_mask_check(c->cfg.key_sets, asked, ks);
     if (rc == FA_ERR_UNSUPPORTED) {
-        c->err = std::string(fn) + ((asked & ROLLUP_SKETCH_SETS) ? ": the sketches and the distinct-address sets are fed from wire bytes only (fa_ingest / fa_ingest_device)" :
+        c->err = std::string(fn) + ((asked & ROLLUP_SKETCH_SETS) ? ": this door does not feed the sketches and the distinct-address sets - they are fed from wire bytes only here; from columns and parts by fa_sketch_fold_columns_device / fa_raw_restore" :
                                                                    ": the ctx was created without an exact key set: nothing to fold into");
     } else if (rc) {
         c->err = std::string(fn) + ": key_sets names a key set the ctx was not created with";

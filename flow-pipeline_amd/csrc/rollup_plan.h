@@ -14,8 +14,9 @@ constexpr uint32_t ROLLUP_EXACT_SETS = FA_KEYS_AS_PAIR | FA_KEYS_ADDR_PORT_PROTO
 constexpr uint32_t ROLLUP_SKETCH_SETS = FA_KEYS_SRCADDR_CMS | FA_KEYS_DSTADDR_CMS;
 
 // The key sets a call folds: `asked` == 0 means every exact key set the ctx was created with (`ctx_sets` = fa_config.key_sets);
-// otherwise a subset of those.  FA_OK and *out, or: FA_ERR_UNSUPPORTED for a sketch bit (sketches are fed from wire bytes only)
-// and for a ctx without any exact key set, FA_ERR_ARG for any other bit the ctx was not created with.
+// otherwise a subset of those.  FA_OK and *out, or: FA_ERR_UNSUPPORTED for a sketch bit (the rollup doors do not feed the sketches:
+// sketch_plan.h, fa_sketch_fold_columns_device / fa_raw_restore) and for a ctx without any exact key set, FA_ERR_ARG for any other
+// bit the ctx was not created with.
 inline int rollup_mask_check(uint32_t ctx_sets, uint32_t asked, uint32_t* out) {
     *out = 0;
     if (asked & ROLLUP_SKETCH_SETS) return FA_ERR_UNSUPPORTED;

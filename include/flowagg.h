@@ -95,6 +95,11 @@ typedef struct {
                                      of a ctx with FA_KEYS_ADDR_PORT_PROTO - those are split.  R is therefore a function of the
                                      stream, the caller's batches AND the configuration; what is guaranteed for every split is
                                      the containment below, and bit-for-bit reproducibility for a fixed configuration.)
+                                     (A chunk of a sketch fold from columns or from parts - fa_sketch_fold_columns_device,
+                                     fa_raw_restore - IS a batch too: a fold of n records is cut into chunks of at most
+                                     max_batch_records, in fa_raw_restore also at part boundaries and at the other selected
+                                     destinations' caps; each chunk is admitted against the bits of the boundary before it and
+                                     ends in a boundary of its own, whether the batch before it was an ingest launch or a chunk.)
                                      fa_topk ranks R - every key whose estimate stood at or above the running topk_track-th
                                      estimate at a batch boundary and that occurred again afterwards: on a stream whose heavy
                                      hitters recur in every batch the same rows as the exact mode (BASELINE config 3: checked),
@@ -656,7 +661,8 @@ int fa_raw_lz4_stats(fa_ctx*, fa_raw_lz4_stats_t* out);
  * NOT inspected: the column VALUES (that Date matches TimeReceived, that TimeReceived is sorted).  NOT fed: loading never builds
  * parts again (a ctx with fa_raw_enable gets no pending part from a load) and never touches flows_5m, the wide table or the
  * sketches - fa_raw_load_rollup below ("the rollups from columns and from parts") is the door that feeds flows_5m and the exact
- * dashboard key sets, the minute series among them, from parts; the sketches are fed from wire bytes only.
+ * dashboard key sets, the minute series among them, from parts; fa_raw_restore ("the sketches from columns and from parts") feeds
+ * those, the sketches and the folds in one pass.
  * Memory, allocated on first use, kept until fa_raw_load_reset / fa_raw_reset / fa_destroy: the compressed copy, 64 KiB per block of decoded image,
  * one chunk of columns (117 bytes per row).  FA_ERR_NOMEM leaves the ctx usable; a caller with a large file loads it in
  * pieces cut at frame boundaries. */
@@ -735,13 +741,13 @@ int fa_raw_merge_stats(fa_ctx*, fa_raw_merge_stats_t* out);
  * adds to it.  Records with status != 0 are skipped (inserter.go:125-126); a record below a closed flows_5m window is folded
  * and counted in fa_stats.records_late, as an ingested one is.
  * key_sets: 0 = every exact key set the ctx was created with; otherwise a subset of those - a bit the ctx was not created with
- * is FA_ERR_ARG, a sketch bit (FA_KEYS_SRCADDR_CMS, FA_KEYS_DSTADDR_CMS) FA_ERR_UNSUPPORTED: the sketches and the
- * distinct-address sets are fed from wire bytes only.
+ * is FA_ERR_ARG, a sketch bit (FA_KEYS_SRCADDR_CMS, FA_KEYS_DSTADDR_CMS) FA_ERR_UNSUPPORTED: these two doors do not feed the
+ * sketches and the distinct-address sets - fa_sketch_fold_columns_device and fa_raw_restore below do.
  * Both doors are synchronous and end in the settle every read starts with: table growth and the replay of parked updates have
  * happened and fa_last_error is meaningful when they return.  fa_stats.records_ok / records_bad / bytes_in do not move (they
  * count wire records); table_used, wide_used, table_capacity, wide_capacity and records_late do, as after any settle.
- * Additive: a ctx that never calls these functions runs the code it ran.  NOT built: sketches from columns, a group door (a
- * loaded ctx is a group member like any other), a consumer flag. */
+ * Additive: a ctx that never calls these functions runs the code it ran.  NOT built: a group door (a loaded ctx is a group member
+ * like any other), a consumer flag. */
 typedef struct {
     uint64_t calls;                   /* fa_rollup_fold_columns_device + fa_raw_load_rollup calls that succeeded */
     uint64_t records_in, records_bad; /* records handed to fold launches; of them status != 0, skipped */
@@ -763,6 +769,45 @@ int fa_rollup_fold_columns_device(fa_ctx*, const fa_columns* cols, size_t n, uin
 int fa_raw_load_rollup(fa_ctx*, const uint8_t* bytes, size_t n, uint32_t key_sets, int folds);
 /* The counters of this ctx's rollup folds; works on any ctx (all zero before the first call). */
 int fa_rollup_stats(fa_ctx*, fa_rollup_stats_t* out);
+
+/* ---- ABI 8, addition: the sketches from columns and from parts ---------------------- */
+/* The last piece of a ctx's state that parts could not bring back: the two Count-Min sketches (FA_KEYS_SRCADDR_CMS,
+ * FA_KEYS_DSTADDR_CMS) and the distinct-address sets behind fa_topk.  sketch_fold_kernel (csrc/sketch_fold.cuh) takes decoded
+ * columns through the helpers every ingest path ends in (cms_add, keyset_offer): weight = Bytes * SamplingRate (u64, wrapping), key =
+ * the raw 16 address bytes (the EType plays no part), records with status != 0 skipped.  Sums commute: the sketches are what an
+ * ingest of the same records leaves, bit for bit, and a fold on top of ingested state adds to it.  In the exact mode the sets are
+ * those of an ingest too; in the candidates mode every chunk is one batch of the contract (fa_config.topk_mode), so a restored
+ * ctx equals a ctx that ingested the same records in the same batches.  A fold makes the merged view stale, as an ingest does.
+ * fa_stats.records_ok / records_bad / bytes_in / batches / kernel_launches do not move (they count wire records and ingest
+ * launches); topk_theta / topk_candidates do.  After fa_raw_restore(key_sets = 0, folds = 1) a ctx equals, read for read, a ctx
+ * that ingested the records the parts hold.
+ * Additive: a ctx that never calls these functions runs the code it ran.  NOT built: a group door (a restored ctx is a group
+ * member like any other), a consumer flag, the fold fused into the parts' unpack. */
+typedef struct {
+    uint64_t calls;                   /* fa_sketch_fold_columns_device + fa_raw_restore (with a sketch selected) calls that succeeded */
+    uint64_t records_in, records_bad; /* records handed to fold launches; of them status != 0, skipped */
+    uint64_t records_folded;          /* records_in - records_bad */
+    uint64_t batches;                 /* chunks = batches of the candidates contract */
+    uint64_t launches;                /* sketch_fold_kernel launches (one per chunk) */
+    uint64_t fold_ns;                 /* hipEvent time of those launches */
+} fa_sketch_fold_stats_t;
+/* n records of `cols` - DEVICE pointers: status, bytes, sampling_rate and the address column of every selected sketch (src_addr,
+ * dst_addr) are needed, the others may be null, and every pointer given must be naturally aligned (8 / 4 / 16 / 1 bytes):
+ * FA_ERR_ARG otherwise.  key_sets: 0 = every sketch the ctx was created with; otherwise a subset of those - any other bit (an
+ * exact key set, a sketch the ctx was created without) is FA_ERR_ARG; a ctx without any sketch: FA_ERR_UNSUPPORTED.  n == 0 is
+ * FA_OK without a launch.  Chunks of at most max_batch_records.  Synchronous: it ends in the settle every read starts with; the
+ * columns are not referenced after the call. */
+int fa_sketch_fold_columns_device(fa_ctx*, const fa_columns* cols, size_t n, uint32_t key_sets);
+/* fa_raw_load's input contract and front half - LZ4 frames or plain Native parts in HOST memory, everything validated before
+ * the first fold, FA_ERR_FRAMING with the reason and the byte position, A REFUSED CALL FOLDS NOTHING.  key_sets: 0 = everything
+ * the ctx was created with, exact key sets and sketches alike; otherwise a subset (FA_ERR_ARG for a bit the ctx lacks).
+ * folds != 0: also the enabled talker and port folds, as fa_raw_load feeds them.  Each chunk is unpacked once and goes to the
+ * rollup fold (an exact key set selected), the sketch fold (a sketch selected) and the folds; its length is the smallest of the
+ * selected destinations' caps, and chunks end at part boundaries.  FA_ERR_UNSUPPORTED when nothing is selected to fold into.
+ * Counted in fa_raw_load_stats, fa_rollup_stats and fa_sketch_fold_stats. */
+int fa_raw_restore(fa_ctx*, const uint8_t* bytes, size_t n, uint32_t key_sets, int folds);
+/* The counters of this ctx's sketch folds; works on any ctx (all zero before the first call). */
+int fa_sketch_fold_stats(fa_ctx*, fa_sketch_fold_stats_t* out);
 
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
