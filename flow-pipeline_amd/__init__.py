@@ -139,6 +139,16 @@ class SketchFoldStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RawRangeStats(C.Structure):
+    """fa_raw_range_stats_t: what the ctx's ranged loads (raw_range_probe, raw_restore_range) have done so far."""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "calls", "parts_seen", "parts_skipped_date", "parts_empty", "blocks_seen", "blocks_decoded", "rows_seen", "rows_loaded",
+        "launches", "probe_ns", "range_ns", "decode_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class RawMergeStats(C.Structure):
     """fa_raw_merge_stats_t: what the ctx's merges of pending parts (raw_merge) have done so far."""
     _fields_ = [(n, C.c_uint64) for n in (
@@ -149,6 +159,8 @@ class RawMergeStats(C.Structure):
 
 
 LZ4_SPAN_DTYPE = np.dtype([("offset", "<u8"), ("bytes", "<u8")])  # fa_lz4_span
+RAW_RANGE_DTYPE = np.dtype([("date", "<u4"), ("t_min", "<u4"), ("t_max", "<u4"), ("_pad", "<u4"), ("rows", "<u8"), ("r_lo", "<u8"), ("r_hi", "<u8")])  # fa_raw_range
+assert RAW_RANGE_DTYPE.itemsize == 40 and C.sizeof(RawRangeStats) == 96
 
 
 class MockParams(C.Structure):
@@ -230,6 +242,7 @@ EXPORTS = [
     "fa_lz4_decode", "fa_lz4_decode_device", "fa_raw_columns_device", "fa_raw_load", "fa_raw_load_stats", "fa_raw_load_reset",
     "fa_rollup_fold_columns_device", "fa_raw_load_rollup", "fa_rollup_stats",
     "fa_sketch_fold_columns_device", "fa_raw_restore", "fa_sketch_fold_stats",
+    "fa_raw_range_probe", "fa_raw_restore_range", "fa_raw_range_stats",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -440,6 +453,9 @@ def lib():
     L.fa_sketch_fold_columns_device.argtypes = [vp, C.POINTER(Columns), sz, u32]
     L.fa_raw_restore.argtypes = [vp, vp, sz, u32, C.c_int]
     L.fa_sketch_fold_stats.argtypes = [vp, C.POINTER(SketchFoldStats)]
+    L.fa_raw_range_probe.argtypes = [vp, vp, sz, u32, u32, vp, sz, szp]
+    L.fa_raw_restore_range.argtypes = [vp, vp, sz, u32, u32, u32, C.c_int]
+    L.fa_raw_range_stats.argtypes = [vp, C.POINTER(RawRangeStats)]
     L.fa_raw_merge.argtypes = [vp]
     L.fa_raw_merge_stats.argtypes = [vp, C.POINTER(RawMergeStats)]
     _LIB = L
@@ -1062,6 +1078,38 @@ class FlowAgg:
     def sketch_fold_stats(self) -> dict:
         s = SketchFoldStats()
         self._chk(self._L.fa_sketch_fold_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
+    # -- ranged loads of flows_raw parts (include/flowagg.h, the section of that name) ----
+    def raw_range_probe(self, data, t_lo: int, t_hi: int, cap: int = None):
+        """One RAW_RANGE_DTYPE entry per part of `data`, input order: date, rows and the rows [r_lo, r_hi) whose
+        (uint32)TimeReceived lies in [t_lo, t_hi) (t_hi = 0xFFFFFFFF: to the end), t_min / t_max of those rows.  Only the blocks the
+        headers and the TimeReceived columns of the parts selected by Date lie in are decoded; no fold.  An unsorted part or a row of
+        another Date is FlowAggError -7.  cap: the entries there is room for (default: asked for first)."""
+        a = _host_bytes(data)
+        ptr = a.ctypes.data if a.size else None
+        need = C.c_size_t()
+        if cap is None:
+            rc = self._L.fa_raw_range_probe(self._h, ptr, a.size, t_lo, t_hi, None, 0, C.byref(need))
+            if rc == 0:  # (no part at all)
+                return np.zeros(0, dtype=RAW_RANGE_DTYPE)
+            if rc != -6:
+                self._chk(rc)
+            cap = need.value
+        out = np.zeros(cap, dtype=RAW_RANGE_DTYPE)
+        self._chk(self._L.fa_raw_range_probe(self._h, ptr, a.size, t_lo, t_hi, out.ctypes.data if cap else None, cap, C.byref(need)))
+        return out[:need.value]
+
+    def raw_restore_range(self, data, t_lo: int, t_hi: int, key_sets: int = 0, folds: bool = False):
+        """raw_restore for the rows of `data` whose (uint32)TimeReceived lies in [t_lo, t_hi) (t_hi = 0xFFFFFFFF: to the end): the
+        parts' sort key, not TimeFlowStart.  Only the blocks that hold those rows, the headers and the TimeReceived columns are decoded.
+        A refused input (FlowAggError -7: also an unsorted part or a row of another Date) folds nothing."""
+        a = _host_bytes(data)
+        self._chk(self._L.fa_raw_restore_range(self._h, a.ctypes.data if a.size else None, a.size, t_lo, t_hi, key_sets, 1 if folds else 0))
+
+    def raw_range_stats(self) -> dict:
+        s = RawRangeStats()
+        self._chk(self._L.fa_raw_range_stats(self._h, C.byref(s)))
         return s.as_dict()
 
     def raw_reset(self):

@@ -36,6 +36,7 @@
 #include "lz4_decode.cuh"
 #include "raw.cuh"
 #include "raw_merge.cuh"
+#include "raw_range.cuh"
 #include "rollup_plan.h"
 #include "sketch_plan.h"
 #include "table_room.h"
@@ -236,6 +237,7 @@ struct fa_ctx {
     struct LoadState* load = nullptr;   // loading parts back (raw_load_host.inc), nullptr until the first decode / load call
     struct RollupState* rollup = nullptr;  // the rollups from columns and from parts (rollup_host.inc), nullptr until the first fold
     struct SketchFoldState* sketch_fold = nullptr;  // the sketches from columns and from parts (sketch_fold_host.inc), nullptr until the first fold
+    struct RangeState* range = nullptr;  // ranged loads of parts (raw_range_host.inc), nullptr until the first ranged call
 
     fa_stats_t stats{};
     uint64_t used_base = 0;  // groups created before the current counter epoch
@@ -281,6 +283,7 @@ static void load_destroy(fa_ctx* c);
 static void load_release(fa_ctx* c);
 static void rollup_destroy(fa_ctx* c);
 static void sketch_fold_destroy(fa_ctx* c);
+static void range_destroy(fa_ctx* c);
 
 extern "C" uint32_t fa_abi_version(void) { return FA_ABI_VERSION; }
 
@@ -576,6 +579,7 @@ extern "C" void fa_destroy(fa_ctx* c) {
     load_destroy(c);
     rollup_destroy(c);
     sketch_fold_destroy(c);
+    range_destroy(c);
     const hipStream_t streams[3] = {c->copy_stream, c->cand_stream, c->stream};
     delete c;  // every buffer is released here (fa_ctx's members own them): before the streams go, as ever
     for (hipStream_t s : streams)
@@ -616,6 +620,7 @@ static bool bucket_range(const fa_ctx* c, uint32_t timeslot, uint32_t& lo, uint3
 #include "raw_load_host.inc"
 #include "rollup_host.inc"
 #include "sketch_fold_host.inc"
+#include "raw_range_host.inc"
 
 extern "C" int fa_stats(fa_ctx* c, fa_stats_t* out) {
     FA_ON_DEVICE(c);

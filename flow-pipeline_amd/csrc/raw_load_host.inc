@@ -88,18 +88,27 @@ struct LoadPrepared {
     std::vector<LoadPart> parts;  // (want_parts only)
 };
 
-// in[0, n) -> the decoded image in HBM.  want_parts: the input is LZ4 frames or plain Native parts, told apart by its first four
-// bytes, and every frame (or plain block) is also checked as a flows_raw part; otherwise it is LZ4 frames.
-// FA_ERR_FRAMING (text in fa_last_error) on the first violation in input order; nothing was unpacked or folded then.
-static int load_prepare(fa_ctx* c, LoadState* s, const char* fn, const uint8_t* in, size_t n, bool want_parts, LoadPrepared& pr) {
+// why raw_header_check_kernel refused a part (empty: no such code)
+static std::string load_verdict_why(const RawPartVerdict& v) {
+    switch (v.code) {
+    case RAW_V_SIZE: return std::to_string(v.bytes) + " bytes fit no row count of a flows_raw part (a truncated part or trailing bytes)";
+    case RAW_V_NCOLS: return "a flows_raw block has 16 columns, not this column count";
+    case RAW_V_ROWS: return "the row count at byte " + std::to_string(v.at) + " is not the one the part's size gives (a size that fits no row count, or trailing bytes)";
+    case RAW_V_NAME: return "column " + std::to_string(v.at) + " has a wrong name (" + RAW_COLS_H[v.at & 15].name + " is expected)";
+    case RAW_V_TYPE: return "column " + std::to_string(v.at) + " has a wrong type (" + RAW_COLS_H[v.at & 15].type + " is expected)";
+    default: return std::string();
+    }
+}
+
+// The host's half: the frames walked (or the plain parts' row counts read) -> pr.walk and one RawPartPlan per part.  Nothing is
+// copied or counted.  (Shared with the ranged doors, raw_range_host.inc.)
+static int load_walk(fa_ctx* c, const char* fn, const uint8_t* in, size_t n, bool want_parts, LoadPrepared& pr, std::vector<RawPartPlan>& pplan, bool* is_lz4) {
     auto framing = [&](const std::string& why) {
         c->err = std::string(fn) + ": " + why;
         return FA_ERR_FRAMING;
     };
-    s->ev_used = 2;  // (chunk events of a call that failed half-way are dropped unread)
     const bool lz4 = !want_parts || (n >= 4 && (lz4_read32(in) == 0x184D2204u || (lz4_read32(in) >= 0x184D2A50u && lz4_read32(in) <= 0x184D2A5Fu)));
     std::string err;
-    std::vector<RawPartPlan> pplan;
     if (lz4) {
         if (!lz4_walk_frames(in, n, pr.walk, &err)) return framing(err);
         if (pr.walk.first.size() - 1 > pr.frames_cap) return fail(c, FA_ERR_CAPACITY, "the span buffer is too small (the frames needed are returned); nothing was decoded");
@@ -123,12 +132,30 @@ static int load_prepare(fa_ctx* c, LoadState* s, const char* fn, const uint8_t* 
             p += fa_raw_part_bytes(rows);
         }
     }
+    *is_lz4 = lz4;
+    return FA_OK;
+}
+
+// in[0, n) -> the decoded image in HBM.  want_parts: the input is LZ4 frames or plain Native parts, told apart by its first four
+// bytes, and every frame (or plain block) is also checked as a flows_raw part; otherwise it is LZ4 frames.
+// FA_ERR_FRAMING (text in fa_last_error) on the first violation in input order; nothing was unpacked or folded then.
+static int load_prepare(fa_ctx* c, LoadState* s, const char* fn, const uint8_t* in, size_t n, bool want_parts, LoadPrepared& pr) {
+    auto framing = [&](const std::string& why) {
+        c->err = std::string(fn) + ": " + why;
+        return FA_ERR_FRAMING;
+    };
+    s->ev_used = 2;  // (chunk events of a call that failed half-way are dropped unread)
+    std::string err;
+    std::vector<RawPartPlan> pplan;
+    bool lz4 = false;
+    int rc = load_walk(c, fn, in, n, want_parts, pr, pplan, &lz4);
+    if (rc) return rc;
     const size_t nb = pr.walk.blocks.size(), np = pplan.size();
     if (n == 0) return FA_OK;
     // ---- buffers
     const size_t plan_b = align256(nb * sizeof(Lz4DBlock)), pplan_b = align256(np * sizeof(RawPartPlan));
     const size_t st_b = align256(nb * sizeof(Lz4DecStatus)), ver_b = align256(np * sizeof(RawPartVerdict));
-    int rc = ensure_dev(c, s->meta, plan_b + pplan_b + st_b + ver_b + 256, "load plan");
+    rc = ensure_dev(c, s->meta, plan_b + pplan_b + st_b + ver_b + 256, "load plan");
     if (rc) return rc;
     bool ok = s->h_meta.grow(std::max(plan_b + pplan_b, st_b + ver_b) + 256) && s->in.grow(n + 16) && s->img.grow(std::max<size_t>(nb, 1) * LZ4_BLOCK_MAX);
     if (!ok) {
@@ -176,14 +203,9 @@ static int load_prepare(fa_ctx* c, LoadState* s, const char* fn, const uint8_t* 
         if (i < nf && !lz4_frame_verdict(pr.walk, (uint32_t)i, st, &pr.frame_bytes[i], &err)) return framing(err);
         if (i < np && ver[i].code) {
             const std::string where = lz4 ? "frame " + std::to_string(i) : "the part at byte " + std::to_string(pplan[i].off);
-            switch (ver[i].code) {
-            case RAW_V_SIZE: return framing(where + ": " + std::to_string(ver[i].bytes) + " bytes fit no row count of a flows_raw part (a truncated part or trailing bytes)");
-            case RAW_V_NCOLS: return framing(where + ": a flows_raw block has 16 columns, not this column count");
-            case RAW_V_ROWS: return framing(where + ": the row count at byte " + std::to_string(ver[i].at) + " is not the one the part's size gives (a size that fits no row count, or trailing bytes)");
-            case RAW_V_NAME: return framing(where + ": column " + std::to_string(ver[i].at) + " has a wrong name (" + RAW_COLS_H[ver[i].at & 15].name + " is expected)");
-            case RAW_V_TYPE: return framing(where + ": column " + std::to_string(ver[i].at) + " has a wrong type (" + RAW_COLS_H[ver[i].at & 15].type + " is expected)");
-            default: return fail(c, FA_ERR_HIP, "internal: a part's verdict is inconsistent");
-            }
+            const std::string v = load_verdict_why(ver[i]);
+            if (v.empty()) return fail(c, FA_ERR_HIP, "internal: a part's verdict is inconsistent");
+            return framing(where + ": " + v);
         }
         if (i < np) {
             if (ver[i].rows > ((uint64_t)1 << 31)) return fail(c, FA_ERR_ARG, "a part of more than 2^31 rows");

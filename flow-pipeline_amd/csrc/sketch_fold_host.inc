@@ -139,26 +139,40 @@ extern "C" int fa_sketch_fold_columns_device(fa_ctx* c, const fa_columns* cols, 
     return FA_OK;
 }
 
-extern "C" int fa_raw_restore(fa_ctx* c, const uint8_t* bytes, size_t n, uint32_t key_sets, int folds) {
-    LOAD_ENTER(c);
-    uint32_t ks = 0, sets = 0;
-    int rc = restore_mask_check(c->cfg.key_sets, key_sets, &ks, &sets);
-    if (rc) return fail(c, rc, "fa_raw_restore: key_sets names a key set the ctx was not created with");
-    const bool talk = folds && c->talk, ports = folds && c->ports;
-    if (!ks && !sets && !talk && !ports)
-        return fail(c, FA_ERR_UNSUPPORTED, "fa_raw_restore: nothing is selected to fold into (no key set of the ctx, and no enabled talker or port fold asked for)");
-    if (!bytes && n) return fail(c, FA_ERR_ARG, "fa_raw_restore: null argument");
-    LoadState* s = nullptr;
-    rc = load_state(c, &s);
-    if (rc) return rc;
-    LoadPrepared pr;
-    rc = load_prepare(c, s, "fa_raw_restore", bytes, n, true, pr);
-    if (rc) return rc;
-    // (from here on the input is known to be whole: a refused call has folded nothing)
+// ---- the restore's two halves, shared with the ranged door (raw_range_host.inc) -----------------------------------------------------
+struct RestoreSel {
+    uint32_t ks = 0, sets = 0;  // the exact key sets and the sketches selected
+    bool talk = false, ports = false;
+};
+// rows [r_lo, r_hi) of a part
+struct LoadSlice {
+    LoadPart part;
+    uint64_t r_lo, r_hi;
+};
+// what key_sets / folds select on this ctx: the mask refusals, FA_ERR_UNSUPPORTED when nothing is selected
+static int restore_select(fa_ctx* c, const char* fn, uint32_t key_sets, int folds, RestoreSel* sel) {
+    int rc = restore_mask_check(c->cfg.key_sets, key_sets, &sel->ks, &sel->sets);
+    if (rc) {
+        c->err = std::string(fn) + ": key_sets names a key set the ctx was not created with";
+        return rc;
+    }
+    sel->talk = folds && c->talk, sel->ports = folds && c->ports;
+    if (!sel->ks && !sel->sets && !sel->talk && !sel->ports) {
+        c->err = std::string(fn) + ": nothing is selected to fold into (no key set of the ctx, and no enabled talker or port fold asked for)";
+        return FA_ERR_UNSUPPORTED;
+    }
+    return FA_OK;
+}
+// every slice, in order, unpacked a chunk at a time and folded into everything selected; then the settle and the folds' ends
+static int restore_fold_slices(fa_ctx* c, LoadState* s, const std::vector<LoadSlice>& slices, const RestoreSel& sel) {
+    const uint32_t ks = sel.ks, sets = sel.sets;
+    const bool talk = sel.talk, ports = sel.ports;
+    int rc = FA_OK;
     const size_t cap = restore_chunk_cap(ks ? rollup_chunk(c, ks) : 0, sets ? sketch_chunk_cap(c->cfg.max_batch_records) : 0, talk ? talk_chunk_cap(c) : 0, ports ? port_chunk_cap(c) : 0);
-    for (const LoadPart& p : pr.parts)
-        for (uint64_t r0 = 0; r0 < p.rows;) {  // (chunks end at part boundaries)
-            const size_t m = (size_t)std::min<uint64_t>(p.rows - r0, cap);
+    for (const LoadSlice& sl : slices)
+        for (uint64_t r0 = sl.r_lo; r0 < sl.r_hi;) {  // (chunks end at part boundaries)
+            const LoadPart& p = sl.part;
+            const size_t m = (size_t)std::min<uint64_t>(sl.r_hi - r0, cap);
             fa_columns cols;
             void* dst[RAW_NCOLS];
             rc = load_columns(c, s, m, &cols, dst);
@@ -201,6 +215,24 @@ extern "C" int fa_raw_restore(fa_ctx* c, const uint8_t* bytes, size_t n, uint32_
         f->calls++;
     }
     return FA_OK;
+}
+
+extern "C" int fa_raw_restore(fa_ctx* c, const uint8_t* bytes, size_t n, uint32_t key_sets, int folds) {
+    LOAD_ENTER(c);
+    RestoreSel sel;
+    int rc = restore_select(c, "fa_raw_restore", key_sets, folds, &sel);
+    if (rc) return rc;
+    if (!bytes && n) return fail(c, FA_ERR_ARG, "fa_raw_restore: null argument");
+    LoadState* s = nullptr;
+    rc = load_state(c, &s);
+    if (rc) return rc;
+    LoadPrepared pr;
+    rc = load_prepare(c, s, "fa_raw_restore", bytes, n, true, pr);
+    if (rc) return rc;
+    // (from here on the input is known to be whole: a refused call has folded nothing)
+    std::vector<LoadSlice> slices;
+    for (const LoadPart& p : pr.parts) slices.push_back({p, 0, p.rows});
+    return restore_fold_slices(c, s, slices, sel);
 }
 
 extern "C" int fa_sketch_fold_stats(fa_ctx* c, fa_sketch_fold_stats_t* out) {

@@ -809,6 +809,72 @@ int fa_raw_restore(fa_ctx*, const uint8_t* bytes, size_t n, uint32_t key_sets, i
 /* The counters of this ctx's sketch folds; works on any ctx (all zero before the first call). */
 int fa_sketch_fold_stats(fa_ctx*, fa_sketch_fold_stats_t* out);
 
+/* ---- ABI 8, addition: ranged loads of flows_raw parts ------------------------------- */
+/* flows_raw is PARTITION BY Date ORDER BY TimeReceived (compose/clickhouse/create.sh:36-62): a WHERE on TimeReceived skips the
+ * partitions of other Dates and reads only the granules that can hold the range.  The parts carry the same order, and these
+ * doors use it: fa_raw_restore_range is fa_raw_restore for the rows with t_lo <= t32 < t_hi, t32 = (uint32_t)TimeReceived, and
+ * decodes only the 64 KiB blocks it needs.  A time range is a row range [r_lo, r_hi) of a sorted part, a row range is one
+ * contiguous byte slice per column, and the frames' blocks decode alone (FLG 0x60).
+ * THE RANGE IS ON THE PRIMARY KEY, TimeReceived, the one ORDER BY serves - not on TimeFlowStart, which the panels filter on
+ * (viz-ch.json:66,225).  A caller widens the range by its collectors' delay; the bucketed tables (fa_top_talkers_range,
+ * fa_top_ports_range) then answer the exact panel range.  t_hi == 0xFFFFFFFF means "to the end" and includes that second
+ * (fa_top_talkers_range's convention); t_lo > t_hi is FA_ERR_ARG; t_lo == t_hi probes and validates but loads nothing (FA_OK).
+ * No grid is required.
+ * Input: fa_raw_restore's contract - LZ4 frames or plain Native parts in HOST memory, told apart by the first four bytes; ONE
+ * copy brings them to HBM.  Three stages, each ending in one synchronisation (csrc/raw_range_plan.h, csrc/raw_range_host.inc):
+ *   A probe  block 0 and the last block of every frame are decoded: the decoded size gives the rows, the first bytes are checked
+ *            (column count, varuint(rows)) and give Date[0].  A part is SELECTED when rows > 0 and
+ *            [Date * 86400, Date * 86400 + 86400) meets the range: partition pruning.
+ *   B range  of every selected part the blocks that hold a byte of the 16 column headers or of the TimeReceived column (4 bytes
+ *            per row) are decoded; raw_header_check_kernel compares the headers, raw_range_kernel (csrc/raw_range.cuh) makes one
+ *            pass over the column: r_lo, r_hi, the first descent, the first row of another Date, t_min and t_max.
+ *   C load   of every part with r_lo < r_hi the blocks, not decoded yet, that hold a byte of rows [r_lo, r_hi) of the 14 columns
+ *            behind TimeReceived are decoded (the Date values are never needed); then the unpack and fold loop of fa_raw_restore
+ *            runs over [r_lo, r_hi).
+ * A block is decoded at most once per call.  Plain Native input skips the decodes (stage A reads the host's bytes) and keeps
+ * the checks, stage B's kernels and stage C's slice.
+ * VALIDATED, before the first fold (A REFUSED CALL FOLDS NOTHING, the ctx stays usable): every frame is walked on the host, as by
+ * fa_raw_restore; every block the call decodes (status, and 65536 decoded bytes unless it is its frame's last); every part's
+ * row count from its size, column count and varuint(rows); for every selected part all 16 headers, that TimeReceived ascends,
+ * and that t32 / 86400 is the part's Date on every row.  A part that is not sorted or holds a row of another Date is
+ * FA_ERR_FRAMING, the part and the row in fa_last_error: the range rests on the order, which the whole-file doors never needed
+ * (they accept such a part, and go on doing so).  NOT validated: blocks that are not decoded - a corrupt block outside the
+ * needed set is not seen -, and of the parts skipped by Date (or without rows) everything beyond their first and last block.
+ * Result: afterwards the ctx equals, read for read, a ctx that got fa_raw_restore of parts holding only those rows, in the same
+ * order; chunks end at part boundaries, and in the candidates mode each chunk of ranged rows is one batch.  Sums commute: the
+ * call adds to ingested state.  key_sets, folds, the mask refusals and FA_ERR_UNSUPPORTED when nothing is selected to fold into:
+ * as fa_raw_restore.  Counted in fa_raw_load_stats as a restore is (calls, frames, bytes_in, rows_loaded, launches, unpack_ns,
+ * fold_ns; blocks, stored_blocks, bytes_decoded, decode_ns: what went through lz4_decode_kernel; parts: the parts unpacked), in
+ * fa_rollup_stats and fa_sketch_fold_stats, and in fa_raw_range_stats.  fa_raw_range_probe counts there too, as the call that loads
+ * nothing that it is: calls, frames, bytes_in, blocks, stored_blocks, bytes_decoded, decode_ns and launches move, parts and
+ * rows_loaded do not.  A REFUSED call of either door counts nothing - except the launches it had queued and their decode_ns, in both
+ * statistics, as a refused call of the whole-file doors does.
+ * Memory: that of fa_raw_restore (a slot per block of the input, decoded or not) plus 152 bytes per part.
+ * Additive: a ctx that never calls these functions runs the code it ran.  NOT built: copying only the needed compressed bytes
+ * (the whole input is copied), a compact image (undecoded slots are allocated), a group or dist door, a consumer flag, a range
+ * on TimeFlowStart. */
+typedef struct {
+    uint32_t date, t_min, t_max, _pad; /* Date[0] (0 for a part without rows); t_min / t_max of the rows in range, 0 when none */
+    uint64_t rows, r_lo, r_hi;         /* the part's rows; the rows in range are [r_lo, r_hi) (0, 0 for a part that is not selected) */
+} fa_raw_range; /* one per part, input order */
+typedef struct {
+    uint64_t calls;                        /* fa_raw_restore_range + fa_raw_range_probe calls that succeeded */
+    uint64_t parts_seen;                   /* parts of those calls = parts_skipped_date + parts_empty + parts with r_lo < r_hi */
+    uint64_t parts_skipped_date;           /* rows > 0, but the Date cannot meet the range: only their first and last block were decoded */
+    uint64_t parts_empty;                  /* selected by Date but r_lo == r_hi; also a part without rows */
+    uint64_t blocks_seen, blocks_decoded;  /* LZ4 blocks of the input; of them sent through lz4_decode_kernel */
+    uint64_t rows_seen, rows_loaded;       /* rows of every part; rows handed to the folds (fa_raw_restore_range only) */
+    uint64_t launches;                     /* kernel launches queued: decode, probe, header check, range, unpack (the folds count their own) */
+    uint64_t probe_ns, range_ns, decode_ns; /* hipEvent times: stage A's kernels; raw_range_kernel; the decode launches of stages B and C */
+} fa_raw_range_stats_t;
+/* Stages A and B, no fold; works on any ctx.  out[i] describes part i of the input.  FA_ERR_CAPACITY (found by the host's walk,
+ * before anything is copied): *n_out = the parts there are.  Synchronous. */
+int fa_raw_range_probe(fa_ctx*, const uint8_t* bytes, size_t n, uint32_t t_lo, uint32_t t_hi, fa_raw_range* out, size_t cap, size_t* n_out);
+/* Stages A, B and C.  Synchronous: it ends in the settle every read starts with. */
+int fa_raw_restore_range(fa_ctx*, const uint8_t* bytes, size_t n, uint32_t t_lo, uint32_t t_hi, uint32_t key_sets, int folds);
+/* The counters of this ctx's ranged loads; works on any ctx (all zero before the first call). */
+int fa_raw_range_stats(fa_ctx*, fa_raw_range_stats_t* out);
+
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
  *   if(EType = 0x800, IPv4NumToString(reinterpretAsUInt32(substring(reverse(Addr), 13, 4))), IPv6NumToString(Addr))
