@@ -149,6 +149,56 @@ class RawRangeStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RawSelectStats(C.Structure):
+    """fa_raw_select_stats_t: what the ctx's selects of rows (raw_select) have done so far."""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "calls", "rows_scanned", "rows_matched", "rows_out", "parts_out", "bytes_out", "launches", "select_ns", "emit_ns", "gather_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class RawFilter(C.Structure):
+    """fa_raw_filter (include/flowagg.h "selecting rows of flows_raw parts"): 96 bytes; a member whose RAW_F_* bit is clear is not read."""
+    _fields_ = [("fields", C.c_uint32), ("t_lo", C.c_uint32), ("t_hi", C.c_uint32), ("tf_lo", C.c_uint32), ("tf_hi", C.c_uint32),
+                ("src_as", C.c_uint32), ("dst_as", C.c_uint32), ("etype", C.c_uint32), ("proto", C.c_uint32),
+                ("src_port_lo", C.c_uint32), ("src_port_hi", C.c_uint32), ("dst_port_lo", C.c_uint32), ("dst_port_hi", C.c_uint32),
+                ("src_prefix_len", C.c_uint8), ("dst_prefix_len", C.c_uint8), ("_pad", C.c_uint8 * 2),
+                ("src_addr", C.c_uint8 * 16), ("dst_addr", C.c_uint8 * 16), ("limit", C.c_uint64)]
+
+
+RAW_F_FLOW_START, RAW_F_SRC_AS, RAW_F_DST_AS, RAW_F_ETYPE, RAW_F_PROTO, RAW_F_SRC_PORT = 1, 2, 4, 8, 16, 32
+RAW_F_DST_PORT, RAW_F_SRC_ADDR, RAW_F_DST_ADDR, RAW_F_EITHER, RAW_F_COUNT_ONLY = 64, 128, 256, 512, 1024
+assert C.sizeof(RawFilter) == 96 and C.sizeof(RawSelectStats) == 80
+
+
+def raw_filter(t_lo=0, t_hi=0xFFFFFFFF, *, flow_start=None, src_as=None, dst_as=None, etype=None, proto=None, src_port=None, dst_port=None,
+               src_net=None, dst_net=None, either=False, limit=0, count_only=False) -> RawFilter:
+    """The RawFilter of FlowAgg.raw_select's keywords: flow_start and the ports are (lo, hi), the nets (16 bytes, prefix_len)."""
+    f = RawFilter()
+    f.t_lo, f.t_hi, f.limit = t_lo, t_hi, limit
+    if flow_start is not None:
+        f.fields |= RAW_F_FLOW_START
+        f.tf_lo, f.tf_hi = flow_start
+    for name, bit, v in (("src_as", RAW_F_SRC_AS, src_as), ("dst_as", RAW_F_DST_AS, dst_as), ("etype", RAW_F_ETYPE, etype), ("proto", RAW_F_PROTO, proto)):
+        if v is not None:
+            f.fields |= bit
+            setattr(f, name, v)
+    for name, bit, v in (("src_port", RAW_F_SRC_PORT, src_port), ("dst_port", RAW_F_DST_PORT, dst_port)):
+        if v is not None:
+            f.fields |= bit
+            setattr(f, name + "_lo", v[0]), setattr(f, name + "_hi", v[1])
+    for name, bit, v in (("src", RAW_F_SRC_ADDR, src_net), ("dst", RAW_F_DST_ADDR, dst_net)):
+        if v is not None:
+            addr, plen = v
+            if len(addr) != 16 or not 0 <= plen <= 255:
+                raise ValueError("a net is (16 bytes, prefix_len)")
+            f.fields |= bit
+            setattr(f, name + "_addr", (C.c_uint8 * 16)(*bytes(addr))), setattr(f, name + "_prefix_len", plen)
+    f.fields |= (RAW_F_EITHER if either else 0) | (RAW_F_COUNT_ONLY if count_only else 0)
+    return f
+
+
 class RawMergeStats(C.Structure):
     """fa_raw_merge_stats_t: what the ctx's merges of pending parts (raw_merge) have done so far."""
     _fields_ = [(n, C.c_uint64) for n in (
@@ -243,6 +293,7 @@ EXPORTS = [
     "fa_rollup_fold_columns_device", "fa_raw_load_rollup", "fa_rollup_stats",
     "fa_sketch_fold_columns_device", "fa_raw_restore", "fa_sketch_fold_stats",
     "fa_raw_range_probe", "fa_raw_restore_range", "fa_raw_range_stats",
+    "fa_raw_select", "fa_raw_selection_device", "fa_raw_selection_fetch", "fa_raw_select_stats",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -456,6 +507,10 @@ def lib():
     L.fa_raw_range_probe.argtypes = [vp, vp, sz, u32, u32, vp, sz, szp]
     L.fa_raw_restore_range.argtypes = [vp, vp, sz, u32, u32, u32, C.c_int]
     L.fa_raw_range_stats.argtypes = [vp, C.POINTER(RawRangeStats)]
+    L.fa_raw_select.argtypes = [vp, vp, sz, C.POINTER(RawFilter), vp, sz, szp, szp]
+    L.fa_raw_selection_device.argtypes = [vp, C.POINTER(C.c_void_p), szp]
+    L.fa_raw_selection_fetch.argtypes = [vp, vp, sz, szp]
+    L.fa_raw_select_stats.argtypes = [vp, C.POINTER(RawSelectStats)]
     L.fa_raw_merge.argtypes = [vp]
     L.fa_raw_merge_stats.argtypes = [vp, C.POINTER(RawMergeStats)]
     _LIB = L
@@ -1110,6 +1165,49 @@ class FlowAgg:
     def raw_range_stats(self) -> dict:
         s = RawRangeStats()
         self._chk(self._L.fa_raw_range_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
+    # -- selecting rows of flows_raw parts (include/flowagg.h, the section of that name) ----
+    def raw_select(self, data, t_lo=0, t_hi=0xFFFFFFFF, *, flow_start=None, src_as=None, dst_as=None, etype=None, proto=None, src_port=None,
+                   dst_port=None, src_net=None, dst_net=None, either=False, limit=0, count_only=False, out=None, filter=None):
+        """-> (bytes, parts): the rows of `data` (what raw_take_lz4 or raw_take delivered) whose (uint32)TimeReceived lies in
+        [t_lo, t_hi) and that meet every condition given, as one plain Native part per input part with a match, in input order, rows
+        in the input's order (RAW_PART_DTYPE descriptions).  flow_start and the ports are (lo, hi) - the ports inclusive at both
+        ends -, the nets (16 bytes, prefix_len); either: "between A and B in either direction"; limit: the first rows of the call;
+        count_only: the descriptions alone, bytes is then b"".  out: a uint8 buffer to fill (page-locked: one copy-engine transfer);
+        bytes is then a view of it.  filter: a RawFilter that stands for all the keywords.  A refused input is FlowAggError -7."""
+        f = filter if filter is not None else raw_filter(t_lo, t_hi, flow_start=flow_start, src_as=src_as, dst_as=dst_as, etype=etype, proto=proto, src_port=src_port,
+                                                         dst_port=dst_port, src_net=src_net, dst_net=dst_net, either=either, limit=limit, count_only=count_only)
+        a = _host_bytes(data)
+        ptr = a.ctypes.data if a.size else None
+        nparts, nbytes = C.c_size_t(), C.c_size_t()
+        pcap = 16
+        while True:  # (too few descriptions: the library's host walk says how many before anything is copied)
+            parts = np.zeros(pcap, dtype=RAW_PART_DTYPE)
+            rc = self._L.fa_raw_select(self._h, ptr, a.size, C.byref(f), parts.ctypes.data, pcap, C.byref(nparts), C.byref(nbytes))
+            if rc == -6:
+                pcap = nparts.value
+                continue
+            self._chk(rc)
+            break
+        parts = parts[:nparts.value]
+        if f.fields & RAW_F_COUNT_ONLY:
+            return b"", parts
+        buf = out if out is not None and out.dtype == np.uint8 and out.size >= nbytes.value else np.empty(nbytes.value, dtype=np.uint8)
+        self._chk(self._L.fa_raw_selection_fetch(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(nbytes)))
+        sel = buf[:nbytes.value]
+        return (sel if out is not None and buf is out else sel.tobytes()), parts
+
+    def raw_selection_device(self):
+        """-> (device pointer, bytes): the last raw_select's parts where they lie in HBM (0, 0 when there is none); valid until the
+        ctx's next select, decode, load, restore or range call."""
+        p, nbytes = C.c_void_p(), C.c_size_t()
+        self._chk(self._L.fa_raw_selection_device(self._h, C.byref(p), C.byref(nbytes)))
+        return p.value or 0, nbytes.value
+
+    def raw_select_stats(self) -> dict:
+        s = RawSelectStats()
+        self._chk(self._L.fa_raw_select_stats(self._h, C.byref(s)))
         return s.as_dict()
 
     def raw_reset(self):

@@ -37,6 +37,7 @@ static void load_release(fa_ctx* c) {
     LoadState* s = c->load;
     if (!s) return;
     s->in.reset(), s->img.reset(), s->meta.reset(), s->h_meta.reset(), s->cols.reset();
+    select_release(c);
 }
 static int load_event(fa_ctx* c, LoadState* s, size_t i) {
     while (s->ev.size() <= i) {
@@ -50,6 +51,7 @@ static int load_event(fa_ctx* c, LoadState* s, size_t i) {
     return FA_OK;
 }
 static int load_state(fa_ctx* c, LoadState** out) {
+    select_drop(c);  // (every decode, load, restore, range and select door starts here: a selection lives until the next of them)
     if (!c->load) c->load = new LoadState();
     *out = c->load;
     return load_event(c, c->load, 1);

@@ -875,6 +875,93 @@ int fa_raw_restore_range(fa_ctx*, const uint8_t* bytes, size_t n, uint32_t t_lo,
 /* The counters of this ctx's ranged loads; works on any ctx (all zero before the first call). */
 int fa_raw_range_stats(fa_ctx*, fa_raw_range_stats_t* out);
 
+/* ---- ABI 8, addition: selecting rows of flows_raw parts ------------------------------- */
+/* "Which flows touched this host, this prefix or this port between 10:05 and 10:20": README.md:144-160's SELECT ... FROM flows_raw
+ * with a WHERE.  fa_raw_select reads flows_raw parts as fa_raw_restore_range does - the same input contract (LZ4 frames or plain
+ * Native parts in HOST memory), the same three stages, the same validation, the same refusals (an unsorted part or a row of
+ * another Date is FA_ERR_FRAMING, the part and the row in fa_last_error), NO DECODE BEYOND stage C's - and delivers, instead of
+ * folding them, the ROWS of the time range that meet a filter, as flows_raw parts again.  It works on any ctx: no fa_raw_enable,
+ * no fold.
+ * The filter.  The time range on TimeReceived, the parts' sort key, ALWAYS applies: t_lo <= (uint32_t)TimeReceived < t_hi;
+ * t_hi == 0xFFFFFFFF means "to the end" and includes that second; t_lo == t_hi selects nothing (fa_raw_restore_range's rule).
+ * It is what prunes parts and blocks.  Every other condition is named by its bit in `fields`; a member whose bit is clear is
+ * not read.  A row matches iff the time range holds, every set condition among FLOW_START, ETYPE and PROTO holds, and
+ *     P(Src, Dst) || (EITHER && P(Dst, Src)),
+ * P(s, d) = the conjunction of the AS, port and address conditions that are set, the src_* members tested on s, the dst_* members
+ * on d.  EITHER is "between A and B in either direction"; with SRC_ADDR alone it is "this host on either side".
+ *   FLOW_START   tf_lo <= stored TimeFlowStart (DateTime, 32 bits) < tf_hi, the rule of t_lo / t_hi.  The parts are not sorted by
+ *                it: nothing is pruned by it, every row of the TimeReceived range is tested.
+ *   SRC_AS, DST_AS, ETYPE, PROTO   equality with the whole UInt32 column value.
+ *   SRC_PORT, DST_PORT             lo <= the whole UInt32 column value <= hi (inclusive at both ends).
+ *   SRC_ADDR, DST_ADDR             the first prefix_len bits of the stored 16 bytes - from byte 0 on, most significant bit first -
+ *                equal those of `addr`; the bits of `addr` behind the prefix are ignored; length 0 matches every row.  The column
+ *                holds what the producer stored, whatever the family (README.md:186-191): an IPv4 /24 is prefix_len = 24 over
+ *                bytes 0..2, together with ETYPE 0x800 if only that family is wanted.
+ *   COUNT_ONLY   nothing is gathered or kept: the parts are still described, with bytes = fa_raw_part_bytes(rows), and *bytes_out
+ *                is their sum.
+ * FA_ERR_ARG (the reason in fa_last_error): an unknown bit, t_lo > t_hi, tf_lo > tf_hi, a port lo > hi, a prefix length above 128,
+ * non-zero _pad.
+ * The result: ONE plain Native part per input part that has at least one matching row, in input order, back to back; rows keep the
+ * input part's order, so every output part is sorted and holds one Date: each is what INSERT INTO flows_raw FORMAT Native takes and
+ * what fa_raw_load, fa_raw_restore and fa_raw_select read.  parts[i]: date, t_min / t_max of the SELECTED rows, rows, offset /
+ * bytes inside the selection.  `limit` counts over the call in that order: part by part, and the first rows of the part in which
+ * it runs out.  parts_cap below the INPUT's part count is FA_ERR_CAPACITY, found by the host's walk before anything is copied;
+ * *n_parts = the parts there are (fa_raw_range_probe's rule).  More than 2^31 - 1 rows in the parts that hold a row of the time
+ * range is FA_ERR_ARG before any select launch (the gather's index width, fa_raw_merge's rule).
+ * THE SELECTION STAYS IN HBM, owned by the ctx, until the ctx's next fa_raw_select, decode, load, restore or range call
+ * (fa_lz4_decode_device, fa_raw_columns_device, fa_raw_load, fa_raw_load_rollup, fa_raw_restore, fa_raw_range_probe,
+ * fa_raw_restore_range), fa_raw_load_reset, fa_raw_reset or fa_destroy.  A refused call leaves no selection: the previous one is
+ * dropped when the call starts.  FA_ERR_NOMEM leaves the ctx usable.
+ * Waits: the three of the ranged load, one for the per-part counts (the output's layout depends on them), one behind the gathers.
+ * Counted in fa_raw_load_stats and fa_raw_range_stats as a ranged call that loads nothing: what fa_raw_range_probe moves, plus
+ * stage C's decodes and `parts` (the parts with a row of the time range); rows_loaded does not move.  The select's own launches
+ * are counted in fa_raw_select_stats alone.
+ * Memory, kept until fa_raw_load_reset / fa_raw_reset / fa_destroy: that of the ranged load, 10 bytes per 64 rows of the time
+ * range, 8 bytes per selected row, 68 bytes per part with a row of the time range (and as many page-locked), hipcub's storage for
+ * one scan, the selection.
+ * NOT built: selecting from a live ctx's pending parts, a projection of columns, a group or dist door, a consumer flag, decoding
+ * the predicate's columns first and only the blocks of matching rows afterwards, OR-lists of values, pruning by TimeFlowStart. */
+#define FA_RAW_F_FLOW_START 1u
+#define FA_RAW_F_SRC_AS 2u
+#define FA_RAW_F_DST_AS 4u
+#define FA_RAW_F_ETYPE 8u
+#define FA_RAW_F_PROTO 16u
+#define FA_RAW_F_SRC_PORT 32u
+#define FA_RAW_F_DST_PORT 64u
+#define FA_RAW_F_SRC_ADDR 128u
+#define FA_RAW_F_DST_ADDR 256u
+#define FA_RAW_F_EITHER 512u
+#define FA_RAW_F_COUNT_ONLY 1024u
+#define FA_RAW_F_ALL 2047u
+typedef struct {
+    uint32_t fields;                 /* FA_RAW_F_* bits; any other bit: FA_ERR_ARG */
+    uint32_t t_lo, t_hi;             /* ALWAYS applied: t_lo <= (uint32_t)TimeReceived < t_hi; t_hi = 0xFFFFFFFF: to the end, that
+                                        second included; t_lo == t_hi: nothing (fa_raw_restore_range's rule, its text) */
+    uint32_t tf_lo, tf_hi;           /* FA_RAW_F_FLOW_START: the same rule on the stored TimeFlowStart (DateTime, 32 bits) */
+    uint32_t src_as, dst_as, etype, proto;                          /* equality */
+    uint32_t src_port_lo, src_port_hi, dst_port_lo, dst_port_hi;    /* inclusive at both ends; the whole UInt32 column value */
+    uint8_t  src_prefix_len, dst_prefix_len, _pad[2];               /* 0 .. 128; _pad must be 0 */
+    uint8_t  src_addr[16], dst_addr[16];
+    uint64_t limit;                  /* 0: none; else at most this many rows of the call, the FIRST in output order */
+} fa_raw_filter; /* 96 bytes */
+typedef struct {
+    uint64_t calls;                        /* fa_raw_select calls that succeeded */
+    uint64_t rows_scanned;                 /* rows of the time ranges: what raw_select_kernel tested */
+    uint64_t rows_matched;                 /* of them matching, before `limit` */
+    uint64_t rows_out, parts_out, bytes_out; /* delivered (COUNT_ONLY: described) */
+    uint64_t launches;                     /* select, scan, totals, emit, gather */
+    uint64_t select_ns, emit_ns, gather_ns; /* hipEvent times: raw_select_kernel with the scan; raw_select_emit_kernel; the gathers */
+} fa_raw_select_stats_t;
+/* Synchronous.  *n_parts = the output parts (FA_ERR_CAPACITY: the input's parts), *bytes_out = the selection's bytes. */
+int fa_raw_select(fa_ctx*, const uint8_t* bytes, size_t n, const fa_raw_filter* filter, fa_raw_part* parts, size_t parts_cap, size_t* n_parts, size_t* bytes_out);
+/* The ctx's selection where it lies in HBM (nullptr and 0 bytes when there is none). */
+int fa_raw_selection_device(fa_ctx*, const void** d_bytes, size_t* bytes_out);
+/* Copies the selection out; page-locked `out` takes one copy-engine transfer.  FA_ERR_CAPACITY returns the size in *bytes_out;
+ * the selection stays either way. */
+int fa_raw_selection_fetch(fa_ctx*, uint8_t* out, size_t cap, size_t* bytes_out);
+/* The counters of this ctx's selects; works on any ctx (all zero before the first call). */
+int fa_raw_select_stats(fa_ctx*, fa_raw_select_stats_t* out);
+
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
  *   if(EType = 0x800, IPv4NumToString(reinterpretAsUInt32(substring(reverse(Addr), 13, 4))), IPv6NumToString(Addr))
