@@ -199,6 +199,28 @@ def raw_filter(t_lo=0, t_hi=0xFFFFFFFF, *, flow_start=None, src_as=None, dst_as=
     return f
 
 
+class RawQuery(C.Structure):
+    """fa_raw_query_t (include/flowagg.h "grouped queries over flows_raw parts"): 104 bytes."""
+    _fields_ = [("where", RawFilter), ("groups", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RawQueryStats(C.Structure):
+    """fa_raw_query_stats_t: what the ctx's grouped queries (raw_query and its reads) have done so far."""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "calls", "rows_scanned", "rows_matched", "updates", "absorbed", "groups", "grows", "launches", "fold_ns", "order_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+RAW_G_SRC_ADDR, RAW_G_DST_ADDR, RAW_G_SRC_PORT, RAW_G_DST_PORT, RAW_G_MINUTE, RAW_G_SRC_AS, RAW_G_DST_AS, RAW_G_PROTO, RAW_G_TOTAL = (1 << i for i in range(9))
+RAW_G_ALL = 511
+RAW_Q_KEEP = 1
+RAW_O_WEIGHT, RAW_O_KEY = 0, 1
+QUERY_ROW_DTYPE = np.dtype([("key", "u1", 16), ("etype", "<u4"), ("value", "<u4"), ("weight", "<u8"), ("count", "<u8")])  # fa_query_row
+assert C.sizeof(RawQuery) == 104 and C.sizeof(RawQueryStats) == 80 and QUERY_ROW_DTYPE.itemsize == 40
+
+
 class RawMergeStats(C.Structure):
     """fa_raw_merge_stats_t: what the ctx's merges of pending parts (raw_merge) have done so far."""
     _fields_ = [(n, C.c_uint64) for n in (
@@ -294,6 +316,7 @@ EXPORTS = [
     "fa_sketch_fold_columns_device", "fa_raw_restore", "fa_sketch_fold_stats",
     "fa_raw_range_probe", "fa_raw_restore_range", "fa_raw_range_stats",
     "fa_raw_select", "fa_raw_selection_device", "fa_raw_selection_fetch", "fa_raw_select_stats",
+    "fa_raw_query", "fa_raw_query_rows", "fa_raw_query_rows_device", "fa_raw_query_reset", "fa_raw_query_stats",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -511,6 +534,11 @@ def lib():
     L.fa_raw_selection_device.argtypes = [vp, C.POINTER(C.c_void_p), szp]
     L.fa_raw_selection_fetch.argtypes = [vp, vp, sz, szp]
     L.fa_raw_select_stats.argtypes = [vp, C.POINTER(RawSelectStats)]
+    L.fa_raw_query.argtypes = [vp, vp, sz, C.POINTER(RawQuery)]
+    L.fa_raw_query_rows.argtypes = [vp, C.c_uint32, C.c_int, sz, vp, sz, szp]
+    L.fa_raw_query_rows_device.argtypes = [vp, C.c_uint32, C.c_int, sz, C.POINTER(C.c_void_p), szp]
+    L.fa_raw_query_reset.argtypes = [vp]
+    L.fa_raw_query_stats.argtypes = [vp, C.POINTER(RawQueryStats)]
     L.fa_raw_merge.argtypes = [vp]
     L.fa_raw_merge_stats.argtypes = [vp, C.POINTER(RawMergeStats)]
     _LIB = L
@@ -1208,6 +1236,45 @@ class FlowAgg:
     def raw_select_stats(self) -> dict:
         s = RawSelectStats()
         self._chk(self._L.fa_raw_select_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
+    # -- grouped queries over flows_raw parts (include/flowagg.h, the section of that name) ----
+    def raw_query(self, data, groups, t_lo=0, t_hi=0xFFFFFFFF, *, keep=False, filter=None, **conditions):
+        """WHERE and one GROUP BY per RAW_G_* bit of `groups` over the rows of `data` (what raw_take_lz4 or raw_take delivered), all
+        kinds in one pass; the result stays in HBM until the next raw_query without keep (read it with raw_query_rows).  The
+        conditions are raw_filter's keywords (no limit, no count_only); filter: a RawFilter that stands for them and the time
+        range.  keep: add to the result held.  A refused input is FlowAggError -7."""
+        q = RawQuery()
+        q.where = filter if filter is not None else raw_filter(t_lo, t_hi, **conditions)
+        q.groups, q.flags = groups, RAW_Q_KEEP if keep else 0
+        a = _host_bytes(data)
+        self._chk(self._L.fa_raw_query(self._h, a.ctypes.data if a.size else None, a.size, C.byref(q)))
+
+    def raw_query_rows(self, group, k=0, order=RAW_O_WEIGHT) -> np.ndarray:
+        """QUERY_ROW_DTYPE rows of one kind of the last raw_query: every group (k = 0) or the first k in `order` (RAW_O_WEIGHT:
+        weight descending; RAW_O_KEY: value, key bytes, etype ascending), ordered and cut on the device."""
+        need = C.c_size_t()
+        rc = self._L.fa_raw_query_rows(self._h, group, order, k, None, 0, C.byref(need))
+        if rc != -6:
+            self._chk(rc)
+            return np.zeros(0, dtype=QUERY_ROW_DTYPE)
+        out = np.zeros(need.value, dtype=QUERY_ROW_DTYPE)
+        self._chk(self._L.fa_raw_query_rows(self._h, group, order, k, out.ctypes.data, out.size, C.byref(need)))
+        return out[:need.value]
+
+    def raw_query_rows_device(self, group, k=0, order=RAW_O_WEIGHT):
+        """-> (device pointer, rows): raw_query_rows' rows where they lie in HBM (0, 0 when there is none); valid until the ctx's
+        next query call."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._chk(self._L.fa_raw_query_rows_device(self._h, group, order, k, C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
+
+    def raw_query_reset(self):
+        self._chk(self._L.fa_raw_query_reset(self._h))
+
+    def raw_query_stats(self) -> dict:
+        s = RawQueryStats()
+        self._chk(self._L.fa_raw_query_stats(self._h, C.byref(s)))
         return s.as_dict()
 
     def raw_reset(self):

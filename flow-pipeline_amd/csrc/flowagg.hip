@@ -37,6 +37,7 @@
 #include "raw.cuh"
 #include "raw_merge.cuh"
 #include "raw_range.cuh"
+#include "raw_query.cuh"
 #include "raw_select.cuh"
 #include "rollup_plan.h"
 #include "sketch_plan.h"
@@ -240,6 +241,7 @@ struct fa_ctx {
     struct SketchFoldState* sketch_fold = nullptr;  // the sketches from columns and from parts (sketch_fold_host.inc), nullptr until the first fold
     struct RangeState* range = nullptr;  // ranged loads of parts (raw_range_host.inc), nullptr until the first ranged call
     struct SelectState* select = nullptr;  // selecting rows of parts (raw_select_host.inc), nullptr until the first select
+    struct QueryState* query = nullptr;  // grouped queries over parts (raw_query_host.inc), nullptr until the first query
 
     fa_stats_t stats{};
     uint64_t used_base = 0;  // groups created before the current counter epoch
@@ -289,6 +291,8 @@ static void range_destroy(fa_ctx* c);
 static void select_destroy(fa_ctx* c);
 static void select_drop(fa_ctx* c);
 static void select_release(fa_ctx* c);
+static void query_destroy(fa_ctx* c);
+static void query_release(fa_ctx* c);
 
 extern "C" uint32_t fa_abi_version(void) { return FA_ABI_VERSION; }
 
@@ -586,6 +590,7 @@ extern "C" void fa_destroy(fa_ctx* c) {
     sketch_fold_destroy(c);
     range_destroy(c);
     select_destroy(c);
+    query_destroy(c);
     const hipStream_t streams[3] = {c->copy_stream, c->cand_stream, c->stream};
     delete c;  // every buffer is released here (fa_ctx's members own them): before the streams go, as ever
     for (hipStream_t s : streams)
@@ -628,6 +633,7 @@ static bool bucket_range(const fa_ctx* c, uint32_t timeslot, uint32_t& lo, uint3
 #include "sketch_fold_host.inc"
 #include "raw_range_host.inc"
 #include "raw_select_host.inc"
+#include "raw_query_host.inc"
 
 extern "C" int fa_stats(fa_ctx* c, fa_stats_t* out) {
     FA_ON_DEVICE(c);

@@ -38,6 +38,7 @@ static void load_release(fa_ctx* c) {
     if (!s) return;
     s->in.reset(), s->img.reset(), s->meta.reset(), s->h_meta.reset(), s->cols.reset();
     select_release(c);
+    query_release(c);
 }
 static int load_event(fa_ctx* c, LoadState* s, size_t i) {
     while (s->ev.size() <= i) {

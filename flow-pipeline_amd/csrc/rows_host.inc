@@ -34,6 +34,7 @@ static_assert(RowOps<RK_TALKERS_SRC>::NK2 <= RP_MAX_WORDS, "emit words");
 // talker state's scratch (talkers_host.inc).  The packed emit sort below returned rows out of order on sets of a million talker
 // rows (DESIGN.md 3.7); these four sorts never did.
 static int talk_order_rows(fa_ctx* c, hipStream_t stream, const TalkRow* rows, uint32_t n, size_t need, TalkRow* out);
+static int talk_order_passes(fa_ctx* c, hipStream_t stream, DevBuf<>& order, const TalkRow* rows, uint32_t n, size_t need, TalkRow* out, int passes);
 extern "C" size_t fa_row_bytes(int kind) { return row_bytes_of(kind); }
 
 static int ensure_dev(fa_ctx* c, DevBuf<>& b, size_t bytes, const char* what) {

@@ -217,21 +217,26 @@ extern "C" int fa_top_talkers(fa_ctx* c, int dst, size_t k, fa_talker_row* out, 
 static int talk_order_rows(fa_ctx* c, hipStream_t stream, const TalkRow* rows, uint32_t n, size_t need, TalkRow* out) {
     TalkState* t = c->talk;
     if (!t) return fail(c, FA_ERR_UNSUPPORTED, TALK_OFF);
+    return talk_order_passes(c, stream, t->order, rows, n, need, out, 4);
+}
+// The scheme itself, for any owner of 40-byte talker rows (the grouped queries, raw_query_host.inc): `order` is the owner's scratch;
+// passes = 4: the order above; 3: without the weight - key bytes ascending, etype ascending.
+static int talk_order_passes(fa_ctx* c, hipStream_t stream, DevBuf<>& order, const TalkRow* rows, uint32_t n, size_t need, TalkRow* out, int passes) {
     if (!n || !need) return FA_OK;
     size_t tmp_bytes = 0;
     if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0,
                                            64, stream) != hipSuccess)
         return fail(c, FA_ERR_HIP, "talker rows: sort sizing failed");
     const size_t key_b = align256((size_t)n * 8), perm_b = align256((size_t)n * 4);
-    int rc = ensure_dev(c, t->order, 2 * key_b + 2 * perm_b + align256(tmp_bytes), "talker row order");
+    int rc = ensure_dev(c, order, 2 * key_b + 2 * perm_b + align256(tmp_bytes), "talker row order");
     if (rc) return rc;
-    uint8_t* p = (uint8_t*)t->order;
+    uint8_t* p = (uint8_t*)order;
     unsigned long long* keys[2] = {(unsigned long long*)p, (unsigned long long*)(p + key_b)};
     uint32_t* perm[2] = {(uint32_t*)(p + 2 * key_b), (uint32_t*)(p + 2 * key_b + perm_b)};
     void* tmp = p + 2 * key_b + 2 * perm_b;
     const unsigned gn = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, (uint64_t)c->num_cus * 8);
     int cur = 0;
-    for (int pass = 0; pass < 4; pass++) {
+    for (int pass = 0; pass < passes; pass++) {
         hipLaunchKernelGGL(talker_sortkey_kernel, dim3(gn), dim3(256), 0, stream, rows, pass ? (const uint32_t*)perm[cur] : (const uint32_t*)nullptr, n, pass, keys[0], perm[cur]);
         size_t tb = tmp_bytes;
         if (hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const unsigned long long*)keys[0], keys[1], (const uint32_t*)perm[cur], perm[cur ^ 1], (int)n, 0, pass == 0 ? 16 : 64, stream) !=

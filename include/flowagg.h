@@ -962,6 +962,78 @@ int fa_raw_selection_fetch(fa_ctx*, uint8_t* out, size_t cap, size_t* bytes_out)
 /* The counters of this ctx's selects; works on any ctx (all zero before the first call). */
 int fa_raw_select_stats(fa_ctx*, fa_raw_select_stats_t* out);
 
+/* ---- ABI 8, addition: grouped queries over flows_raw parts ----------------------------- */
+/* The ANSWER of a dashboard panel out of stored parts.  The five ClickHouse panels (viz-ch.json:74, 233, 358, 479, 604) are
+ *     SELECT <key>, sum(Bytes*SamplingRate) FROM flows_raw WHERE $timeFilter [AND ...] GROUP BY <key> ORDER BY ...
+ * with the minute of TimeFlowStart, the rendered SrcAddr, the rendered DstAddr, SrcPort and DstPort as keys.  fa_raw_query reads
+ * its input exactly as fa_raw_select does - LZ4 frames or plain Native parts in HOST memory, the same three stages and waits, the
+ * same validation and refusals (an unsorted part or a row of another Date is FA_ERR_FRAMING, the part and the row in
+ * fa_last_error), no decode beyond stage C's - and folds the rows that meet `where` into one GROUP BY per bit of `groups`, ALL of
+ * them in ONE pass over the rows.  It works on any ctx, nothing enabled, and like every range call it drops the ctx's selection.
+ * The filter: `where` is fa_raw_filter with its text unchanged (the time range on TimeReceived, the other conditions, EITHER).
+ * FA_ERR_ARG (the reason in fa_last_error): what fa_raw_select refuses in a filter; where.limit != 0 or COUNT_ONLY; groups == 0 or
+ * a bit outside FA_RAW_G_ALL; an unknown flag; KEEP with `groups` other than those of the result the ctx holds.
+ * The values of a group: weight = sum(Bytes*SamplingRate) mod 2^64, count = count().  A group of weight 0 is a row; a kind with no
+ * matching row has no rows.
+ *   address kinds  key, etype are exactly fa_talker_row's, so fa_format_addr gives the panel's string: EType 0x800 -> etype 0x800,
+ *                  bytes 0..3 and twelve zero bytes; any other EType -> etype 0 and all 16 bytes; the same bytes under the two
+ *                  families are two groups.  value is 0.
+ *   scalar kinds   key is all zeros, etype 0; value = the whole UInt32 column value; MINUTE: the start of the minute in seconds;
+ *                  TOTAL: 0.
+ * THE RESULT LIES IN HBM, owned by the ctx, until the next fa_raw_query without KEEP (which clears it when it STARTS),
+ * fa_raw_query_reset, fa_raw_load_reset, fa_raw_reset or fa_destroy; it survives every other call, fa_raw_select and the restores
+ * included.  With KEEP the call's rows are added to the result held (several files, one answer).  Every refusal of the input
+ * happens before the first fold launch, so a refused KEEP call leaves the accumulated result as it was; a refused call without
+ * KEEP leaves none.
+ * Reading: `group` is exactly one bit of the last query's groups (else FA_ERR_ARG; also before any query).  k = 0: every group,
+ * else the first k in `order`.  The rows are ordered and cut on the device: only the rows returned cross PCIe.  FA_ERR_CAPACITY
+ * puts the rows needed in *n_out.  fa_raw_query_rows_device hands out the same rows in HBM, valid until the ctx's next query call.
+ * Rows read with k = 0 are mergeable by sum.
+ * The query never reads or writes another aggregate of the ctx: flows_5m, the wide table, the sketches, the talker and port
+ * tables and pending raw parts are untouched; it can run on a ctx that is ingesting.
+ * Counted in fa_raw_load_stats and fa_raw_range_stats as fa_raw_select is; never in fa_raw_select_stats.
+ * Memory, kept until fa_raw_load_reset / fa_raw_reset / fa_destroy: that of the ranged load, 32 bytes per part with a row of the
+ * time range (and as many page-locked), two tables of 64-byte slots that start at 2^16 slots and grow until the rows x kinds of
+ * a fold launch (at most 2^20 keys) fit at half load - 2^21 slots each for a million rows scanned, whatever matches -, 40 bytes per
+ * group of the kind being read, the order's keys.
+ * NOT built: decoding only the columns a query names; pending parts of a live ctx and columns already in HBM; sum(Packets),
+ * compound keys such as (SrcAS, DstAS), OR-lists; a group or dist door (rows with k = 0 are mergeable by sum: a merge call can
+ * follow); a consumer flag. */
+#define FA_RAW_G_SRC_ADDR 1u   /* the talker panels' key: fa_talker_row's canonical (key, etype), talkers.cuh's rule */
+#define FA_RAW_G_DST_ADDR 2u
+#define FA_RAW_G_SRC_PORT 4u   /* the whole UInt32 column value */
+#define FA_RAW_G_DST_PORT 8u
+#define FA_RAW_G_MINUTE   16u  /* toStartOfMinute(TimeFlowStart): t - t % 60 of the stored 32-bit TimeFlowStart */
+#define FA_RAW_G_SRC_AS   32u
+#define FA_RAW_G_DST_AS   64u
+#define FA_RAW_G_PROTO    128u
+#define FA_RAW_G_TOTAL    256u /* one group: every matching row */
+#define FA_RAW_G_ALL      511u
+#define FA_RAW_Q_KEEP 1u       /* flags: add to the result the ctx holds instead of replacing it */
+#define FA_RAW_O_WEIGHT 0      /* weight DESC; ties: value ascending (numeric), key bytes ascending (memcmp), etype ascending */
+#define FA_RAW_O_KEY    1      /* value ascending, key bytes ascending, etype ascending */
+typedef struct { fa_raw_filter where; uint32_t groups, flags; } fa_raw_query_t;          /* 104 bytes */
+typedef struct { uint8_t key[16]; uint32_t etype, value; uint64_t weight, count; } fa_query_row; /* 40 bytes */
+typedef struct {
+    uint64_t calls;                        /* fa_raw_query calls that succeeded */
+    uint64_t rows_scanned;                 /* rows of the time ranges: what raw_query_fold_kernel tested */
+    uint64_t rows_matched;                 /* of them matching */
+    uint64_t updates;                      /* rows_matched x kinds, summed over the calls */
+    uint64_t absorbed;                     /* of them ended in a workgroup's LDS cache */
+    uint64_t groups;                       /* occupied slots now: the groups of all kinds of the result held */
+    uint64_t grows;                        /* doublings of a table */
+    uint64_t launches;                     /* fold, rehash, collect, order and emit launches */
+    uint64_t fold_ns, order_ns;            /* hipEvent times: the fold launches; collect, order and emit of the reads */
+} fa_raw_query_stats_t;
+/* Synchronous. */
+int fa_raw_query(fa_ctx*, const uint8_t* bytes, size_t n, const fa_raw_query_t* q);
+int fa_raw_query_rows(fa_ctx*, uint32_t group, int order, size_t k, fa_query_row* out, size_t cap, size_t* n_out);
+int fa_raw_query_rows_device(fa_ctx*, uint32_t group, int order, size_t k, const void** d_rows, size_t* n_out);
+/* Drops the result (the tables keep their size); FA_OK on a ctx that never queried. */
+int fa_raw_query_reset(fa_ctx*);
+/* The counters of this ctx's queries; works on any ctx (all zero before the first call). */
+int fa_raw_query_stats(fa_ctx*, fa_raw_query_stats_t* out);
+
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
  *   if(EType = 0x800, IPv4NumToString(reinterpretAsUInt32(substring(reverse(Addr), 13, 4))), IPv6NumToString(Addr))
