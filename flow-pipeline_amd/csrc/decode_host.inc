@@ -60,9 +60,9 @@ static int decode_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
         LaunchPlan p;  // (the default: workgroup tiles, the flows_5m variant)
         p.tile_recs = a.tile_recs = tile_recs_for(bytes, n);
         p.grid = grid_for(c, tile_kernel<MODE_DECODE, 1u>, a.n, p.tile_recs);
-        rc = acquire_events(c, c->dev_pool, c->dev_used, 1024);
+        rc = acquire_events(c, c->dev_pool, 1024);
         if (rc) return rc;
-        rc = launch_tiles<MODE_DECODE>(c, a, p, &c->dev_pool[c->dev_used++]);
+        rc = launch_tiles<MODE_DECODE>(c, a, p, c->dev_pool.take(3));
         if (rc) return rc;
     }
     out->time_received = c->cols.time_received;

@@ -30,6 +30,7 @@
 #include "../../include/flowagg.h"
 #include "bucket_range.h"
 #include "buffers.h"
+#include "events.h"
 #include "kernels.cuh"
 #include "launch_plan.h"
 #include "lz4.cuh"
@@ -59,17 +60,23 @@ struct PinnedAlloc {
 };
 template <class T = void> using DevBuf = Buf<DevAlloc, T>;
 template <class T = void> using PinnedBuf = Buf<PinnedAlloc, T>;
+// Every HIP event of the library is owned by an EventPool (events.h) over this; nothing else creates, destroys or times one.
+struct HipEventApi {
+    typedef hipEvent_t Event;
+    static bool create(hipEvent_t* e, bool timing) { return (timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming)) == hipSuccess; }
+    static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+    static bool elapsed_ms(float* ms, hipEvent_t e0, hipEvent_t e1) { return hipEventElapsedTime(ms, e0, e1) == hipSuccess; }
+};
+using Events = EventPool<HipEventApi>;
+static constexpr bool EV_SYNC = false;  // an Events of untimed events: waited for and recorded, never read
 
 struct fa_ctx {
     fa_config cfg{};
     uint32_t gran = 300;
     hipStream_t stream = nullptr;
     // three events per ingest launch: before / after the tile kernel, after the aggregation kernel
-    struct LaunchEvents { hipEvent_t e0, e1, e2; };
-    std::vector<LaunchEvents> ev_pool;
-    size_t ev_used = 0;
-    std::vector<LaunchEvents> dev_pool;  // ... of fa_decode_device launches
-    size_t dev_used = 0;
+    Events ev_pool;
+    Events dev_pool;  // ... of fa_decode_device launches
 
     DevBuf<Slot> tab;
     uint32_t cap_log2 = 20;
@@ -83,7 +90,7 @@ struct fa_ctx {
     // counter snapshots, one per ingest launch (ring): what the device had counted when that launch finished
     static constexpr int NSNAP = 8;
     PinnedBuf<Counters> h_snap;  // NSNAP entries
-    hipEvent_t snap_ev[NSNAP] = {};
+    Events snap_ev{EV_SYNC};  // NSNAP
     uint64_t snap_records[NSNAP] = {};  // records launched up to and including the snapshot's batch
     uint64_t snap_seq[NSNAP] = {};      // launch sequence number (0 = unused)
     uint64_t launch_seq = 0, known_seq = 0;
@@ -169,7 +176,7 @@ struct fa_ctx {
 
     // host-fed path: pinned staging (double buffered) + device input
     PinnedBuf<uint8_t> h_stage[2];
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
+    Events stage_ev{EV_SYNC};  // 2
     int stage_cur = 0;
     DevBuf<uint8_t> d_in[2];
 
@@ -187,7 +194,7 @@ struct fa_ctx {
     // contexts with a sketch: the flows_5m tuple aggregation of a launch runs on a stream of its own BESIDE the sketch fold (and the
     // candidates mode's boundary kernels) - it touches neither sketch nor set, they touch neither tuple segments nor table (launch_tiles)
     hipStream_t cand_stream = nullptr;
-    hipEvent_t cand_ev[2] = {nullptr, nullptr};  // ingest + second-chance kernels done (main -> side), aggregation done (side -> main)
+    Events cand_ev{EV_SYNC};  // 2 (candidates mode only): ingest + second-chance kernels done (main -> side), aggregation done (side -> main)
     DevBuf<> fs_scratch;      // device-side framing (framing.cuh): block starts, exits, counts, bases, error / trust flags, sub-block entries, counters
     DevBuf<> fs_off;          // ... the offsets it produces
     DevBuf<> wl_scratch;      // window reads of log chunks: per-segment counts, their scan, hipcub storage
@@ -198,7 +205,7 @@ struct fa_ctx {
     DevBuf<> xch_buf;
     uint32_t group_members = 0;        // > 0 while the ctx is a member of a group (of that many contexts)
     PinnedBuf<> h_rows;              // rows on their way to the caller
-    hipEvent_t copy_ev[2] = {nullptr, nullptr};  // the two halves of h_rows while a large result leaves in pieces (rows_host.inc)
+    Events copy_ev{EV_SYNC};  // 2: the two halves of h_rows while a large result leaves in pieces (rows_host.inc)
 
     DevBuf<unsigned long long> cms_src, cms_dst;
     size_t cms_words = 0;   // words of ONE copy; the buffers hold CMS_REPLICAS copies
@@ -273,25 +280,36 @@ static int fail(fa_ctx* c, int code, const char* msg) {
     if (c) c->err = msg;
     return code;
 }
+// A lazily created state behind `slot` goes: its members (DevBuf, Events) clean up after themselves.
+template <class S>
+static void state_destroy(S*& slot) {
+    static_assert(sizeof(S) > 0, "the state's definition is in sight where its destructor is called");
+    delete slot;
+    slot = nullptr;
+}
+// what the caller of a pool's ensure / take answers when it reports a failed creation
+static int events_failed(fa_ctx* c) {
+    (void)hipGetLastError();
+    return fail(c, FA_ERR_HIP, "hipEventCreate failed");
+}
+// ... and comes into being with its fixed set of n events, or not at all
+template <class S>
+static int state_with_events(fa_ctx* c, S*& slot, size_t n) {
+    if (slot) return FA_OK;
+    std::unique_ptr<S> s(new S());
+    if (!s->ev.ensure(n)) return events_failed(c);
+    slot = s.release();
+    return FA_OK;
+}
 // exact top talkers (talkers_host.inc), bucketed port tables (ports_host.inc) and flows_raw parts (raw_host.inc): the second pass
 // behind an ingest call's launches (second_pass.inc) - one decode per chunk for every enabled fold - and the states' release
 static int second_pass_records(fa_ctx* c, const void* d_buf, size_t len, const uint32_t* d_off, size_t n);
-static void talk_destroy(fa_ctx* c);
-static void port_destroy(fa_ctx* c);
 static void raw_destroy(fa_ctx* c);
-static void raw_merge_destroy(fa_ctx* c);
 static void raw_merge_release(fa_ctx* c);
-static void lz4_destroy(fa_ctx* c);
 static void lz4_release(fa_ctx* c);
-static void load_destroy(fa_ctx* c);
 static void load_release(fa_ctx* c);
-static void rollup_destroy(fa_ctx* c);
-static void sketch_fold_destroy(fa_ctx* c);
-static void range_destroy(fa_ctx* c);
-static void select_destroy(fa_ctx* c);
 static void select_drop(fa_ctx* c);
 static void select_release(fa_ctx* c);
-static void query_destroy(fa_ctx* c);
 static void query_release(fa_ctx* c);
 
 extern "C" uint32_t fa_abi_version(void) { return FA_ABI_VERSION; }
@@ -418,12 +436,7 @@ extern "C" int fa_create(const fa_config* cfg_in, fa_ctx** out) {
     }
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
         return bail("hipStreamCreate", e);
-    for (int i = 0; i < 2; i++)
-        if ((e = hipEventCreateWithFlags(&c->stage_ev[i], hipEventDisableTiming)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&c->copy_ev[i], hipEventDisableTiming)) != hipSuccess)
-            return bail("hipEventCreate", e);
-    for (int i = 0; i < fa_ctx::NSNAP; i++)
-        if ((e = hipEventCreateWithFlags(&c->snap_ev[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
+    if (!c->stage_ev.ensure(2) || !c->copy_ev.ensure(2) || !c->snap_ev.ensure(fa_ctx::NSNAP)) return bail("hipEventCreate", hipGetLastError());
     if (!c->h_snap.grow(sizeof(Counters) * fa_ctx::NSNAP)) return bail("hipHostMalloc", hipGetLastError());
     c->spill_cap = 2u * cfg.max_batch_records + (1u << 21);
     c->wide_per_record = ((cfg.key_sets & FA_KEYS_ADDR_PORT_PROTO) ? 1u : 0u) + ((cfg.key_sets & FA_KEYS_PORT_HIST) ? 2u : 0u) +
@@ -455,8 +468,7 @@ extern "C" int fa_create(const fa_config* cfg_in, fa_ctx** out) {
         // created here: a stream costs milliseconds, not a thing for the first ingest launch)
         if (cfg.topk_mode == FA_TOPK_CANDIDATES) {  // (only the candidates mode uses it: every stream of a process competes for its few hardware queues)
             if ((e = hipStreamCreateWithFlags(&c->cand_stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate(side stream)", e);
-            for (int i = 0; i < 2; i++)
-                if ((e = hipEventCreateWithFlags(&c->cand_ev[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
+            if (!c->cand_ev.ensure(2)) return bail("hipEventCreate", hipGetLastError());
         }
         c->ks_log2 = cfg.topk_capacity_log2;
         const size_t ks_bytes = sizeof(KeySlot) << c->ks_log2;
@@ -567,32 +579,19 @@ extern "C" void fa_destroy(fa_ctx* c) {
                     (double)tot / (double)np, mx, (double)mx * (double)np / (double)std::max(1ull, tot), mxseg, (double)tot / (double)(np * c->last_nwg));
         }
     }
-    for (int i = 0; i < fa_ctx::NSNAP; i++)
-        if (c->snap_ev[i]) (void)hipEventDestroy(c->snap_ev[i]);
-    for (int i = 0; i < 2; i++) {
-        if (c->stage_ev[i]) (void)hipEventDestroy(c->stage_ev[i]);
-        if (c->copy_ev[i]) (void)hipEventDestroy(c->copy_ev[i]);
-        if (c->cand_ev[i]) (void)hipEventDestroy(c->cand_ev[i]);
-    }
-    for (auto* pool : {&c->ev_pool, &c->dev_pool})
-        for (auto& p : *pool) {
-            (void)hipEventDestroy(p.e0);
-            (void)hipEventDestroy(p.e1);
-            (void)hipEventDestroy(p.e2);
-        }
-    talk_destroy(c);
-    port_destroy(c);
+    state_destroy(c->talk);
+    state_destroy(c->ports);
     raw_destroy(c);
-    raw_merge_destroy(c);
-    lz4_destroy(c);
-    load_destroy(c);
-    rollup_destroy(c);
-    sketch_fold_destroy(c);
-    range_destroy(c);
-    select_destroy(c);
-    query_destroy(c);
+    state_destroy(c->raw_merge);
+    state_destroy(c->lz4);
+    state_destroy(c->load);
+    state_destroy(c->rollup);
+    state_destroy(c->sketch_fold);
+    state_destroy(c->range);
+    state_destroy(c->select);
+    state_destroy(c->query);
     const hipStream_t streams[3] = {c->copy_stream, c->cand_stream, c->stream};
-    delete c;  // every buffer is released here (fa_ctx's members own them): before the streams go, as ever
+    delete c;  // every event and buffer is released here (fa_ctx's members own them): before the streams go, as ever
     for (hipStream_t s : streams)
         if (s) (void)hipStreamDestroy(s);
 }

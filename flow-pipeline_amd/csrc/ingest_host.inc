@@ -34,13 +34,13 @@ static int cand_boundary(fa_ctx* c) {
 }
 // Launch order on the ctx stream: tile -> deferred -> [agg]   (the wave-tile kernel finds the batch's time base itself).
 template <int MODE>
-static int launch_tiles(fa_ctx* c, KArgs& a, const LaunchPlan& p, fa_ctx::LaunchEvents* ev) {
+static int launch_tiles(fa_ctx* c, KArgs& a, const LaunchPlan& p, const hipEvent_t* ev) {
     // (wave tiles only with tuple segments, which only an ingest with the flows_5m rollup has)
     if (p.wave_tiles && (MODE != MODE_INGEST || !(p.variant & FA_KEYS_AS_PAIR) || !a.seg)) return fail(c, FA_ERR_ARG, "internal: wave tiles without tuple segments");
     const dim3 b(BLOCK), ge(std::min(256u, (a.n + BLOCK - 1) / BLOCK));
     a.par = c->par;
     c->par ^= 1u;
-    if (ev) (void)hipEventRecord(ev->e0, c->stream);
+    if (ev) (void)hipEventRecord(ev[0], c->stream);
     if (p.seq_variant) c->stats.learnt_order_launches += 1;
     if (p.wave_tiles) c->stats.wave_tile_launches += 1;
     if (p.t8) c->stats.compact_tuple_launches += 1;
@@ -53,7 +53,7 @@ static int launch_tiles(fa_ctx* c, KArgs& a, const LaunchPlan& p, fa_ctx::Launch
         } else if constexpr (MODE == MODE_INGEST && (KS & FA_KEYS_AS_PAIR) != 0u) {  // (no other variant has a wave-tile kernel compiled)
             launch_wave_tiles<KS>(c, a, p);
         }
-        if (ev) (void)hipEventRecord(ev->e1, c->stream);
+        if (ev) (void)hipEventRecord(ev[1], c->stream);
         // (the second-chance kernel runs in line: on a side stream beside the aggregation it cost MORE - 66 vs 58 us for
         // deferred + aggregation per launch, the cross-stream hand-over being slower than the 4.5 us kernel - and its atomic
         // upserts would race with the region-owned plain stores of agg8_kernel / cms_agg_kernel)
@@ -112,7 +112,7 @@ static int launch_tiles(fa_ctx* c, KArgs& a, const LaunchPlan& p, fa_ctx::Launch
         if (rc == FA_OK) return fail(c, FA_ERR_HIP, "joining the side stream failed");
     }
     if (rc) return rc;
-    if (ev) (void)hipEventRecord(ev->e2, c->stream);
+    if (ev) (void)hipEventRecord(ev[2], c->stream);
     HIPCHK(c, hipGetLastError());
     return FA_OK;
 }
@@ -395,18 +395,13 @@ static int ingest_device_any(fa_ctx* c, const void* d_buf, size_t len, const voi
     return second_pass_records(c, d_buf, len, (const uint32_t*)d_off, n);
 }
 
-// Room for one more launch's three events in a pool that settle hands back whole: afterwards pool[used] exists and the launch
-// takes it with used++ (a settle in between starts the pool over; the launch then takes its first triple).  A pool at its
-// limit is settled instead of grown; no event is destroyed before the ctx goes.
-static int acquire_events(fa_ctx* c, std::vector<fa_ctx::LaunchEvents>& pool, const size_t& used, size_t limit) {
-    if (used < pool.size()) return FA_OK;
-    if (pool.size() >= limit) return settle(c);  // bound the pool: fold what is pending
-    fa_ctx::LaunchEvents e{};
-    HIPCHK(c, hipEventCreate(&e.e0));
-    HIPCHK(c, hipEventCreate(&e.e1));
-    HIPCHK(c, hipEventCreate(&e.e2));
-    pool.push_back(e);
-    return FA_OK;
+// Room for one more launch's three events in a pool that settle hands back whole: afterwards the launch's take(3) creates
+// nothing (a settle in between starts the pool over; the launch then takes its first triple).  A pool at its limit of `limit`
+// launches is settled instead of grown; no event is destroyed before the ctx goes.
+static int acquire_events(fa_ctx* c, Events& pool, size_t limit) {
+    if (pool.used() + 3 <= pool.size()) return FA_OK;
+    if (pool.size() >= 3 * limit) return settle(c);  // bound the pool: fold what is pending
+    return pool.ensure(pool.used() + 3) ? FA_OK : events_failed(c);
 }
 
 // the launch arguments that name a table (settle / rebuild_* replace them)
@@ -469,7 +464,7 @@ static int ingest_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
     if (rc) return rc;
     rc = ensure_exotic(c, n);
     if (rc) return rc;
-    rc = acquire_events(c, c->ev_pool, c->ev_used, 4096);
+    rc = acquire_events(c, c->ev_pool, 4096);
     if (rc) return rc;
     KArgs a = make_args(c);
     a.buf = (const uint8_t*)d_buf;
@@ -511,7 +506,7 @@ static int ingest_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
     p.seq_variant = p.wave_tiles && c->cfg.key_sets == FA_KEYS_AS_PAIR && c->seq_mode != 2 && (c->seq_mode == 1 || c->stats.batches < c->seq_until);
     p.side = p.cms_segments && c->cand_stream && c->cand_state;
     if (c->wtab) c->wpot_total += (uint64_t)n * c->wide_per_record;  // (rows this launch may open in the wide table: wide_rows_bound)
-    rc = launch_tiles<MODE_INGEST>(c, a, p, &c->ev_pool[c->ev_used++]);
+    rc = launch_tiles<MODE_INGEST>(c, a, p, c->ev_pool.take(3));
     if (rc) return rc;
     if (p.wlog) {
         rc = wlog_record(c, a, n);

@@ -15,26 +15,13 @@ struct TabPair {
     size_t chunk = (size_t)1 << 20;  // env FA_TALK_CHUNK (the one knob of the second pass)
     uint32_t wgpc = T::WG_PER_CU;    // env T::WGPC_ENV (A/B: workgroups per CU of the fold kernel)
     uint64_t grows = 0, fold_launches = 0, fold_ns_total = 0;
-    struct Ev { hipEvent_t e0, e1; };
-    std::vector<Ev> ev;  // one pair per fold launch that has not been read yet
-    size_t ev_used = 0;
+    Events ev;  // one pair per fold launch that has not been read yet
 
     uint64_t slots(int d) const { return 1ull << log2[d]; }
     uint32_t mask(int d) const { return (uint32_t)(slots(d) - 1); }
     dim3 scan_grid(const fa_ctx* c, int d) const { return dim3((unsigned)std::min<uint64_t>((slots(d) + 255) / 256, (uint64_t)c->num_cus * 8)); }
-    ~TabPair() {
-        for (auto& e : ev) {
-            (void)hipEventDestroy(e.e0);
-            (void)hipEventDestroy(e.e1);
-        }
-    }
 };
-
-template <class S>
-static void tab_destroy(S*& slot) {
-    delete slot;
-    slot = nullptr;
-}
+static constexpr size_t TAB_EV_MAX = 2 * 1024;  // fold launches whose times are pending before the tables are settled
 
 #define TAB_ENTER(c, state, off)                                                                       \
     FA_ON_DEVICE(c);                                                                                   \
@@ -61,7 +48,7 @@ static int tab_enable(fa_ctx* c, S*& slot, const char* fn, uint32_t capacity_log
     ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        tab_destroy(slot);
+        state_destroy(slot);
         return fail(c, FA_ERR_NOMEM, std::string(fn) + ": allocating the tables failed");
     }
     return FA_OK;
@@ -72,11 +59,8 @@ template <class T>
 static int tab_settle(fa_ctx* c, TabPair<T>& t, typename T::Counters& h) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(&h, t.d_ctr, sizeof h, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < t.ev_used; i++) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, t.ev[i].e0, t.ev[i].e1) == hipSuccess) t.fold_ns_total += (uint64_t)((double)ms * 1e6);
-    }
-    t.ev_used = 0;
+    for (size_t i = 0; i + 1 < t.ev.used(); i += 2) Events::elapsed_ns(t.ev[i], t.ev[i + 1], &t.fold_ns_total);
+    t.ev.rewind();
     if (h.lost) {
         c->sticky = FA_ERR_TABLE_FULL;
         return fail(c, FA_ERR_TABLE_FULL, std::string("internal: a ") + T::NOUN + " table was full during a launch; updates were lost");
@@ -158,39 +142,22 @@ static int tab_chunks(fa_ctx* c, TabPair<T>& t, int dirs, size_t n, Launch&& lau
     return FA_OK;
 }
 
-// The event pair of the next fold launch.  The pool is bounded: a full one is read first (the exact counts replace the bounds -
-// no larger, so room reserved before still holds).
-template <class T>
-static int tab_next_event(fa_ctx* c, TabPair<T>& t, typename TabPair<T>::Ev*& ev) {
-    if (t.ev_used == t.ev.size()) {
-        if (t.ev.size() >= 1024) {
-            typename T::Counters h;
-            int rc = tab_settle(c, t, h);
-            if (rc) return rc;
-        } else {
-            typename TabPair<T>::Ev e{};
-            HIPCHK(c, hipEventCreate(&e.e0));
-            if (hipEventCreate(&e.e1) != hipSuccess) {
-                (void)hipEventDestroy(e.e0);
-                return fail(c, FA_ERR_HIP, "hipEventCreate failed");
-            }
-            t.ev.push_back(e);
-        }
-    }
-    ev = &t.ev[t.ev_used++];
-    return FA_OK;
-}
-// One fold launch over m records, timed: kernel(grid) launches it on the ctx stream.
+// One fold launch over m records, timed: kernel(grid) launches it on the ctx stream.  The pool of event pairs is bounded: a
+// full one is read first (the exact counts replace the bounds - no larger, so room reserved before still holds).
 // persistent grid: the workgroups that are co-resident, records grid-strided
 template <class T, class Kernel>
 static int tab_fold_launch(fa_ctx* c, TabPair<T>& t, size_t m, Kernel&& kernel) {
-    typename TabPair<T>::Ev* ev = nullptr;
-    int rc = tab_next_event(c, t, ev);
-    if (rc) return rc;
+    if (t.ev.used() + 2 > TAB_EV_MAX) {
+        typename T::Counters h;
+        int rc = tab_settle(c, t, h);
+        if (rc) return rc;
+    }
+    const hipEvent_t* ev = t.ev.take(2);
+    if (!ev) return events_failed(c);
     const uint32_t grid = (uint32_t)std::max<size_t>(1, std::min<size_t>((m + T::BLOCK - 1) / T::BLOCK, (size_t)c->num_cus * t.wgpc));
-    (void)hipEventRecord(ev->e0, c->stream);
+    (void)hipEventRecord(ev[0], c->stream);
     kernel(dim3(grid));
-    (void)hipEventRecord(ev->e1, c->stream);
+    (void)hipEventRecord(ev[1], c->stream);
     HIPCHK(c, hipGetLastError());
     t.fold_launches++;
     return FA_OK;

@@ -27,18 +27,10 @@ struct Lz4State {
     std::vector<uint64_t> starts;
     uint64_t raw_takes = 0;
     DevBuf<uint8_t> one;  // fa_lz4_frame_device's result
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // before / behind the block kernel, behind the pack kernel
+    Events ev;            // 3: before / behind the block kernel, behind the pack kernel
     uint64_t n_frames = 0, n_blocks = 0, n_stored = 0, bytes_in = 0, bytes_out = 0, launches = 0, block_ns = 0, pack_ns = 0;
 };
 
-static void lz4_destroy(fa_ctx* c) {
-    Lz4State* z = c->lz4;
-    if (!z) return;
-    for (hipEvent_t e : z->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete z;
-    c->lz4 = nullptr;
-}
 // fa_raw_reset: the buffers go, the counters of fa_raw_lz4_stats go on counting
 static void lz4_release(fa_ctx* c) {
     Lz4State* z = c->lz4;
@@ -48,18 +40,9 @@ static void lz4_release(fa_ctx* c) {
     z->starts.clear();
 }
 static int lz4_state(fa_ctx* c, Lz4State** out) {
-    if (!c->lz4) {
-        Lz4State* z = new Lz4State();
-        c->lz4 = z;
-        for (int i = 0; i < 3; i++)
-            if (hipEventCreate(&z->ev[i]) != hipSuccess) {
-                (void)hipGetLastError();
-                lz4_destroy(c);
-                return fail(c, FA_ERR_HIP, "hipEventCreate failed");
-            }
-    }
+    const int rc = state_with_events(c, c->lz4, 3);
     *out = c->lz4;
-    return FA_OK;
+    return rc;
 }
 
 // ---- host only: the bound, the twin ------------------------------------------------------------------------------------------------
@@ -191,9 +174,8 @@ static int lz4_compress(fa_ctx* c, Lz4State* z, const std::vector<Lz4Src>& in, D
     bool ok = end > *used && end <= *used + bound && h_fo[nf + 1] <= nb;
     for (size_t f = 0; f < nf && ok; f++) ok = h_fo[f] >= *used && h_fo[f] < end && (f == 0 ? h_fo[f] == *used : h_fo[f] > h_fo[f - 1]);
     if (!ok) return fail(c, FA_ERR_HIP, "internal: the LZ4 frame offsets are inconsistent");
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, z->ev[0], z->ev[1]) == hipSuccess) z->block_ns += (uint64_t)((double)ms * 1e6);
-    if (hipEventElapsedTime(&ms, z->ev[1], z->ev[2]) == hipSuccess) z->pack_ns += (uint64_t)((double)ms * 1e6);
+    Events::elapsed_ns(z->ev[0], z->ev[1], &z->block_ns);
+    Events::elapsed_ns(z->ev[1], z->ev[2], &z->pack_ns);
     for (size_t f = 0; f < nf; f++) starts.push_back(h_fo[f]);
     z->n_frames += nf, z->n_blocks += nb, z->n_stored += h_fo[nf + 1], z->bytes_in += bytes, z->bytes_out += end - *used, z->launches += 3;
     *used = end;

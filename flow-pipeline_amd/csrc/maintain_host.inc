@@ -165,25 +165,19 @@ static int settle(fa_ctx* c) {
     }
     HIPCHK(c, hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < c->ev_used; i++) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_pool[i].e0, c->ev_pool[i].e1) == hipSuccess) {
-            c->stats.kernel_ns = (uint64_t)((double)ms * 1e6);
-            c->stats.kernel_ns_total += c->stats.kernel_ns;
+    for (size_t i = 0; i + 2 < c->ev_pool.used(); i += 3) {
+        uint64_t ns = 0;
+        if (Events::elapsed_ns(c->ev_pool[i], c->ev_pool[i + 1], &ns)) {
+            c->stats.kernel_ns = ns;
+            c->stats.kernel_ns_total += ns;
             c->stats.kernel_launches += 1;
         }
-        if (hipEventElapsedTime(&ms, c->ev_pool[i].e0, c->ev_pool[i].e2) == hipSuccess)
-            c->stats.batch_ns_total += (uint64_t)((double)ms * 1e6);
+        Events::elapsed_ns(c->ev_pool[i], c->ev_pool[i + 2], &c->stats.batch_ns_total);
     }
-    c->ev_used = 0;
-    for (size_t i = 0; i < c->dev_used; i++) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, c->dev_pool[i].e0, c->dev_pool[i].e2) == hipSuccess) {
-            c->stats.decode_ns_total += (uint64_t)((double)ms * 1e6);
-            c->stats.decode_launches += 1;
-        }
-    }
-    c->dev_used = 0;
+    c->ev_pool.rewind();
+    for (size_t i = 0; i + 2 < c->dev_pool.used(); i += 3)
+        if (Events::elapsed_ns(c->dev_pool[i], c->dev_pool[i + 2], &c->stats.decode_ns_total)) c->stats.decode_launches += 1;
+    c->dev_pool.rewind();
     Counters h = *c->h_ctr;
     c->stats.records_ok = h.ok;
     c->stats.records_bad = h.bad;

@@ -12,7 +12,6 @@ struct PortState : TabPair<PortTab> {
 };
 
 static uint32_t port_bucket_secs(const fa_ctx* c) { return c->ports ? c->ports->bucket_secs : 0; }
-static void port_destroy(fa_ctx* c) { tab_destroy(c->ports); }
 
 #define PORT_ENTER(c) TAB_ENTER(c, ports, PORT_OFF)
 

@@ -16,7 +16,7 @@ struct RawState {
     std::vector<fa_raw_part> pending;
     DevBuf<> scratch;      // flags, positions, 2 x keys, 2 x indices, the part list, hipcub storage
     PinnedBuf<uint8_t> h_list;  // the part list's first RAW_LIST_FIRST bytes on their way to the host
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // build start, order done, first gather launch, gather done
+    Events ev;             // 4: build start, order done, first gather launch, gather done
     bool ev_pending = false;
     uint64_t records_in = 0, records_bad = 0, rows_out = 0, parts_out = 0, bytes_out = 0, chunks = 0;
     uint64_t order_ns = 0, gather_ns = 0, launches = 0;
@@ -30,10 +30,7 @@ static void raw_destroy(fa_ctx* c) {
     if (getenv("FA_VERBOSE"))
         fprintf(stderr, "[flowagg] raw parts: %llu records in %llu chunks, order %llu ns, gather %llu ns\n", (unsigned long long)t->records_in, (unsigned long long)t->chunks,
                 (unsigned long long)t->order_ns, (unsigned long long)t->gather_ns);
-    for (hipEvent_t e : t->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete t;
-    c->raw = nullptr;
+    state_destroy(c->raw);
 }
 
 #define RAW_ENTER(c, fn)                                                                                   \
@@ -99,9 +96,7 @@ extern "C" int fa_raw_enable(fa_ctx* c, uint32_t chunk_records) {
     RawState* t = new RawState();
     if (chunk_records) t->chunk = chunk_records;
     c->raw = t;
-    bool ok = t->h_list.grow(RAW_LIST_FIRST);
-    for (int i = 0; i < 4 && ok; i++) ok = hipEventCreate(&t->ev[i]) == hipSuccess;
-    if (!ok) {
+    if (!t->h_list.grow(RAW_LIST_FIRST) || !t->ev.ensure(4)) {
         (void)hipGetLastError();
         raw_destroy(c);
         return fail(c, FA_ERR_NOMEM, "fa_raw_enable: allocating the part list's staging failed");
@@ -114,8 +109,7 @@ static size_t raw_chunk_cap(const fa_ctx* c) { return c->raw->chunk; }
 // the gather of the last build has finished (the caller synchronised, or does so here): its time is added
 static void raw_read_events(RawState* t) {
     if (!t->ev_pending) return;
-    float ms = 0;
-    if (hipEventSynchronize(t->ev[3]) == hipSuccess && hipEventElapsedTime(&ms, t->ev[2], t->ev[3]) == hipSuccess) t->gather_ns += (uint64_t)((double)ms * 1e6);
+    if (hipEventSynchronize(t->ev[3]) == hipSuccess) Events::elapsed_ns(t->ev[2], t->ev[3], &t->gather_ns);
     t->ev_pending = false;
 }
 
@@ -232,10 +226,7 @@ static int raw_build_chunk(fa_ctx* c, const fa_columns& cols, size_t m) {
     std::vector<RawPartEntry> ent;
     rc = raw_order_and_list(c, o, pos, t->ev[1], &t->launches, 5, &h, &ent);
     if (rc) return rc;
-    {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, t->ev[0], t->ev[1]) == hipSuccess) t->order_ns += (uint64_t)((double)ms * 1e6);
-    }
+    Events::elapsed_ns(t->ev[0], t->ev[1], &t->order_ns);
     if (h.good > n || h.nparts > RAW_MAX_DATES || (h.good != 0) != (h.nparts != 0)) return fail(c, FA_ERR_HIP, "internal: the raw part list is inconsistent");
     // (the counters move only once the chunk's parts are certain to be built: rows_out + records_bad == records_in always holds)
     auto count_chunk = [&] {

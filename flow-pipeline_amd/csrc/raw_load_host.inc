@@ -18,20 +18,12 @@ struct LoadState {
     DevBuf<> meta;        // block plan, part plan | block status, part verdicts (the second half comes back in one copy)
     PinnedBuf<> h_meta;   // both halves on their way
     DevBuf<> cols;        // one chunk of columns (fa_raw_columns_device: every row of the call)
-    std::vector<hipEvent_t> ev;  // [0], [1]: around the decode kernel; then per chunk: before unpack, behind unpack, behind the folds
-    size_t ev_used = 2;
+    Events ev;            // [0], [1]: around the decode kernel; then per chunk: before unpack, behind unpack, behind the folds
     uint64_t calls = 0, frames = 0, blocks = 0, stored = 0, bytes_in = 0, bytes_decoded = 0, parts = 0, rows_loaded = 0, launches = 0;
     uint64_t decode_ns = 0, unpack_ns = 0, fold_ns = 0;
 };
 static constexpr size_t LOAD_EV_MAX = 2 + 3 * 256;  // chunks whose times are pending before the stream is waited for
 
-static void load_destroy(fa_ctx* c) {
-    LoadState* s = c->load;
-    if (!s) return;
-    for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
-    delete s;
-    c->load = nullptr;
-}
 // fa_raw_load_reset, fa_raw_reset: the buffers go, the counters of fa_raw_load_stats go on counting
 static void load_release(fa_ctx* c) {
     LoadState* s = c->load;
@@ -40,31 +32,20 @@ static void load_release(fa_ctx* c) {
     select_release(c);
     query_release(c);
 }
-static int load_event(fa_ctx* c, LoadState* s, size_t i) {
-    while (s->ev.size() <= i) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, FA_ERR_HIP, "hipEventCreate failed");
-        }
-        s->ev.push_back(e);
-    }
-    return FA_OK;
-}
 static int load_state(fa_ctx* c, LoadState** out) {
     select_drop(c);  // (every decode, load, restore, range and select door starts here: a selection lives until the next of them)
-    if (!c->load) c->load = new LoadState();
+    const int rc = state_with_events(c, c->load, 2);
+    if (rc == FA_OK) c->load->ev.rewind(2);  // (the decode's pair stays; chunk events of a call that failed half-way are dropped unread)
     *out = c->load;
-    return load_event(c, c->load, 1);
+    return rc;
 }
 // the chunks' events (the stream was waited for): their times are added, the pool is free again
 static void load_read_events(LoadState* s) {
-    float ms = 0;
-    for (size_t i = 2; i + 2 < s->ev_used; i += 3) {
-        if (hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]) == hipSuccess) s->unpack_ns += (uint64_t)((double)ms * 1e6);
-        if (hipEventElapsedTime(&ms, s->ev[i + 1], s->ev[i + 2]) == hipSuccess) s->fold_ns += (uint64_t)((double)ms * 1e6);
+    for (size_t i = 2; i + 2 < s->ev.used(); i += 3) {
+        Events::elapsed_ns(s->ev[i], s->ev[i + 1], &s->unpack_ns);
+        Events::elapsed_ns(s->ev[i + 1], s->ev[i + 2], &s->fold_ns);
     }
-    s->ev_used = 2;
+    s->ev.rewind(2);
 }
 
 // ---- host only: the twin (the frame walk and the decoder over lz4_seq_parse: lz4_decode.cuh) ---------------------------------------
@@ -147,7 +128,6 @@ static int load_prepare(fa_ctx* c, LoadState* s, const char* fn, const uint8_t* 
         c->err = std::string(fn) + ": " + why;
         return FA_ERR_FRAMING;
     };
-    s->ev_used = 2;  // (chunk events of a call that failed half-way are dropped unread)
     std::string err;
     std::vector<RawPartPlan> pplan;
     bool lz4 = false;
@@ -193,10 +173,7 @@ static int load_prepare(fa_ctx* c, LoadState* s, const char* fn, const uint8_t* 
     if (nb + np) HIPCHK(c, hipMemcpyAsync(hb, d_st, st_b + ver_b, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     s->launches += launches;
-    if (nb) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) s->decode_ns += (uint64_t)((double)ms * 1e6);
-    }
+    if (nb) Events::elapsed_ns(s->ev[0], s->ev[1], &s->decode_ns);
     const Lz4DecStatus* st = (const Lz4DecStatus*)hb;
     const RawPartVerdict* ver = (const RawPartVerdict*)(hb + st_b);
     // ---- validation, in input order
@@ -282,6 +259,32 @@ static int load_unpack(fa_ctx* c, LoadState* s, const LoadPart& part, uint32_t r
     s->launches++;
     return FA_OK;
 }
+// One chunk of a load door, timed: rows [r0, r0 + m) of a part unpacked into the ctx's column chunk and handed to fold(cols, m).
+// A failed unpack returns before the chunk's three events count; a failed fold after they do (the next call drops them unread).
+template <class Fold>
+static int load_chunk(fa_ctx* c, LoadState* s, const LoadPart& part, uint64_t r0, size_t m, Fold&& fold) {
+    fa_columns cols;
+    void* dst[RAW_NCOLS];
+    int rc = load_columns(c, s, m, &cols, dst);
+    if (rc) return rc;
+    if (s->ev.used() + 3 > LOAD_EV_MAX) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        load_read_events(s);
+    }
+    const size_t at = s->ev.used();
+    if (!s->ev.ensure(at + 3)) return events_failed(c);
+    (void)hipEventRecord(s->ev[at], c->stream);
+    HIPCHK(c, hipMemsetAsync(const_cast<uint8_t*>(cols.status), 0, m, c->stream));
+    rc = load_unpack(c, s, part, (uint32_t)r0, (uint32_t)m, dst, 0);
+    if (rc) return rc;
+    (void)hipEventRecord(s->ev[at + 1], c->stream);
+    rc = fold(cols, m);
+    (void)hipEventRecord(s->ev[at + 2], c->stream);
+    s->ev.take(3);  // (the chunk's events count from here on: they exist, nothing is created)
+    if (rc) return rc;
+    s->rows_loaded += m;
+    return FA_OK;
+}
 
 extern "C" int fa_raw_columns_device(fa_ctx* c, const uint8_t* bytes, size_t n, fa_columns* out, size_t* rows_out) {
     LOAD_ENTER(c);
@@ -329,27 +332,8 @@ extern "C" int fa_raw_load(fa_ctx* c, const uint8_t* bytes, size_t n) {
             size_t m = (size_t)std::min<uint64_t>(p.rows - r0, (uint64_t)1 << 24);
             if (c->talk) m = std::min(m, talk_chunk_cap(c));
             if (c->ports) m = std::min(m, port_chunk_cap(c));
-            fa_columns cols;
-            void* dst[RAW_NCOLS];
-            rc = load_columns(c, s, m, &cols, dst);
+            rc = load_chunk(c, s, p, r0, m, [&](const fa_columns& cols, size_t m) { return fold_chunk_cols(c, cols, m); });
             if (rc) return rc;
-            if (s->ev_used + 3 > LOAD_EV_MAX) {
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                load_read_events(s);
-            }
-            rc = load_event(c, s, s->ev_used + 2);
-            if (rc) return rc;
-            hipEvent_t* e = &s->ev[s->ev_used];
-            (void)hipEventRecord(e[0], c->stream);
-            HIPCHK(c, hipMemsetAsync(const_cast<uint8_t*>(cols.status), 0, m, c->stream));
-            rc = load_unpack(c, s, p, (uint32_t)r0, (uint32_t)m, dst, 0);
-            if (rc) return rc;
-            (void)hipEventRecord(e[1], c->stream);
-            rc = fold_chunk_cols(c, cols, m);
-            (void)hipEventRecord(e[2], c->stream);
-            s->ev_used += 3;
-            if (rc) return rc;
-            s->rows_loaded += m;
             r0 += m;
         }
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -15,37 +15,15 @@ struct RawMergeState {
     DevBuf<uint8_t> spare;     // the image the next merge writes: the one the last merge read
     DevBuf<> scratch;          // 2 x keys, 2 x indices (+ the word raw_parts_kernel reads as pos[n]), descriptors, the Date list, hipcub storage
     PinnedBuf<uint8_t> h_src;  // the descriptors on their way in
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // order start / done, gather start / done
+    Events ev;                 // 4: order start / done, gather start / done
     uint64_t merges = 0, parts_in = 0, parts_out = 0, rows = 0, bytes_in = 0, bytes_out = 0, launches = 0, order_ns = 0, gather_ns = 0;
 };
 
-static void raw_merge_destroy(fa_ctx* c) {
-    RawMergeState* m = c->raw_merge;
-    if (!m) return;
-    for (hipEvent_t e : m->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete m;
-    c->raw_merge = nullptr;
-}
 // fa_raw_reset: the buffers go, the counters of fa_raw_merge_stats go on counting
 static void raw_merge_release(fa_ctx* c) {
     RawMergeState* m = c->raw_merge;
     if (!m) return;
     m->spare.reset(), m->scratch.reset(), m->h_src.reset();
-}
-static int raw_merge_state(fa_ctx* c, RawMergeState** out) {
-    if (!c->raw_merge) {
-        RawMergeState* m = new RawMergeState();
-        c->raw_merge = m;
-        for (int i = 0; i < 4; i++)
-            if (hipEventCreate(&m->ev[i]) != hipSuccess) {
-                (void)hipGetLastError();
-                raw_merge_destroy(c);
-                return fail(c, FA_ERR_HIP, "hipEventCreate failed");
-            }
-    }
-    *out = c->raw_merge;
-    return FA_OK;
 }
 
 extern "C" int fa_raw_merge(fa_ctx* c) {
@@ -78,9 +56,9 @@ extern "C" int fa_raw_merge(fa_ctx* c) {
     if (bytes_out > t->used) return fail(c, FA_ERR_HIP, "internal: the merged parts are larger than their sources");
 
     // ---- everything the merge needs, before anything changes
-    RawMergeState* m = nullptr;
-    int rc = raw_merge_state(c, &m);
+    int rc = state_with_events(c, c->raw_merge, 4);
     if (rc) return rc;
+    RawMergeState* m = c->raw_merge;
     HIPCHK(c, hipStreamSynchronize(c->stream));  // (the last build's gather has written the image)
     raw_read_events(t);
     RawOrder o(c, n);
@@ -149,9 +127,8 @@ extern "C" int fa_raw_merge(fa_ctx* c) {
     (void)hipEventRecord(m->ev[3], c->stream);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // ---- the gather has finished: the images change places (the old one is the next spare), the pending list is the merged one
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, m->ev[0], m->ev[1]) == hipSuccess) m->order_ns += (uint64_t)((double)ms * 1e6);
-    if (hipEventElapsedTime(&ms, m->ev[2], m->ev[3]) == hipSuccess) m->gather_ns += (uint64_t)((double)ms * 1e6);
+    Events::elapsed_ns(m->ev[0], m->ev[1], &m->order_ns);
+    Events::elapsed_ns(m->ev[2], m->ev[3], &m->gather_ns);
     m->merges++, m->parts_in += nsrc, m->parts_out += out.size(), m->rows += n, m->bytes_in += t->used, m->bytes_out += used, m->launches += launches;
     std::swap(t->img, m->spare);
     t->used = used;

@@ -19,12 +19,12 @@ struct QueryTabs : TabPair<QueryTab> {
 };
 struct QueryState {
     QueryTabs* tabs = nullptr;  // nullptr until the first query and after a release
+    ~QueryState() { delete tabs; }
     uint32_t groups = 0;        // of the result held (0: none)
     DevBuf<> plan;              // the slices of the call
     PinnedBuf<> h_plan;
     DevBuf<> rows, order, top;  // a read: the kind's rows collected; the order's scratch; the rows returned
-    hipEvent_t ev[2] = {};      // around a read's launches
-    bool ev_ok = false;
+    Events ev;                  // 2: around a read's launches
     fa_raw_query_stats_t st{};  // calls, rows_scanned, updates, launches (reads), order_ns; the rest comes from the tables
     uint64_t matched0 = 0, absorbed0 = 0, grows0 = 0, launches0 = 0, fold_ns0 = 0;  // ... of tables that were released
     uint64_t matched_seen = 0;  // rows matched up to the last call's end (a call's updates = its matched rows x its kinds)
@@ -38,37 +38,20 @@ static void query_bank(fa_ctx* c, QueryState* q) {
     if (tab_settle(c, *t, h) == FA_OK) q->matched0 += h.folded, q->absorbed0 += h.absorbed;
     q->grows0 += t->grows, q->launches0 += t->fold_launches, q->fold_ns0 += t->fold_ns_total;
 }
-static void query_destroy(fa_ctx* c) {
-    QueryState* q = c->query;
-    if (!q) return;
-    tab_destroy(q->tabs);
-    if (q->ev_ok)
-        for (hipEvent_t e : q->ev) (void)hipEventDestroy(e);
-    delete q;
-    c->query = nullptr;
-}
 // fa_raw_load_reset, fa_raw_reset: the result and the buffers go, the counters of fa_raw_query_stats go on counting
 static void query_release(fa_ctx* c) {
     QueryState* q = c->query;
     if (!q) return;
     query_bank(c, q);
-    tab_destroy(q->tabs);
+    state_destroy(q->tabs);
     q->groups = 0;
     q->plan.reset(), q->h_plan.reset(), q->rows.reset(), q->order.reset(), q->top.reset();
 }
 static int query_state(fa_ctx* c, QueryState** out, bool tables) {
-    if (!c->query) {
-        std::unique_ptr<QueryState> q(new QueryState());
-        for (hipEvent_t& e : q->ev)
-            if (hipEventCreate(&e) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(c, FA_ERR_HIP, "hipEventCreate failed");
-            }
-        q->ev_ok = true;
-        c->query = q.release();
-    }
+    int rc = state_with_events(c, c->query, 2);
+    if (rc) return rc;
     if (tables && !c->query->tabs) {
-        int rc = tab_enable<QueryTab>(c, c->query->tabs, "fa_raw_query", 0, 0);
+        rc = tab_enable<QueryTab>(c, c->query->tabs, "fa_raw_query", 0, 0);
         if (rc) return rc;
     }
     *out = c->query;
@@ -111,13 +94,11 @@ extern "C" int fa_raw_query(fa_ctx* c, const uint8_t* bytes, size_t n, const fa_
     rc = range_run(c, s, g, "fa_raw_query", bytes, n, f.t_lo, f.t_hi, true, (size_t)-1, nullptr, run);
     if (rc) return rc;
     // (from here on every byte the fold kernel reads is decoded and validated)
-    std::vector<const RangePart*> sl;
-    uint64_t scanned = 0, ntiles64 = 0;
-    for (const RangePart& p : run.parts)
-        if (p.r_lo < p.r_hi) sl.push_back(&p), scanned += p.r_hi - p.r_lo, ntiles64 += raw_select_tiles(p.r_hi - p.r_lo);
-    const size_t ns = sl.size();
-    if (ntiles64 > 0x7FFFFFFFull) return fail(c, FA_ERR_ARG, "fa_raw_query: more than 2^39 rows in the time range of one call; query the file in pieces with KEEP");
-    const uint32_t ntiles = (uint32_t)ntiles64, kinds = (uint32_t)__builtin_popcount(qa.groups);
+    const SelectSlices slices(run);
+    const size_t ns = slices.sl.size();
+    const uint64_t scanned = slices.scanned;
+    if (slices.ntiles > 0x7FFFFFFFull) return fail(c, FA_ERR_ARG, "fa_raw_query: more than 2^39 rows in the time range of one call; query the file in pieces with KEEP");
+    const uint32_t ntiles = (uint32_t)slices.ntiles, kinds = (uint32_t)__builtin_popcount(qa.groups);
     if (ns) {
         rc = ensure_dev(c, q->plan, ns * sizeof(RawSelectPart), "query plan");
         if (rc) return rc;
@@ -126,12 +107,7 @@ extern "C" int fa_raw_query(fa_ctx* c, const uint8_t* bytes, size_t n, const fa_
             return fail(c, FA_ERR_NOMEM, "hipHostMalloc(query plan) failed; nothing was folded");
         }
         RawSelectPart* h_parts = (RawSelectPart*)q->h_plan.get();
-        uint32_t tile0 = 0;
-        for (size_t j = 0; j < ns; j++) {
-            const RangePart& p = *sl[j];
-            h_parts[j] = RawSelectPart{p.plan.off, (uint32_t)p.rows, (uint32_t)p.r_lo, (uint32_t)p.r_hi, tile0, 0, 0};
-            tile0 += (uint32_t)raw_select_tiles(p.r_hi - p.r_lo);
-        }
+        slices.plan(h_parts, false);
         HIPCHK(c, hipMemcpyAsync(q->plan.get(), h_parts, ns * sizeof(RawSelectPart), hipMemcpyHostToDevice, c->stream));
         for (uint32_t t0 = 0; t0 < ntiles;) {
             const uint32_t nt = std::min(ntiles - t0, raw_query_launch_tiles(t.chunk, kinds));
@@ -209,8 +185,7 @@ static int query_rows(fa_ctx* c, const char* fn, uint32_t group, int order, size
     return FA_OK;
 }
 static void query_read_time(QueryState* q) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, q->ev[0], q->ev[1]) == hipSuccess) q->st.order_ns += (uint64_t)((double)ms * 1e6);
+    Events::elapsed_ns(q->ev[0], q->ev[1], &q->st.order_ns);
 }
 
 extern "C" int fa_raw_query_rows(fa_ctx* c, uint32_t group, int order, size_t k, fa_query_row* out, size_t cap, size_t* n_out) {

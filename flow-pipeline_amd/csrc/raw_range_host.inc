@@ -16,32 +16,14 @@
 // keep what an earlier call left and are never read (DESIGN 3.9) -, the plans, one chunk of columns.
 
 struct RangeState {
-    hipEvent_t ev[8] = {};  // pairs around: stage A's kernels, stage B's decode, raw_range_kernel, stage C's decode
-    bool ev_ok = false;
+    Events ev;  // 8: pairs around stage A's kernels, stage B's decode, raw_range_kernel, stage C's decode
     fa_raw_range_stats_t st{};
 };
 
-static void range_destroy(fa_ctx* c) {
-    RangeState* g = c->range;
-    if (!g) return;
-    if (g->ev_ok)
-        for (hipEvent_t e : g->ev) (void)hipEventDestroy(e);
-    delete g;
-    c->range = nullptr;
-}
 static int range_state(fa_ctx* c, RangeState** out) {
-    if (!c->range) {
-        std::unique_ptr<RangeState> g(new RangeState());
-        for (hipEvent_t& e : g->ev)
-            if (hipEventCreate(&e) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(c, FA_ERR_HIP, "hipEventCreate failed");
-            }
-        g->ev_ok = true;
-        c->range = g.release();
-    }
+    const int rc = state_with_events(c, c->range, 8);
     *out = c->range;
-    return FA_OK;
+    return rc;
 }
 
 struct RangePart {
@@ -64,7 +46,6 @@ static int range_run(fa_ctx* c, LoadState* s, RangeState* g, const char* fn, con
         c->err = std::string(fn) + ": " + why;
         return FA_ERR_FRAMING;
     };
-    s->ev_used = 2;  // (chunk events of a call that failed half-way are dropped unread)
     LoadPrepared pr;
     std::vector<RawPartPlan> pplan;
     bool lz4 = false;
@@ -84,9 +65,8 @@ static int range_run(fa_ctx* c, LoadState* s, RangeState* g, const char* fn, con
     uint64_t launches = 0, blocks_decoded = 0, stored = 0, bytes_decoded = 0;
     auto commit_launches = [&] { s->launches += launches, g->st.launches += launches, launches = 0; };
     auto add_ns = [&](uint64_t* a, uint64_t* b, hipEvent_t e0, hipEvent_t e1) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return;
-        const uint64_t ns = (uint64_t)((double)ms * 1e6);
+        uint64_t ns = 0;
+        Events::elapsed_ns(e0, e1, &ns);
         *a += ns;
         if (b) *b += ns;
     };
@@ -110,10 +90,10 @@ static int range_run(fa_ctx* c, LoadState* s, RangeState* g, const char* fn, con
         std::vector<uint8_t> done(nb, 0);
         std::vector<uint32_t> order;  // plan entry k decodes block order[k]
         order.reserve(nb);
-        // plan entries [k0, order.size()) -> the device, one decode launch between the events e[0], e[1], their status words back
-        auto decode = [&](size_t k0, hipEvent_t* e) -> int {
+        // plan entries [k0, order.size()) -> the device, one decode launch between the events e, e + 1, their status words back
+        auto decode = [&](size_t k0, size_t e) -> int {
             const size_t k1 = order.size();
-            (void)hipEventRecord(e[0], c->stream);
+            (void)hipEventRecord(g->ev[e], c->stream);
             if (k1 > k0) {
                 for (size_t k = k0; k < k1; k++) {
                     const Lz4WalkBlock& w = pr.walk.blocks[order[k]];
@@ -128,7 +108,7 @@ static int range_run(fa_ctx* c, LoadState* s, RangeState* g, const char* fn, con
                 HIPCHK(c, hipMemcpyAsync(hb + o_st + k0 * sizeof(Lz4DecStatus), mb + o_st + k0 * sizeof(Lz4DecStatus), (k1 - k0) * sizeof(Lz4DecStatus), hipMemcpyDeviceToHost, c->stream));
                 blocks_decoded += k1 - k0;
             }
-            (void)hipEventRecord(e[1], c->stream);
+            (void)hipEventRecord(g->ev[e + 1], c->stream);
             return FA_OK;
         };
         // the verdict on plan entry k (behind the stage's wait)
@@ -158,7 +138,7 @@ static int range_run(fa_ctx* c, LoadState* s, RangeState* g, const char* fn, con
                 h_poff[i] = p.off;
             }
             HIPCHK(c, hipMemcpyAsync(mb + o_poff, h_poff, np * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-            rc = decode(0, &g->ev[0]);
+            rc = decode(0, 0);
             if (rc) return rc;
             hipLaunchKernelGGL(raw_probe_kernel, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, (const uint64_t*)(mb + o_poff), (uint32_t)np, image, (uint4*)(mb + o_pout));
             (void)hipEventRecord(g->ev[1], c->stream);
@@ -221,7 +201,7 @@ static int range_run(fa_ctx* c, LoadState* s, RangeState* g, const char* fn, con
             kb[ns] = order.size();
             if (tiles > 0x7FFFFFFFu) return fail(c, FA_ERR_ARG, "more than 2^43 rows in the selected parts of one call");
             HIPCHK(c, hipMemcpyAsync(mb + b_pplan, hb + b_pplan, b_ver - b_pplan, hipMemcpyHostToDevice, c->stream));
-            rc = decode(k0, &g->ev[2]);
+            rc = decode(k0, 2);
             if (rc) return rc;
             hipLaunchKernelGGL(raw_header_check_kernel, dim3((unsigned)ns), dim3(64), 0, c->stream, (const RawPartPlan*)(mb + b_pplan), (const uint32_t*)(mb + o_st), image,
                                (RawPartVerdict*)(mb + b_ver));
@@ -263,7 +243,7 @@ static int range_run(fa_ctx* c, LoadState* s, RangeState* g, const char* fn, con
             for (const RangePart& p : run.parts)
                 if (p.r_lo < p.r_hi) raw_range_load_blocks(RAW_COLS_H, p.rows, p.plan.first_block, p.plan.nblocks, p.r_lo, p.r_hi, done, order);
             if (order.size() > k0) {
-                rc = decode(k0, &g->ev[6]);
+                rc = decode(k0, 6);
                 if (rc) return rc;
                 HIPCHK(c, hipStreamSynchronize(c->stream));
                 commit_launches();

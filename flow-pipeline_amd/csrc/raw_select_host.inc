@@ -18,19 +18,10 @@ struct SelectState {
     DevBuf<> work;         // slices, sources | masks, counts, bases | totals, spans | outs | hipcub's storage
     DevBuf<> order;        // idx, key of the delivered rows
     PinnedBuf<> h_work;    // slices, sources, outs on their way in; totals, spans on their way back
-    hipEvent_t ev[6] = {};  // pairs around: the select kernel with the scan, the emit kernel, the gathers
-    bool ev_ok = false;
+    Events ev;             // 6: pairs around the select kernel with the scan, the emit kernel, the gathers
     fa_raw_select_stats_t st{};
 };
 
-static void select_destroy(fa_ctx* c) {
-    SelectState* q = c->select;
-    if (!q) return;
-    if (q->ev_ok)
-        for (hipEvent_t e : q->ev) (void)hipEventDestroy(e);
-    delete q;
-    c->select = nullptr;
-}
 // the next select, decode, load, restore or range call: the selection is gone (its memory is kept)
 static void select_drop(fa_ctx* c) {
     if (c->select) c->select->sel_bytes = 0;
@@ -42,20 +33,26 @@ static void select_release(fa_ctx* c) {
     q->sel_bytes = 0;
     q->sel.reset(), q->work.reset(), q->order.reset(), q->h_work.reset();
 }
-static int select_state(fa_ctx* c, SelectState** out) {
-    if (!c->select) {
-        std::unique_ptr<SelectState> q(new SelectState());
-        for (hipEvent_t& e : q->ev)
-            if (hipEventCreate(&e) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(c, FA_ERR_HIP, "hipEventCreate failed");
-            }
-        q->ev_ok = true;
-        c->select = q.release();
+
+// The slices a range run left - the parts that hold a row of the time range, in input order - and what the select and the
+// query door (raw_query_host.inc) both plan over them.
+struct SelectSlices {
+    std::vector<const RangePart*> sl;
+    uint64_t scanned = 0, src_rows = 0, ntiles = 0;  // rows of the slices, rows of their parts, workgroups of the flattened grid
+    explicit SelectSlices(const RangeRun& run) {
+        for (const RangePart& p : run.parts)
+            if (p.r_lo < p.r_hi) sl.push_back(&p), scanned += p.r_hi - p.r_lo, src_rows += p.rows, ntiles += raw_select_tiles(p.r_hi - p.r_lo);
     }
-    *out = c->select;
-    return FA_OK;
-}
+    // the plan entries: tile0 running; first running (the gather numbers the source rows) or 0
+    void plan(RawSelectPart* h_parts, bool number_rows) const {
+        uint32_t tile0 = 0, first = 0;
+        for (size_t j = 0; j < sl.size(); j++) {
+            const RangePart& p = *sl[j];
+            h_parts[j] = RawSelectPart{p.plan.off, (uint32_t)p.rows, (uint32_t)p.r_lo, (uint32_t)p.r_hi, tile0, number_rows ? first : 0u, 0};
+            tile0 += (uint32_t)raw_select_tiles(p.r_hi - p.r_lo), first += (uint32_t)p.rows;
+        }
+    }
+};
 
 extern "C" int fa_raw_select(fa_ctx* c, const uint8_t* bytes, size_t n, const fa_raw_filter* filter, fa_raw_part* parts, size_t parts_cap, size_t* n_parts, size_t* bytes_out) {
     LOAD_ENTER(c);
@@ -72,19 +69,18 @@ extern "C" int fa_raw_select(fa_ctx* c, const uint8_t* bytes, size_t n, const fa
     RangeState* g = nullptr;
     rc = range_state(c, &g);
     if (rc) return rc;
-    SelectState* q = nullptr;
-    rc = select_state(c, &q);
+    rc = state_with_events(c, c->select, 6);
     if (rc) return rc;
+    SelectState* q = c->select;
     RangeRun run;
     size_t np_in = 0;
     rc = range_run(c, s, g, "fa_raw_select", bytes, n, f.t_lo, f.t_hi, true, parts_cap, &np_in, run);
     if (rc == FA_ERR_CAPACITY) *n_parts = np_in;
     if (rc) return rc;
     // (from here on every byte the select, emit and gather kernels read is decoded and validated)
-    std::vector<const RangePart*> sl;
-    uint64_t scanned = 0, src_rows = 0, ntiles64 = 0;
-    for (const RangePart& p : run.parts)
-        if (p.r_lo < p.r_hi) sl.push_back(&p), scanned += p.r_hi - p.r_lo, src_rows += p.rows, ntiles64 += raw_select_tiles(p.r_hi - p.r_lo);
+    const SelectSlices slices(run);
+    const std::vector<const RangePart*>& sl = slices.sl;
+    const uint64_t scanned = slices.scanned, src_rows = slices.src_rows;
     const size_t ns = sl.size();
     const bool count_only = f.fields & FA_RAW_F_COUNT_ONLY;
     fa_raw_select_stats_t& st = q->st;
@@ -94,7 +90,7 @@ extern "C" int fa_raw_select(fa_ctx* c, const uint8_t* bytes, size_t n, const fa
     }
     if (src_rows > (uint64_t)INT32_MAX)
         return fail(c, FA_ERR_ARG, "fa_raw_select: " + std::to_string(src_rows) + " rows in the parts that hold a row of the time range are more than one gather indexes (2^31 - 1); select the file in pieces");
-    const uint32_t ntiles = (uint32_t)ntiles64;
+    const uint32_t ntiles = (uint32_t)slices.ntiles;
 
     // ---- buffers: the device's work area and its pinned mirror share one layout
     const size_t o_parts = 0, o_src = o_parts + align256(ns * sizeof(RawSelectPart)), o_out = o_src + align256(ns * sizeof(RawMergeSrc));
@@ -116,19 +112,8 @@ extern "C" int fa_raw_select(fa_ctx* c, const uint8_t* bytes, size_t n, const fa
     const RawSelectPart* d_parts = (const RawSelectPart*)(wb + o_parts);
     uint64_t* d_mask = (uint64_t*)(wb + o_mask);
     uint32_t *d_count = (uint32_t*)(wb + o_count), *d_base = (uint32_t*)(wb + o_base);
-    {
-        uint32_t tile0 = 0, first = 0;
-        for (size_t j = 0; j < ns; j++) {
-            const RangePart& p = *sl[j];
-            h_parts[j] = RawSelectPart{p.plan.off, (uint32_t)p.rows, (uint32_t)p.r_lo, (uint32_t)p.r_hi, tile0, first, 0};
-            h_src[j] = RawMergeSrc{run.image + p.plan.off, (uint32_t)p.rows, first};
-            tile0 += (uint32_t)raw_select_tiles(p.r_hi - p.r_lo), first += (uint32_t)p.rows;
-        }
-    }
-    auto add_ns = [&](uint64_t* a, hipEvent_t e0, hipEvent_t e1) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *a += (uint64_t)((double)ms * 1e6);
-    };
+    slices.plan(h_parts, true);
+    for (size_t j = 0; j < ns; j++) h_src[j] = RawMergeSrc{run.image + h_parts[j].off, h_parts[j].rows, h_parts[j].first};
 
     // ---- select: the masks, the scanned bases, the totals
     HIPCHK(c, hipMemcpyAsync(wb + o_parts, hb + o_parts, o_out - o_parts, hipMemcpyHostToDevice, c->stream));
@@ -143,7 +128,7 @@ extern "C" int fa_raw_select(fa_ctx* c, const uint8_t* bytes, size_t n, const fa
     st.launches += 3;
     HIPCHK(c, hipMemcpyAsync(hb + o_tot, wb + o_tot, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    add_ns(&st.select_ns, q->ev[0], q->ev[1]);
+    Events::elapsed_ns(q->ev[0], q->ev[1], &st.select_ns);
 
     // ---- the output's layout: the rows every part delivers under the limit, in input order
     uint64_t matched = 0, left = f.limit ? f.limit : ~(uint64_t)0, total = 0;
@@ -197,8 +182,8 @@ extern "C" int fa_raw_select(fa_ctx* c, const uint8_t* bytes, size_t n, const fa
         (void)hipEventRecord(q->ev[5], c->stream);
         HIPCHK(c, hipMemcpyAsync(hb + o_span, wb + o_span, ns * sizeof(RawSelectSpan), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        add_ns(&st.emit_ns, q->ev[2], q->ev[3]);
-        if (!count_only) add_ns(&st.gather_ns, q->ev[4], q->ev[5]);
+        Events::elapsed_ns(q->ev[2], q->ev[3], &st.emit_ns);
+        if (!count_only) Events::elapsed_ns(q->ev[4], q->ev[5], &st.gather_ns);
         for (size_t i = 0; i < out.size(); i++) {
             out[i].t_min = h_span[from[i]].t_min, out[i].t_max = h_span[from[i]].t_max;
             if (out[i].t_min > out[i].t_max || out[i].t_min / 86400u != out[i].date) return fail(c, FA_ERR_HIP, "internal: an output part's keys are inconsistent");

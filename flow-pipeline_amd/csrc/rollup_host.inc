@@ -10,20 +10,12 @@
 
 struct RollupState {
     DevBuf<unsigned long long> d_bad;  // records with status != 0 the fold launches skipped, so far
-    std::vector<hipEvent_t> ev;        // two per launch: around the kernel
-    size_t ev_used = 0;
+    Events ev;                         // two per launch: around the kernel
     uint32_t wgpc = ROLLUP_WGPC, grid_forced = 0;  // env FA_ROLLUP_WGPC, FA_ROLLUP_GRID (tests: a small grid)
     uint64_t calls = 0, records_in = 0, records_bad = 0, launches = 0, fold_ns = 0;
 };
 static constexpr size_t ROLLUP_EV_MAX = 2 * 256;  // launches whose times are pending before the stream is waited for
 
-static void rollup_destroy(fa_ctx* c) {
-    RollupState* s = c->rollup;
-    if (!s) return;
-    for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
-    delete s;
-    c->rollup = nullptr;
-}
 static int rollup_state(fa_ctx* c, RollupState** out) {
     if (!c->rollup) {
         std::unique_ptr<RollupState> s(new RollupState());
@@ -41,10 +33,8 @@ static int rollup_state(fa_ctx* c, RollupState** out) {
 }
 // the launches' events (the stream was waited for): their times are added, the pool is free again
 static void rollup_read_events(RollupState* s) {
-    float ms = 0;
-    for (size_t i = 0; i + 1 < s->ev_used; i += 2)
-        if (hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]) == hipSuccess) s->fold_ns += (uint64_t)((double)ms * 1e6);
-    s->ev_used = 0;
+    for (size_t i = 0; i + 1 < s->ev.used(); i += 2) Events::elapsed_ns(s->ev[i], s->ev[i + 1], &s->fold_ns);
+    s->ev.rewind();
 }
 
 static size_t rollup_chunk(const fa_ctx* c, uint32_t ks) { return rollup_chunk_cap(c->spill_cap, c->wspill_cap, c->cfg.max_batch_records, ks); }
@@ -61,18 +51,12 @@ static int rollup_fold_cols(fa_ctx* c, const fa_columns& cols, size_t m, uint32_
         rc = wlog_make_room(c, wide_rows);
         if (rc) return rc;
     }
-    if (s->ev_used + 2 > ROLLUP_EV_MAX) {
+    if (s->ev.used() + 2 > ROLLUP_EV_MAX) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         rollup_read_events(s);
     }
-    while (s->ev.size() < s->ev_used + 2) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, FA_ERR_HIP, "hipEventCreate failed");
-        }
-        s->ev.push_back(e);
-    }
+    const hipEvent_t* e = s->ev.take(2);
+    if (!e) return events_failed(c);
     KArgs a = make_args(c);  // (behind the guard and the room: either may have settled and moved a table)
     a.key_sets = ks;
     RollupCols rcols{};
@@ -87,12 +71,10 @@ static int rollup_fold_cols(fa_ctx* c, const fa_columns& cols, size_t m, uint32_
     // persistent grid: wgpc workgroups per CU, never more than the chunk has 256-record runs
     const uint32_t want = s->grid_forced ? s->grid_forced : (uint32_t)c->num_cus * s->wgpc;
     const dim3 grid(std::max<uint32_t>(1u, std::min<uint32_t>(std::min(want, ROLLUP_MAX_GRID), (uint32_t)((m + ROLLUP_BLOCK - 1) / ROLLUP_BLOCK))));
-    hipEvent_t* e = &s->ev[s->ev_used];
     (void)hipEventRecord(e[0], c->stream);
     if (ks == FA_KEYS_AS_PAIR) hipLaunchKernelGGL(rollup_fold_kernel<FA_KEYS_AS_PAIR>, grid, dim3(ROLLUP_BLOCK), 0, c->stream, a, rcols);
     else hipLaunchKernelGGL(rollup_fold_kernel<KS_ALL>, grid, dim3(ROLLUP_BLOCK), 0, c->stream, a, rcols);
     (void)hipEventRecord(e[1], c->stream);
-    s->ev_used += 2;
     HIPCHK(c, hipGetLastError());
     if (c->wtab) c->wpot_total += wide_rows;  // (wide_rows_bound)
     s->launches++;
@@ -188,28 +170,11 @@ extern "C" int fa_raw_load_rollup(fa_ctx* c, const uint8_t* bytes, size_t n, uin
             size_t m = (size_t)std::min<uint64_t>(p.rows - r0, cap);
             if (folds && c->talk) m = std::min(m, talk_chunk_cap(c));
             if (folds && c->ports) m = std::min(m, port_chunk_cap(c));
-            fa_columns cols;
-            void* dst[RAW_NCOLS];
-            rc = load_columns(c, s, m, &cols, dst);
+            rc = load_chunk(c, s, p, r0, m, [&](const fa_columns& cols, size_t m) {
+                const int frc = rollup_fold_cols(c, cols, m, ks);
+                return frc == FA_OK && folds ? fold_chunk_cols(c, cols, m) : frc;
+            });
             if (rc) return rc;
-            if (s->ev_used + 3 > LOAD_EV_MAX) {
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                load_read_events(s);
-            }
-            rc = load_event(c, s, s->ev_used + 2);
-            if (rc) return rc;
-            hipEvent_t* e = &s->ev[s->ev_used];
-            (void)hipEventRecord(e[0], c->stream);
-            HIPCHK(c, hipMemsetAsync(const_cast<uint8_t*>(cols.status), 0, m, c->stream));
-            rc = load_unpack(c, s, p, (uint32_t)r0, (uint32_t)m, dst, 0);
-            if (rc) return rc;
-            (void)hipEventRecord(e[1], c->stream);
-            rc = rollup_fold_cols(c, cols, m, ks);
-            if (rc == FA_OK && folds) rc = fold_chunk_cols(c, cols, m);
-            (void)hipEventRecord(e[2], c->stream);
-            s->ev_used += 3;
-            if (rc) return rc;
-            s->rows_loaded += m;
             r0 += m;
         }
     rc = rollup_finish(c);

@@ -13,20 +13,12 @@
 
 struct SketchFoldState {
     DevBuf<unsigned long long> d_bad;  // records with status != 0 the fold launches skipped, so far
-    std::vector<hipEvent_t> ev;        // two per launch: around the kernel
-    size_t ev_used = 0;
+    Events ev;                         // two per launch: around the kernel
     uint32_t wgpc = SKETCH_WGPC, grid_forced = 0, lds = 1;  // env FA_SKETCH_WGPC, FA_SKETCH_GRID (tests: a small grid), FA_SKETCH_LDS (0: no cache)
     uint64_t calls = 0, records_in = 0, records_bad = 0, batches = 0, launches = 0, fold_ns = 0;
 };
 static constexpr size_t SKETCH_EV_MAX = 2 * 256;  // launches whose times are pending before the stream is waited for
 
-static void sketch_fold_destroy(fa_ctx* c) {
-    SketchFoldState* s = c->sketch_fold;
-    if (!s) return;
-    for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
-    delete s;
-    c->sketch_fold = nullptr;
-}
 static int sketch_fold_state(fa_ctx* c, SketchFoldState** out) {
     if (!c->sketch_fold) {
         std::unique_ptr<SketchFoldState> s(new SketchFoldState());
@@ -45,10 +37,8 @@ static int sketch_fold_state(fa_ctx* c, SketchFoldState** out) {
 }
 // the launches' events (the stream was waited for): their times are added, the pool is free again
 static void sketch_fold_read_events(SketchFoldState* s) {
-    float ms = 0;
-    for (size_t i = 0; i + 1 < s->ev_used; i += 2)
-        if (hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]) == hipSuccess) s->fold_ns += (uint64_t)((double)ms * 1e6);
-    s->ev_used = 0;
+    for (size_t i = 0; i + 1 < s->ev.used(); i += 2) Events::elapsed_ns(s->ev[i], s->ev[i + 1], &s->fold_ns);
+    s->ev.rewind();
 }
 
 // m records (at most sketch_chunk_cap) of `cols` into the sketches `sets` (checked: sketch_mask_check) and their distinct-address sets
@@ -56,18 +46,12 @@ static int sketch_fold_cols(fa_ctx* c, const fa_columns& cols, size_t m, uint32_
     SketchFoldState* s = nullptr;
     int rc = sketch_fold_state(c, &s);
     if (rc) return rc;
-    if (s->ev_used + 2 > SKETCH_EV_MAX) {
+    if (s->ev.used() + 2 > SKETCH_EV_MAX) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         sketch_fold_read_events(s);
     }
-    while (s->ev.size() < s->ev_used + 2) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, FA_ERR_HIP, "hipEventCreate failed");
-        }
-        s->ev.push_back(e);
-    }
+    const hipEvent_t* e = s->ev.take(2);
+    if (!e) return events_failed(c);
     KArgs a = make_args(c);
     a.key_sets = sets;
     SketchCols sc{};
@@ -81,11 +65,9 @@ static int sketch_fold_cols(fa_ctx* c, const fa_columns& cols, size_t m, uint32_
     // persistent grid: wgpc workgroups per CU, never more than the chunk has 256-record runs
     const uint32_t want = s->grid_forced ? s->grid_forced : (uint32_t)c->num_cus * s->wgpc;
     const dim3 grid(std::max<uint32_t>(1u, std::min<uint32_t>(std::min(want, ROLLUP_MAX_GRID), (uint32_t)((m + ROLLUP_BLOCK - 1) / ROLLUP_BLOCK))));
-    hipEvent_t* e = &s->ev[s->ev_used];
     (void)hipEventRecord(e[0], c->stream);
     hipLaunchKernelGGL(sketch_fold_kernel, grid, dim3(ROLLUP_BLOCK), 0, c->stream, a, sc);
     (void)hipEventRecord(e[1], c->stream);
-    s->ev_used += 2;
     HIPCHK(c, hipGetLastError());
     s->launches++;
     s->batches++;
@@ -171,31 +153,14 @@ static int restore_fold_slices(fa_ctx* c, LoadState* s, const std::vector<LoadSl
     const size_t cap = restore_chunk_cap(ks ? rollup_chunk(c, ks) : 0, sets ? sketch_chunk_cap(c->cfg.max_batch_records) : 0, talk ? talk_chunk_cap(c) : 0, ports ? port_chunk_cap(c) : 0);
     for (const LoadSlice& sl : slices)
         for (uint64_t r0 = sl.r_lo; r0 < sl.r_hi;) {  // (chunks end at part boundaries)
-            const LoadPart& p = sl.part;
             const size_t m = (size_t)std::min<uint64_t>(sl.r_hi - r0, cap);
-            fa_columns cols;
-            void* dst[RAW_NCOLS];
-            rc = load_columns(c, s, m, &cols, dst);
+            rc = load_chunk(c, s, sl.part, r0, m, [&](const fa_columns& cols, size_t m) {
+                int frc = ks ? rollup_fold_cols(c, cols, m, ks) : FA_OK;
+                if (frc == FA_OK && sets) frc = sketch_fold_cols(c, cols, m, sets);
+                if (frc == FA_OK && (talk || ports)) frc = fold_chunk_cols(c, cols, m);
+                return frc;
+            });
             if (rc) return rc;
-            if (s->ev_used + 3 > LOAD_EV_MAX) {
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                load_read_events(s);
-            }
-            rc = load_event(c, s, s->ev_used + 2);
-            if (rc) return rc;
-            hipEvent_t* e = &s->ev[s->ev_used];
-            (void)hipEventRecord(e[0], c->stream);
-            HIPCHK(c, hipMemsetAsync(const_cast<uint8_t*>(cols.status), 0, m, c->stream));
-            rc = load_unpack(c, s, p, (uint32_t)r0, (uint32_t)m, dst, 0);
-            if (rc) return rc;
-            (void)hipEventRecord(e[1], c->stream);
-            if (ks) rc = rollup_fold_cols(c, cols, m, ks);
-            if (rc == FA_OK && sets) rc = sketch_fold_cols(c, cols, m, sets);
-            if (rc == FA_OK && (talk || ports)) rc = fold_chunk_cols(c, cols, m);
-            (void)hipEventRecord(e[2], c->stream);
-            s->ev_used += 3;
-            if (rc) return rc;
-            s->rows_loaded += m;
             r0 += m;
         }
     rc = ks ? rollup_finish(c) : settle(c);

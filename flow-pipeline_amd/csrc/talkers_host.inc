@@ -10,7 +10,6 @@ struct TalkState : TabPair<TalkTab> {
 };
 
 static uint32_t talk_bucket_secs(const fa_ctx* c) { return c->talk ? c->talk->bucket_secs : 0; }
-static void talk_destroy(fa_ctx* c) { tab_destroy(c->talk); }
 
 #define TALK_ENTER(c) TAB_ENTER(c, talk, TALK_OFF)
 
