@@ -221,6 +221,19 @@ QUERY_ROW_DTYPE = np.dtype([("key", "u1", 16), ("etype", "<u4"), ("value", "<u4"
 assert C.sizeof(RawQuery) == 104 and C.sizeof(RawQueryStats) == 80 and QUERY_ROW_DTYPE.itemsize == 40
 
 
+class RawPendingStats(C.Structure):
+    """fa_raw_pending_stats_t: what the ctx's calls over its pending parts (raw_pending_probe, raw_query_pending, raw_select_pending)
+    have done so far."""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "calls", "parts_seen", "parts_skipped", "parts_whole", "parts_searched", "rows_seen", "rows_in_range", "bounds_launches", "bounds_ns")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+assert C.sizeof(RawPendingStats) == 72
+
+
 class RawMergeStats(C.Structure):
     """fa_raw_merge_stats_t: what the ctx's merges of pending parts (raw_merge) have done so far."""
     _fields_ = [(n, C.c_uint64) for n in (
@@ -317,6 +330,7 @@ EXPORTS = [
     "fa_raw_range_probe", "fa_raw_restore_range", "fa_raw_range_stats",
     "fa_raw_select", "fa_raw_selection_device", "fa_raw_selection_fetch", "fa_raw_select_stats",
     "fa_raw_query", "fa_raw_query_rows", "fa_raw_query_rows_device", "fa_raw_query_reset", "fa_raw_query_stats",
+    "fa_raw_pending_probe", "fa_raw_query_pending", "fa_raw_select_pending", "fa_raw_pending_stats",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
@@ -539,6 +553,10 @@ def lib():
     L.fa_raw_query_rows_device.argtypes = [vp, C.c_uint32, C.c_int, sz, C.POINTER(C.c_void_p), szp]
     L.fa_raw_query_reset.argtypes = [vp]
     L.fa_raw_query_stats.argtypes = [vp, C.POINTER(RawQueryStats)]
+    L.fa_raw_pending_probe.argtypes = [vp, u32, u32, vp, sz, szp]
+    L.fa_raw_query_pending.argtypes = [vp, C.POINTER(RawQuery)]
+    L.fa_raw_select_pending.argtypes = [vp, C.POINTER(RawFilter), vp, sz, szp, szp]
+    L.fa_raw_pending_stats.argtypes = [vp, C.POINTER(RawPendingStats)]
     L.fa_raw_merge.argtypes = [vp]
     L.fa_raw_merge_stats.argtypes = [vp, C.POINTER(RawMergeStats)]
     _LIB = L
@@ -1275,6 +1293,55 @@ class FlowAgg:
     def raw_query_stats(self) -> dict:
         s = RawQueryStats()
         self._chk(self._L.fa_raw_query_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
+    # -- the pending parts as input (include/flowagg.h "the pending flows_raw parts as input") ----
+    def raw_pending_probe(self, t_lo: int, t_hi: int) -> np.ndarray:
+        """raw_range_probe over the ctx's pending parts, read where they lie in HBM: one RAW_RANGE_DTYPE entry per pending part,
+        build order.  Nothing is copied, taken or changed."""
+        need = C.c_size_t()
+        cap = self.raw_stats()["pending_parts"]
+        out = np.zeros(cap, dtype=RAW_RANGE_DTYPE)
+        self._chk(self._L.fa_raw_pending_probe(self._h, t_lo, t_hi, out.ctypes.data if cap else None, cap, C.byref(need)))
+        return out[:need.value]
+
+    def raw_query_pending(self, groups, t_lo=0, t_hi=0xFFFFFFFF, *, keep=False, filter=None, **conditions):
+        """raw_query over the ctx's pending parts, read where they lie in HBM; the result is read with raw_query_rows.
+        keep: add to the result held - raw_query(bytes of older files) followed by raw_query_pending(keep=True) is one answer over
+        stored and live rows.  The pending parts and the ctx's selection stay as they are."""
+        q = RawQuery()
+        q.where = filter if filter is not None else raw_filter(t_lo, t_hi, **conditions)
+        q.groups, q.flags = groups, RAW_Q_KEEP if keep else 0
+        self._chk(self._L.fa_raw_query_pending(self._h, C.byref(q)))
+
+    def raw_select_pending(self, t_lo=0, t_hi=0xFFFFFFFF, *, flow_start=None, src_as=None, dst_as=None, etype=None, proto=None, src_port=None,
+                           dst_port=None, src_net=None, dst_net=None, either=False, limit=0, count_only=False, out=None, filter=None):
+        """-> (bytes, parts): raw_select over the ctx's pending parts, read where they lie in HBM: one plain Native part per pending
+        part with a match, build order.  The keywords and the return are raw_select's.  The pending parts stay as they are; the
+        selection is a copy and replaces the ctx's selection."""
+        f = filter if filter is not None else raw_filter(t_lo, t_hi, flow_start=flow_start, src_as=src_as, dst_as=dst_as, etype=etype, proto=proto, src_port=src_port,
+                                                         dst_port=dst_port, src_net=src_net, dst_net=dst_net, either=either, limit=limit, count_only=count_only)
+        nparts, nbytes = C.c_size_t(), C.c_size_t()
+        pcap = 16
+        while True:  # (too few descriptions: the library says how many before anything is launched)
+            parts = np.zeros(pcap, dtype=RAW_PART_DTYPE)
+            rc = self._L.fa_raw_select_pending(self._h, C.byref(f), parts.ctypes.data, pcap, C.byref(nparts), C.byref(nbytes))
+            if rc == -6:
+                pcap = nparts.value
+                continue
+            self._chk(rc)
+            break
+        parts = parts[:nparts.value]
+        if f.fields & RAW_F_COUNT_ONLY:
+            return b"", parts
+        buf = out if out is not None and out.dtype == np.uint8 and out.size >= nbytes.value else np.empty(nbytes.value, dtype=np.uint8)
+        self._chk(self._L.fa_raw_selection_fetch(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(nbytes)))
+        sel = buf[:nbytes.value]
+        return (sel if out is not None and buf is out else sel.tobytes()), parts
+
+    def raw_pending_stats(self) -> dict:
+        s = RawPendingStats()
+        self._chk(self._L.fa_raw_pending_stats(self._h, C.byref(s)))
         return s.as_dict()
 
     def raw_reset(self):

@@ -37,9 +37,11 @@
 #include "lz4_decode.cuh"
 #include "raw.cuh"
 #include "raw_merge.cuh"
+#include "raw_pending_plan.h"
 #include "raw_range.cuh"
 #include "raw_query.cuh"
 #include "raw_select.cuh"
+#include "raw_bounds.cuh"  // (behind raw_select.cuh, which it builds on)
 #include "rollup_plan.h"
 #include "sketch_plan.h"
 #include "table_room.h"
@@ -249,6 +251,7 @@ struct fa_ctx {
     struct RangeState* range = nullptr;  // ranged loads of parts (raw_range_host.inc), nullptr until the first ranged call
     struct SelectState* select = nullptr;  // selecting rows of parts (raw_select_host.inc), nullptr until the first select
     struct QueryState* query = nullptr;  // grouped queries over parts (raw_query_host.inc), nullptr until the first query
+    struct PendingState* pending = nullptr;  // the pending parts as input (raw_pending_host.inc), nullptr until the first such call
 
     fa_stats_t stats{};
     uint64_t used_base = 0;  // groups created before the current counter epoch
@@ -311,6 +314,7 @@ static void load_release(fa_ctx* c);
 static void select_drop(fa_ctx* c);
 static void select_release(fa_ctx* c);
 static void query_release(fa_ctx* c);
+static void pending_release(fa_ctx* c);
 
 extern "C" uint32_t fa_abi_version(void) { return FA_ABI_VERSION; }
 
@@ -590,6 +594,7 @@ extern "C" void fa_destroy(fa_ctx* c) {
     state_destroy(c->range);
     state_destroy(c->select);
     state_destroy(c->query);
+    state_destroy(c->pending);
     const hipStream_t streams[3] = {c->copy_stream, c->cand_stream, c->stream};
     delete c;  // every event and buffer is released here (fa_ctx's members own them): before the streams go, as ever
     for (hipStream_t s : streams)
@@ -633,6 +638,7 @@ static bool bucket_range(const fa_ctx* c, uint32_t timeslot, uint32_t& lo, uint3
 #include "raw_range_host.inc"
 #include "raw_select_host.inc"
 #include "raw_query_host.inc"
+#include "raw_pending_host.inc"
 
 extern "C" int fa_stats(fa_ctx* c, fa_stats_t* out) {
     FA_ON_DEVICE(c);

@@ -364,6 +364,7 @@ extern "C" int fa_raw_reset(fa_ctx* c) {
     raw_merge_release(c);
     lz4_release(c);
     load_release(c);
+    pending_release(c);
     return FA_OK;
 }
 

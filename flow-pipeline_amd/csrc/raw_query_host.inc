@@ -58,13 +58,8 @@ static int query_state(fa_ctx* c, QueryState** out, bool tables) {
     return FA_OK;
 }
 
-extern "C" int fa_raw_query(fa_ctx* c, const uint8_t* bytes, size_t n, const fa_raw_query_t* query) {
-    LOAD_ENTER(c);
-    if (!query || (!bytes && n)) return fail(c, FA_ERR_ARG, "fa_raw_query: null argument");
-    LoadState* s = nullptr;
-    int rc = load_state(c, &s);  // (the ctx's selection is dropped here, as under any range call)
-    if (rc) return rc;
-    const fa_raw_query_t qa = *query;
+// what a query door refuses in its query (the reason in fa_last_error)
+static int query_check(fa_ctx* c, const char* fn, const fa_raw_query_t& qa) {
     const fa_raw_filter& f = qa.where;
     const char* why = raw_select_filter_why(f);
     if (!why && f.limit) why = "where.limit is not 0 (a query has no limit: read the first k rows)";
@@ -75,29 +70,33 @@ extern "C" int fa_raw_query(fa_ctx* c, const uint8_t* bytes, size_t n, const fa_
     const bool keep = qa.flags & FA_RAW_Q_KEEP;
     if (!why && keep && c->query && c->query->groups && c->query->groups != qa.groups) why = "KEEP with groups other than those of the result held";
     if (why) {
-        c->err = std::string("fa_raw_query: ") + why;
+        c->err = std::string(fn) + ": " + why;
         return FA_ERR_ARG;
     }
-    RangeState* g = nullptr;
-    rc = range_state(c, &g);
+    return FA_OK;
+}
+// the state and its tables; without KEEP the result held ends here, when the call starts
+static int query_start(fa_ctx* c, QueryState** out, const fa_raw_query_t& qa) {
+    int rc = query_state(c, out, true);
     if (rc) return rc;
-    QueryState* q = nullptr;
-    rc = query_state(c, &q, true);
-    if (rc) return rc;
-    QueryTabs& t = *q->tabs;
-    if (!keep) {  // the result held ends when the call starts
-        q->groups = 0;
-        rc = tab_reset(c, t);
+    if (!(qa.flags & FA_RAW_Q_KEEP)) {
+        (*out)->groups = 0;
+        rc = tab_reset(c, *(*out)->tabs);
         if (rc) return rc;
     }
-    RangeRun run;
-    rc = range_run(c, s, g, "fa_raw_query", bytes, n, f.t_lo, f.t_hi, true, (size_t)-1, nullptr, run);
-    if (rc) return rc;
-    // (from here on every byte the fold kernel reads is decoded and validated)
+    return FA_OK;
+}
+
+// The fold over the slices of a run, whatever door the run came from (fa_raw_query: a ranged load's; fa_raw_query_pending of
+// raw_pending_host.inc: the ctx's pending parts): every byte the fold kernel reads is in run.image and is a flows_raw part's.
+static int query_over(fa_ctx* c, QueryState* q, const char* fn, const RangeRun& run, const fa_raw_query_t& qa) {
+    const fa_raw_filter& f = qa.where;
+    QueryTabs& t = *q->tabs;
+    int rc = FA_OK;
     const SelectSlices slices(run);
     const size_t ns = slices.sl.size();
     const uint64_t scanned = slices.scanned;
-    if (slices.ntiles > 0x7FFFFFFFull) return fail(c, FA_ERR_ARG, "fa_raw_query: more than 2^39 rows in the time range of one call; query the file in pieces with KEEP");
+    if (slices.ntiles > 0x7FFFFFFFull) return fail(c, FA_ERR_ARG, std::string(fn) + ": more than 2^39 rows in the time range of one call; query the file in pieces with KEEP");
     const uint32_t ntiles = (uint32_t)slices.ntiles, kinds = (uint32_t)__builtin_popcount(qa.groups);
     if (ns) {
         rc = ensure_dev(c, q->plan, ns * sizeof(RawSelectPart), "query plan");
@@ -135,6 +134,28 @@ extern "C" int fa_raw_query(fa_ctx* c, const uint8_t* bytes, size_t n, const fa_
     q->st.updates += (matched - q->matched_seen) * kinds, q->matched_seen = matched;
     q->st.calls++, q->st.rows_scanned += scanned;
     return FA_OK;
+}
+
+extern "C" int fa_raw_query(fa_ctx* c, const uint8_t* bytes, size_t n, const fa_raw_query_t* query) {
+    LOAD_ENTER(c);
+    if (!query || (!bytes && n)) return fail(c, FA_ERR_ARG, "fa_raw_query: null argument");
+    LoadState* s = nullptr;
+    int rc = load_state(c, &s);  // (the ctx's selection is dropped here, as under any range call)
+    if (rc) return rc;
+    const fa_raw_query_t qa = *query;
+    rc = query_check(c, "fa_raw_query", qa);
+    if (rc) return rc;
+    RangeState* g = nullptr;
+    rc = range_state(c, &g);
+    if (rc) return rc;
+    QueryState* q = nullptr;
+    rc = query_start(c, &q, qa);
+    if (rc) return rc;
+    RangeRun run;
+    rc = range_run(c, s, g, "fa_raw_query", bytes, n, qa.where.t_lo, qa.where.t_hi, true, (size_t)-1, nullptr, run);
+    if (rc) return rc;
+    // (from here on every byte the fold kernel reads is decoded and validated)
+    return query_over(c, q, "fa_raw_query", run, qa);
 }
 
 // the rows of one kind, ordered and cut, in q->top; *n_out = the rows there are to deliver (all of them when cap is too small)

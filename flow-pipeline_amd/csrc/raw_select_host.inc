@@ -54,30 +54,11 @@ struct SelectSlices {
     }
 };
 
-extern "C" int fa_raw_select(fa_ctx* c, const uint8_t* bytes, size_t n, const fa_raw_filter* filter, fa_raw_part* parts, size_t parts_cap, size_t* n_parts, size_t* bytes_out) {
-    LOAD_ENTER(c);
-    if (!filter || !n_parts || !bytes_out || (!parts && parts_cap) || (!bytes && n)) return fail(c, FA_ERR_ARG, "fa_raw_select: null argument");
-    *n_parts = 0, *bytes_out = 0;
-    LoadState* s = nullptr;
-    int rc = load_state(c, &s);  // (the previous selection is dropped here)
-    if (rc) return rc;
-    const fa_raw_filter f = *filter;
-    if (const char* why = raw_select_filter_why(f)) {
-        c->err = std::string("fa_raw_select: ") + why;
-        return FA_ERR_ARG;
-    }
-    RangeState* g = nullptr;
-    rc = range_state(c, &g);
-    if (rc) return rc;
-    rc = state_with_events(c, c->select, 6);
-    if (rc) return rc;
-    SelectState* q = c->select;
-    RangeRun run;
-    size_t np_in = 0;
-    rc = range_run(c, s, g, "fa_raw_select", bytes, n, f.t_lo, f.t_hi, true, parts_cap, &np_in, run);
-    if (rc == FA_ERR_CAPACITY) *n_parts = np_in;
-    if (rc) return rc;
-    // (from here on every byte the select, emit and gather kernels read is decoded and validated)
+// The select, emit and gather steps over the slices of a run, whatever door the run came from (fa_raw_select: a ranged load's;
+// fa_raw_select_pending of raw_pending_host.inc: the ctx's pending parts): every byte the kernels read is in run.image and is a
+// flows_raw part's.  parts has room for one description per part of the run.
+static int select_over(fa_ctx* c, SelectState* q, const char* fn, const RangeRun& run, const fa_raw_filter& f, fa_raw_part* parts, size_t* n_parts, size_t* bytes_out) {
+    int rc = FA_OK;
     const SelectSlices slices(run);
     const std::vector<const RangePart*>& sl = slices.sl;
     const uint64_t scanned = slices.scanned, src_rows = slices.src_rows;
@@ -89,7 +70,7 @@ extern "C" int fa_raw_select(fa_ctx* c, const uint8_t* bytes, size_t n, const fa
         return FA_OK;
     }
     if (src_rows > (uint64_t)INT32_MAX)
-        return fail(c, FA_ERR_ARG, "fa_raw_select: " + std::to_string(src_rows) + " rows in the parts that hold a row of the time range are more than one gather indexes (2^31 - 1); select the file in pieces");
+        return fail(c, FA_ERR_ARG, std::string(fn) + ": " + std::to_string(src_rows) + " rows in the parts that hold a row of the time range are more than one gather indexes (2^31 - 1); select the file in pieces");
     const uint32_t ntiles = (uint32_t)slices.ntiles;
 
     // ---- buffers: the device's work area and its pinned mirror share one layout
@@ -195,6 +176,32 @@ extern "C" int fa_raw_select(fa_ctx* c, const uint8_t* bytes, size_t n, const fa
     if (!count_only) q->sel_bytes = sel_bytes;
     st.calls++, st.rows_scanned += scanned, st.rows_matched += matched, st.rows_out += total, st.parts_out += out.size(), st.bytes_out += sel_bytes;
     return FA_OK;
+}
+
+extern "C" int fa_raw_select(fa_ctx* c, const uint8_t* bytes, size_t n, const fa_raw_filter* filter, fa_raw_part* parts, size_t parts_cap, size_t* n_parts, size_t* bytes_out) {
+    LOAD_ENTER(c);
+    if (!filter || !n_parts || !bytes_out || (!parts && parts_cap) || (!bytes && n)) return fail(c, FA_ERR_ARG, "fa_raw_select: null argument");
+    *n_parts = 0, *bytes_out = 0;
+    LoadState* s = nullptr;
+    int rc = load_state(c, &s);  // (the previous selection is dropped here)
+    if (rc) return rc;
+    const fa_raw_filter f = *filter;
+    if (const char* why = raw_select_filter_why(f)) {
+        c->err = std::string("fa_raw_select: ") + why;
+        return FA_ERR_ARG;
+    }
+    RangeState* g = nullptr;
+    rc = range_state(c, &g);
+    if (rc) return rc;
+    rc = state_with_events(c, c->select, 6);
+    if (rc) return rc;
+    RangeRun run;
+    size_t np_in = 0;
+    rc = range_run(c, s, g, "fa_raw_select", bytes, n, f.t_lo, f.t_hi, true, parts_cap, &np_in, run);
+    if (rc == FA_ERR_CAPACITY) *n_parts = np_in;
+    if (rc) return rc;
+    // (from here on every byte the select, emit and gather kernels read is decoded and validated)
+    return select_over(c, c->select, "fa_raw_select", run, f, parts, n_parts, bytes_out);
 }
 
 extern "C" int fa_raw_selection_device(fa_ctx* c, const void** d_bytes, size_t* bytes_out) {

@@ -919,7 +919,7 @@ int fa_raw_range_stats(fa_ctx*, fa_raw_range_stats_t* out);
  * Memory, kept until fa_raw_load_reset / fa_raw_reset / fa_destroy: that of the ranged load, 10 bytes per 64 rows of the time
  * range, 8 bytes per selected row, 68 bytes per part with a row of the time range (and as many page-locked), hipcub's storage for
  * one scan, the selection.
- * NOT built: selecting from a live ctx's pending parts, a projection of columns, a group or dist door, a consumer flag, decoding
+ * (A live ctx's pending parts as input: fa_raw_select_pending, below.)  NOT built: a projection of columns, a group or dist door, a consumer flag, decoding
  * the predicate's columns first and only the blocks of matching rows afterwards, OR-lists of values, pruning by TimeFlowStart. */
 #define FA_RAW_F_FLOW_START 1u
 #define FA_RAW_F_SRC_AS 2u
@@ -996,7 +996,8 @@ int fa_raw_select_stats(fa_ctx*, fa_raw_select_stats_t* out);
  * time range (and as many page-locked), two tables of 64-byte slots that start at 2^16 slots and grow until the rows x kinds of
  * a fold launch (at most 2^20 keys) fit at half load - 2^21 slots each for a million rows scanned, whatever matches -, 40 bytes per
  * group of the kind being read, the order's keys.
- * NOT built: decoding only the columns a query names; pending parts of a live ctx and columns already in HBM; sum(Packets),
+ * (Pending parts of a live ctx as input: fa_raw_query_pending, below.)  NOT built: decoding only the columns a query names;
+ * columns already in HBM as input; sum(Packets),
  * compound keys such as (SrcAS, DstAS), OR-lists; a group or dist door (rows with k = 0 are mergeable by sum: a merge call can
  * follow); a consumer flag. */
 #define FA_RAW_G_SRC_ADDR 1u   /* the talker panels' key: fa_talker_row's canonical (key, etype), talkers.cuh's rule */
@@ -1033,6 +1034,63 @@ int fa_raw_query_rows_device(fa_ctx*, uint32_t group, int order, size_t k, const
 int fa_raw_query_reset(fa_ctx*);
 /* The counters of this ctx's queries; works on any ctx (all zero before the first call). */
 int fa_raw_query_stats(fa_ctx*, fa_raw_query_stats_t* out);
+
+/* ---- ABI 8, addition: the pending flows_raw parts as input ------------------------------ */
+/* "Top talkers of the last five minutes": the rows a dashboard asks about most are usually still PENDING in the ingesting ctx - built
+ * by fa_raw_enable's second pass, not yet taken - and they lie in HBM in the very layout fa_raw_select's and fa_raw_query's kernels
+ * read.  These doors answer from where the rows lie.  All of them need fa_raw_enable (FA_ERR_ARG otherwise).
+ * Input: the ctx's pending parts, in build order (what fa_raw_take would deliver now; after fa_raw_merge: one part per Date).
+ * NOTHING IS COPIED, DECODED, TAKEN OR CHANGED: after any of these calls the pending parts are byte for byte what they were, and a
+ * later fa_raw_take, fa_raw_take_lz4 or fa_raw_merge behaves as if the call had not happened.  Nothing is validated either: the
+ * library built every byte itself, sorted.
+ * The time range is on TimeReceived with the rule of the ranged loads: t_lo <= t32 < t_hi; t_hi == 0xFFFFFFFF means "to the end"
+ * and includes that second; t_lo > t_hi is FA_ERR_ARG; t_lo == t_hi selects nothing.
+ * How the range is found (csrc/raw_pending_plan.h, csrc/raw_bounds.cuh): the host holds every pending part's t_min / t_max
+ * (fa_raw_part).  From them alone a part is SKIPPED (no row can be in range), WHOLE (every row is) or SEARCHED.  Only for searched
+ * parts one kernel runs - raw_bounds_kernel, one wave per part, a 64-ary search of the sorted TimeReceived column: at most
+ * ceil(log65(rows)) + 1 loads per lane and bound, against the full pass over the column that untrusted input needs - with one small
+ * plan copy, one small copy back and one wait.  A range that covers everything pending, or nothing, launches no such kernel and has
+ * no such wait.
+ *   fa_raw_pending_probe   fa_raw_range_probe's twin: one fa_raw_range per pending part, build order.  date and rows are always
+ *            filled; [r_lo, r_hi) are the rows in range, t_min / t_max those of the rows in range and 0 when there are none; for a
+ *            part without a row in range only r_lo == r_hi is promised.  cap below the pending part count: FA_ERR_CAPACITY, *n_out =
+ *            the parts there are, nothing launched.
+ *   fa_raw_query_pending   fa_raw_query's contract, validation and refusals (the filter's, no limit, no COUNT_ONLY, groups, flags,
+ *            the KEEP rule) over the pending rows.  The result lands in the same place and is read by fa_raw_query_rows /
+ *            _rows_device, dropped by fa_raw_query_reset, counted in fa_raw_query_stats.  KEEP therefore COMPOSES STORED AND LIVE
+ *            DATA: fa_raw_query(bytes of the older files) followed by fa_raw_query_pending(KEEP) is one answer over both.  It reads
+ *            and writes no other aggregate, and unlike fa_raw_query it uses no load buffer: THE CTX'S SELECTION STAYS.
+ *   fa_raw_select_pending  fa_raw_select's contract: one plain Native part per pending part with a match, rows in input order,
+ *            `limit` counted over the call, COUNT_ONLY.  parts_cap below the pending part count is FA_ERR_CAPACITY with *n_parts =
+ *            the parts there are, before any launch; more than 2^31 - 1 rows in the parts that hold a row of the time range is
+ *            FA_ERR_ARG as in fa_raw_select.  The selection REPLACES the ctx's selection under fa_raw_select's lifetime rule (dropped
+ *            when the call starts; a refused call leaves none) and is read by fa_raw_selection_device / _fetch.  It is a copy: it
+ *            survives later ingests, merges and takes.
+ * No pending parts: FA_OK; a query without KEEP still clears the result held and sets `groups`; a select gives 0 parts.  A pending
+ * part of more than 2^32 - 1 rows is FA_ERR_ARG before any launch.
+ * Ordering: the pending parts are built on the ctx's stream and these doors launch on it; they are synchronous and end in the waits
+ * fa_raw_query / fa_raw_select end in.  A pointer from fa_raw_take_device dies at these calls as at any raw call.
+ * Counted in fa_raw_query_stats / fa_raw_select_stats exactly as the file doors count, and in fa_raw_pending_stats; NEVER in
+ * fa_raw_load_stats or fa_raw_range_stats: nothing is loaded.
+ * Memory, kept until fa_raw_reset / fa_destroy: 48 bytes per searched part (and as many page-locked), plus what the select or the
+ * query keeps.
+ * Additive: a ctx that never calls these functions runs the code it ran.  NOT built: columns already in HBM (fa_columns) as input,
+ * a group or dist door, a consumer flag, a projection of columns. */
+typedef struct {
+    uint64_t calls;                        /* probe, query and select calls whose input stood (pending_run succeeded) */
+    uint64_t parts_seen;                   /* pending parts of those calls = parts_skipped + parts_whole + parts_searched */
+    uint64_t parts_skipped;                /* the host's t_min / t_max say no row can be in range */
+    uint64_t parts_whole;                  /* ... that every row is in range */
+    uint64_t parts_searched;               /* neither: raw_bounds_kernel found the two positions */
+    uint64_t rows_seen, rows_in_range;     /* rows of every pending part; of them in the time range */
+    uint64_t bounds_launches, bounds_ns;   /* raw_bounds_kernel launches (at most one per call) and their hipEvent time */
+} fa_raw_pending_stats_t;
+/* Synchronous. */
+int fa_raw_pending_probe(fa_ctx*, uint32_t t_lo, uint32_t t_hi, fa_raw_range* out, size_t cap, size_t* n_out);
+int fa_raw_query_pending(fa_ctx*, const fa_raw_query_t* query);
+int fa_raw_select_pending(fa_ctx*, const fa_raw_filter* filter, fa_raw_part* parts, size_t parts_cap, size_t* n_parts, size_t* bytes_out);
+/* The counters of this ctx's calls over its pending parts (all zero before the first). */
+int fa_raw_pending_stats(fa_ctx*, fa_raw_pending_stats_t* out);
 
 /* ---- address rendering of the dashboards (host code, no ctx) ------------------ */
 /* The string the top-talker panels group by and display (viz-ch.json:233,479; README.md:186-221):
