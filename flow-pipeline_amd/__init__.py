@@ -213,6 +213,14 @@ class RawQueryStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RawQueryMergeStats(C.Structure):
+    """fa_raw_query_merge_stats_t: the raw_query_merge calls that added their rows, and the rows."""
+    _fields_ = [("merge_calls", C.c_uint64), ("rows_merged", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 RAW_G_SRC_ADDR, RAW_G_DST_ADDR, RAW_G_SRC_PORT, RAW_G_DST_PORT, RAW_G_MINUTE, RAW_G_SRC_AS, RAW_G_DST_AS, RAW_G_PROTO, RAW_G_TOTAL = (1 << i for i in range(9))
 RAW_G_ALL = 511
 RAW_Q_KEEP = 1
@@ -299,7 +307,7 @@ PORT_BLOCK, PORT_LDS_ENTRIES, PORT_WG_PER_CU = 512, 512, 2
 assert ROW5M_DTYPE.itemsize == 48 and FLOW_ROW_DTYPE.itemsize == 120
 assert ROW_APP_DTYPE.itemsize == 56 and PORT_ROW_DTYPE.itemsize == 24 and MINUTE_ROW_DTYPE.itemsize == 24
 ROW_DTYPES = [ROW5M_DTYPE, ROW_APP_DTYPE, PORT_ROW_DTYPE, PORT_ROW_DTYPE, MINUTE_ROW_DTYPE, TOPK_DTYPE, TOPK_DTYPE,
-              None, TALKER_ROW_DTYPE, TALKER_ROW_DTYPE]  # by row kind (7 is none)
+              None, TALKER_ROW_DTYPE, TALKER_ROW_DTYPE, None, None, QUERY_ROW_DTYPE, QUERY_ROW_DTYPE]  # by row kind (7, 10 and 11 are none)
 
 # every symbol include/flowagg.h declares (checked by the CPU test-suite)
 EXPORTS = [
@@ -331,12 +339,15 @@ EXPORTS = [
     "fa_raw_select", "fa_raw_selection_device", "fa_raw_selection_fetch", "fa_raw_select_stats",
     "fa_raw_query", "fa_raw_query_rows", "fa_raw_query_rows_device", "fa_raw_query_reset", "fa_raw_query_stats",
     "fa_raw_pending_probe", "fa_raw_query_pending", "fa_raw_select_pending", "fa_raw_pending_stats",
+    "fa_raw_query_merge_device", "fa_raw_query_merge_rows", "fa_raw_query_merge_stats",
+    "fa_group_raw_query_pending", "fa_group_raw_query_rows", "fa_group_raw_query_reset",
 ]
 GROUP_PEER, GROUP_RCCL = 0, 1
 TOPK_EXACT, TOPK_CANDIDATES = 0, 1
 # row kinds of the device-resident window close (include/flowagg.h, ABI 5)
 ROWS_5M, ROWS_APP, ROWS_PORT_SRC, ROWS_PORT_DST, ROWS_MINUTE, ROWS_TOPK_SRC, ROWS_TOPK_DST = range(7)
 ROWS_TALKERS_SRC, ROWS_TALKERS_DST = 8, 9  # (ABI 8, addition; 7 is unassigned)
+ROWS_QUERY_WEIGHT, ROWS_QUERY_KEY = 12, 13  # query rows in raw_query_rows' two orders (ABI 8, addition; 10 and 11 are unassigned)
 
 _LIB = None
 
@@ -555,6 +566,12 @@ def lib():
     L.fa_raw_query_stats.argtypes = [vp, C.POINTER(RawQueryStats)]
     L.fa_raw_pending_probe.argtypes = [vp, u32, u32, vp, sz, szp]
     L.fa_raw_query_pending.argtypes = [vp, C.POINTER(RawQuery)]
+    L.fa_raw_query_merge_device.argtypes = [vp, C.c_uint32, vp, sz]
+    L.fa_raw_query_merge_rows.argtypes = [vp, C.c_uint32, vp, sz]
+    L.fa_raw_query_merge_stats.argtypes = [vp, C.POINTER(RawQueryMergeStats)]
+    L.fa_group_raw_query_pending.argtypes = [vp, C.POINTER(RawQuery)]
+    L.fa_group_raw_query_rows.argtypes = [vp, C.c_uint32, C.c_int, sz, vp, sz, szp]
+    L.fa_group_raw_query_reset.argtypes = [vp]
     L.fa_raw_select_pending.argtypes = [vp, C.POINTER(RawFilter), vp, sz, szp, szp]
     L.fa_raw_pending_stats.argtypes = [vp, C.POINTER(RawPendingStats)]
     L.fa_raw_merge.argtypes = [vp]
@@ -1295,6 +1312,22 @@ class FlowAgg:
         self._chk(self._L.fa_raw_query_stats(self._h, C.byref(s)))
         return s.as_dict()
 
+    def raw_query_merge(self, group, rows_or_device_ptr, n=None):
+        """Adds rows of ONE kind to the result this ctx holds: another ctx's raw_query_rows(group, k=0) (a QUERY_ROW_DTYPE array),
+        or its raw_query_rows_device pointer with n rows.  Every row is checked before any is added; afterwards raw_query_rows
+        answers for both, and a later query with keep goes on adding."""
+        if isinstance(rows_or_device_ptr, np.ndarray):
+            rows = np.ascontiguousarray(rows_or_device_ptr, dtype=QUERY_ROW_DTYPE)
+            m = len(rows) if n is None else int(n)
+            self._chk(self._L.fa_raw_query_merge_rows(self._h, group, rows.ctypes.data if m else None, m))
+        else:
+            self._chk(self._L.fa_raw_query_merge_device(self._h, group, int(rows_or_device_ptr) or None, int(n or 0)))
+
+    def raw_query_merge_stats(self) -> dict:
+        s = RawQueryMergeStats()
+        self._chk(self._L.fa_raw_query_merge_stats(self._h, C.byref(s)))
+        return s.as_dict()
+
     # -- the pending parts as input (include/flowagg.h "the pending flows_raw parts as input") ----
     def raw_pending_probe(self, t_lo: int, t_hi: int) -> np.ndarray:
         """raw_range_probe over the ctx's pending parts, read where they lie in HBM: one RAW_RANGE_DTYPE entry per pending part,
@@ -1502,6 +1535,24 @@ class FlowGroup:
         cap = cap if cap is not None else (max(int(k), 1) if k else 1 << 12)
         lo, hi = _talker_range(t_lo, t_hi)
         return self._rows(lambda out, c, n: self._L.fa_group_top_ports_range(self._h, dst, lo, hi, int(k), out.ctypes.data, c, C.byref(n)), kind, cap)
+
+    def raw_query_pending(self, groups, t_lo=0, t_hi=0xFFFFFFFF, *, keep=False, filter=None, **conditions):
+        """FlowAgg.raw_query_pending on every member (each needs raw_enable); keep is passed through per member.  Read the answer
+        over the whole topic with raw_query_rows."""
+        q = RawQuery()
+        q.where = filter if filter is not None else raw_filter(t_lo, t_hi, **conditions)
+        q.groups, q.flags = groups, RAW_Q_KEEP if keep else 0
+        self._chk(self._L.fa_group_raw_query_pending(self._h, C.byref(q)))
+
+    def raw_query_rows(self, group, k=0, order=RAW_O_WEIGHT, cap=None) -> np.ndarray:
+        """FlowAgg.raw_query_rows of ONE ctx whose result covers what every member holds, byte for byte: exact, merged in HBM, k
+        rows cross PCIe.  The members' results are not changed."""
+        cap = cap if cap is not None else (max(int(k), 1) if k else 1 << 12)
+        return _rows_with_room(lambda out, c, n: self._L.fa_group_raw_query_rows(self._h, group, order, int(k), out.ctypes.data, c, C.byref(n)), self._chk, QUERY_ROW_DTYPE, cap,
+                               np.zeros)
+
+    def raw_query_reset(self):
+        self._chk(self._L.fa_group_raw_query_reset(self._h))
 
     def stats(self) -> dict:
         s = Stats()

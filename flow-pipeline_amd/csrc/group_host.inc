@@ -722,6 +722,66 @@ extern "C" int fa_group_top_ports_range(fa_group* g, int dst, uint32_t t_lo, uin
     return group_rows_merged(g, dst ? RK_PORT_DST : RK_PORT_SRC, 0, 0, k, out, cap, n_out, nullptr, all_rows);
 }
 
+// ---- grouped queries over the whole topic ---------------------------------------------------------------------------------------
+// The members stay the caller's: fa_group_raw_query_pending runs fa_raw_query_pending on every member (KEEP passed through, so a
+// caller adds stored files member by member with fa_raw_query first), and fa_group_raw_query_rows merges WHAT THE MEMBERS HOLD - it
+// reads their results (fa_raw_query_rows_device, k = 0) and changes none.  An exact first k cannot be built from the members' first
+// k, so the address kinds go the top talkers' two stages (group_shares with the merge cut at k, group_gather_merge with the same
+// cut: the argument above group_top_talkers, with the total order of fa_raw_query_rows) and the scalar kinds - small sets - are
+// gathered whole on one root (fa_group_top_ports_range's way).  Rows of ONE kind meet in a call: the row kinds' duty.
+static uint32_t query_groups_held(const fa_ctx* c);  // raw_query_host.inc
+static int group_query_refuse(fa_group* g, size_t i, int code, const char* what, const std::string& why) {
+    const int rc = gfail_member(g, i, fail(g->m[i], code, why.c_str()), what);
+    g->m[i]->err = "group: " + g->err;
+    return rc;
+}
+extern "C" int fa_group_raw_query_pending(fa_group* g, const fa_raw_query_t* q) {
+    if (!g) return FA_ERR_ARG;
+    if (!q) return gfail(g, FA_ERR_ARG, "fa_group_raw_query_pending: null argument");
+    int rc = group_sticky(g);
+    if (rc) return rc;
+    for (size_t i = 0; i < g->m.size(); i++)  // (before any member runs)
+        if (!g->m[i]->raw) return group_query_refuse(g, i, FA_ERR_UNSUPPORTED, "query of the pending parts", "flows_raw parts are not enabled on this ctx (fa_raw_enable)");
+    const fa_raw_query_t qa = *q;
+    return group_each(g, "query of the pending parts", [&](size_t i) { return fa_raw_query_pending(g->m[i], &qa); });
+}
+extern "C" int fa_group_raw_query_reset(fa_group* g) {
+    if (!g) return FA_ERR_ARG;
+    return group_each(g, "query reset", [&](size_t i) { return fa_raw_query_reset(g->m[i]); });
+}
+extern "C" int fa_group_raw_query_rows(fa_group* g, uint32_t group, int order, size_t k, fa_query_row* out, size_t cap, size_t* n_out) {
+    int rc = group_args(g, out, cap, n_out);
+    if (rc) return rc;
+    *n_out = 0;
+    if (!group || (group & (group - 1)) || (group & ~FA_RAW_G_ALL)) return gfail(g, FA_ERR_ARG, "fa_group_raw_query_rows: group is exactly one FA_RAW_G_* bit");
+    if (order != FA_RAW_O_WEIGHT && order != FA_RAW_O_KEY) return gfail(g, FA_ERR_ARG, "fa_group_raw_query_rows: order is FA_RAW_O_WEIGHT or FA_RAW_O_KEY");
+    const size_t n = g->m.size();
+    for (size_t i = 0; i < n; i++) {  // (before anything is collected or exchanged)
+        const uint32_t held = query_groups_held(g->m[i]);
+        if (!held) return group_query_refuse(g, i, FA_ERR_ARG, "query rows", "the ctx holds no query result");
+        if (!(held & group)) return group_query_refuse(g, i, FA_ERR_ARG, "query rows", "group is not among the groups of the result the ctx holds");
+    }
+    const int kind = order == FA_RAW_O_WEIGHT ? RK_QUERY_WEIGHT : RK_QUERY_KEY;
+    const bool addr = group & (FA_RAW_G_SRC_ADDR | FA_RAW_G_DST_ADDR);
+    StepClock clk;
+    if (clk.on) clk.head = "query rows (group bit " + std::to_string(group) + ", order " + std::to_string(order) + "), " + std::to_string(n) + " members, k " + std::to_string(k) + ",";
+    const GroupRowsSource all_rows = [=](size_t i, const void** d, size_t* m) { return fa_raw_query_rows_device(g->m[i], group, order, 0, d, m); };
+    const GroupRowsSource first_k = [=](size_t i, const void** d, size_t* m) { return fa_raw_query_rows_device(g->m[i], group, order, k, d, m); };
+    std::vector<const void*> res(n, nullptr);
+    std::vector<size_t> cnt(n, 0);
+    RootRows top;
+    if (n == 1 || !addr) {  // a group of one: its member's first k rows are the result; a scalar kind: every member's whole set on one root
+        const GroupRowsSource& src = n == 1 ? first_k : all_rows;
+        rc = group_each(g, "rows", [&](size_t i) { return src(i, &res[i], &cnt[i]); });
+        clk.mark("rows");
+    } else {
+        rc = group_shares(g, kind, 0, k, clk, res, cnt, all_rows);
+    }
+    if (!rc) rc = group_gather_merge(g, kind, res, cnt, k, &clk, top);
+    if (rc || !top.m) return rc;
+    return group_emit(g, kind, top, out, cap, n_out, &clk);
+}
+
 // ---- what a consumer asks before a flush, and at exit ----------------------------------------------------------------------
 extern "C" int fa_group_open_timeslots(fa_group* g, uint32_t* out, size_t cap, size_t* n_out) {
     int rc = group_args(g, out, cap, n_out);

@@ -17,8 +17,8 @@
 
 namespace fa {
 
-// (7 is no kind: the numbers are not dense - "is this a kind" is with_row_kind / row_bytes_of in rows_host.inc)
-enum { RK_5M = 0, RK_APP = 1, RK_PORT_SRC = 2, RK_PORT_DST = 3, RK_MINUTE = 4, RK_TOPK_SRC = 5, RK_TOPK_DST = 6, RK_TALKERS_SRC = 8, RK_TALKERS_DST = 9 };
+// (7, 10 and 11 are no kinds: the numbers are not dense - "is this a kind" is with_row_kind / row_bytes_of in rows_host.inc)
+enum { RK_5M = 0, RK_APP = 1, RK_PORT_SRC = 2, RK_PORT_DST = 3, RK_MINUTE = 4, RK_TOPK_SRC = 5, RK_TOPK_DST = 6, RK_TALKERS_SRC = 8, RK_TALKERS_DST = 9, RK_QUERY_WEIGHT = 12, RK_QUERY_KEY = 13 };
 
 struct RowApp {  // == fa_row_app
     uint32_t date, timeslot;
@@ -187,6 +187,43 @@ template <>
 struct RowOps<RK_TALKERS_SRC> : RowOpsTalk {};
 template <>
 struct RowOps<RK_TALKERS_DST> : RowOpsTalk {};
+
+// query rows (raw_query.cuh; fa_query_row = a talker row whose pad is `value`): one row per (value, 16 key bytes, etype) - the
+// talkers' three words with `value` above them as the most significant -, weight and count summed mod 2^64, and `value` KEPT.
+// Rows of one GROUP BY only are meant to meet in a call (the caller's duty: a SrcPort 80 and a DstPort 80 are one identity here).
+// The emit order is fa_raw_query_rows': FA_RAW_O_KEY = the merge order (value, key bytes, etype), FA_RAW_O_WEIGHT = weight DESC
+// above it.  Five emit words are more than a RowPlan packs, and the packed emit sort is the one that misordered a million talker
+// rows: the groups are ordered by the talkers' full-width passes instead - the very passes fa_raw_query_rows runs -
+// with a scalar's value standing in key bytes 4..7 for their duration (query_rows_key_kernel; rows_host.inc, rows_merge_t).
+// Rows are producible (query_row_producible: fa_rows_merge_device refuses anything else before it merges).
+struct RowOpsQuery {
+    typedef TalkRow Row;
+    static constexpr int NK = 4, NK2 = 0;
+    __host__ __device__ static unsigned long long key(const Row& r, int w, uint32_t) {
+        return w == 0 ? (unsigned long long)r.etype : w == 1 ? bytes_order(r.key[1]) : w == 2 ? bytes_order(r.key[0]) : (unsigned long long)r.pad;
+    }
+    __host__ __device__ static int bits(int w) { return w == 0 ? 12 : w == 3 ? 32 : 64; }
+    __device__ static unsigned long long key2(const Row&, int) { return 0; }
+    __device__ static bool same(const Row& a, const Row& b, uint32_t) { return a.key[0] == b.key[0] && a.key[1] == b.key[1] && a.etype == b.etype && a.pad == b.pad; }
+    __device__ static void add(Row& a, const Row& b) {
+        a.weight += b.weight;
+        a.count += b.count;
+    }
+    __device__ static void add_atomic(Row& a, const Row& b) {
+        atomicAdd(&a.weight, b.weight);
+        atomicAdd(&a.count, b.count);
+    }
+    __device__ static void finish(Row&, uint32_t) {}  // (pad is the value: it stays)
+};
+template <>
+struct RowOps<RK_QUERY_WEIGHT> : RowOpsQuery {};
+template <>
+struct RowOps<RK_QUERY_KEY> : RowOpsQuery {};
+// a row some query can produce: a canonical address row with value 0, or a scalar row (key and etype 0) with any value
+__host__ __device__ __forceinline__ bool query_row_producible(const TalkRow& r) {
+    const bool canon = r.etype == 0u || (r.etype == TALK_FAMILY_V4 && (r.key[0] >> 32) == 0ull && r.key[1] == 0ull);
+    return canon && (r.pad == 0u || (r.key[0] == 0ull && r.key[1] == 0ull && r.etype == 0u));
+}
 
 // ---- sort keys: only the bits that differ ----------------------------------------------------------------------------
 // A row kind's order is up to four 64-bit words (224 bits for (SrcAddr,DstPort,Proto) rows) - but inside ONE row set most of
@@ -401,6 +438,20 @@ __global__ void talker_rows_check_kernel(const TalkRow* rows, uint64_t n, unsign
         const bool ok = r.etype == 0u || (r.etype == TALK_FAMILY_V4 && (r.key[0] >> 32) == 0ull && r.key[1] == 0ull);
         if (!ok) atomicAdd(bad, 1u);
     }
+}
+
+// query rows from elsewhere (fa_rows_merge_device, the query kinds): a row no query produces would become a group of its own
+__global__ void query_rows_check_kernel(const TalkRow* rows, uint64_t n, unsigned int* bad) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        if (!query_row_producible(rows[i])) atomicAdd(bad, 1u);
+}
+// The emit order of merged query rows, in place around the talkers' passes: TO_KEY puts a scalar's value into key bytes 4..7, most
+// significant byte first (the passes then order it numerically, as raw_query.cuh's tables hold it), !TO_KEY clears them again.  An
+// address row (value 0) is left alone; the value 0 of a scalar is the zero key either way.
+template <bool TO_KEY>
+__global__ __launch_bounds__(256) void query_rows_key_kernel(TalkRow* rows, uint32_t n) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        if (rows[i].pad) rows[i].key[0] = TO_KEY ? bytes_order((unsigned long long)rows[i].pad) : 0ull;
 }
 
 // fa_read_window_app48: the rows of ONE window share date and timeslot - they leave without them (a seventh of the bytes of the

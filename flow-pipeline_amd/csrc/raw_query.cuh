@@ -182,4 +182,46 @@ __global__ __launch_bounds__(256) void raw_query_scalar_rows_kernel(TalkRow* row
     }
 }
 
+// ---- adding another ctx's rows to the result held (fa_raw_query_merge_device; the contract: include/flowagg.h) --------------------
+// A row of `kind` as a query of that kind produces it (run on the host by tests/host_raw_query_merge.hip against a naive
+// restatement): an address kind's canonical key with value 0; a scalar kind's value with a zero key and etype 0, MINUTE on the
+// minute grid, TOTAL 0.
+__host__ __device__ __forceinline__ bool raw_query_row_ok(uint32_t kind, const TalkRow& r) {
+    if (raw_query_kind_is_addr(kind)) return r.pad == 0u && (r.etype == 0u || (r.etype == TALK_FAMILY_V4 && (r.key[0] >> 32) == 0ull && r.key[1] == 0ull));
+    if (r.key[0] != 0ull || r.key[1] != 0ull || r.etype != 0u) return false;
+    return kind == RAW_Q_K_MINUTE ? r.pad % 60u == 0u : kind == RAW_Q_K_TOTAL ? r.pad == 0u : true;
+}
+// the key of a row in the tables: the fold's own key text over the row's two little-endian key words and etype, or its value
+__host__ __device__ __forceinline__ void raw_query_row_key(uint32_t kind, const TalkRow& r, TKey& k) {
+    if (raw_query_kind_is_addr(kind)) raw_query_key_addr(kind, r.key[0], r.key[1], r.etype, k);
+    else raw_query_key_scalar(kind, r.pad, k);
+}
+// The status word of a merge: the rows that are no rows of `kind`.  The adds are launched only after it was read as 0.
+__global__ __launch_bounds__(256) void raw_query_rows_check_kernel(const TalkRow* rows, uint64_t n, uint32_t kind, unsigned int* bad) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        if (!raw_query_row_ok(kind, rows[i])) atomicAdd(bad, 1u);
+}
+// raw_query_merge_kernel: one lane per row, n rows of ONE kind (at most the tables' chunk: the host reserved n keys in table
+// kind & 1 - the fold's capacity rule), each added through tab_upsert into the table the fold kernel feeds for that kind.  No LDS
+// cache: a member's rows hold every key once, so a cache would absorb nothing and every entry would be flushed by one more upsert;
+// the keys of different members meet in the global table, where the atomics are memory-side either way.  The row is one 40-byte
+// read per lane (rows back to back: a wave reads 2560 contiguous bytes); the cost is the random 64-byte slot per row.
+struct RawQueryMergeArgs {
+    const TalkRow* rows;
+    uint32_t n, kind;
+    TSlot* tab;
+    uint32_t mask;
+    TalkCounters* ctr;
+};
+__global__ __launch_bounds__(256) void raw_query_merge_kernel(const RawQueryMergeArgs a) {
+    uint32_t created[1] = {0};
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {  // (n <= 2^28, the grid <= 2^20 threads: no wrap)
+        const TalkRow r = a.rows[i];
+        TKey k;
+        raw_query_row_key(a.kind, r, k);
+        tab_upsert<QueryTab>(a.tab, a.mask, k, tkey_hash(k), r.weight, r.count, a.ctr, created);
+    }
+    tab_count_created<QueryTab>(a.ctr, (int)(a.kind & 1u), created);  // (every lane of every wave gets here)
+}
+
 }  // namespace fa

@@ -10,6 +10,8 @@
 // A read: the kind's occupied slots collected by talker_rows_kernel<true> over the range [kind, kind] of table kind & 1, ordered by
 // the talkers' stable radix passes (talk_order_passes: four for FA_RAW_O_WEIGHT, three for FA_RAW_O_KEY), cut at k on the
 // device; a scalar kind's rows get their value back (raw_query_scalar_rows_kernel); only the rows returned are copied out.
+// Another ctx's rows of one kind are added to the result held by fa_raw_query_merge_device / _rows: one check launch and one status
+// word, then raw_query_merge_kernel in launches of at most the tables' chunk under the fold's room rule.
 // The result lies in the tables until the next query without KEEP, fa_raw_query_reset, fa_raw_load_reset, fa_raw_reset or
 // fa_destroy.  Nothing of the ctx's other state is read or written: the tables, the counters and the cursor are the query's own.
 
@@ -28,6 +30,8 @@ struct QueryState {
     fa_raw_query_stats_t st{};  // calls, rows_scanned, updates, launches (reads), order_ns; the rest comes from the tables
     uint64_t matched0 = 0, absorbed0 = 0, grows0 = 0, launches0 = 0, fold_ns0 = 0;  // ... of tables that were released
     uint64_t matched_seen = 0;  // rows matched up to the last call's end (a call's updates = its matched rows x its kinds)
+    fa_raw_query_merge_stats_t mst{};  // fa_raw_query_merge_device / _rows: calls that merged, rows they added
+    uint64_t merge_launches = 0;       // their check launches (the add launches are counted by the tables, as folds)
 };
 
 // the tables' counts into the state (before the tables go)
@@ -57,6 +61,15 @@ static int query_state(fa_ctx* c, QueryState** out, bool tables) {
     *out = c->query;
     return FA_OK;
 }
+// rows_host.inc's merge of the query row kinds orders its groups in the state's scratch (no tables: any ctx, nothing enabled)
+static int query_order_scratch(fa_ctx* c, DevBuf<>** order) {
+    QueryState* q = nullptr;
+    const int rc = query_state(c, &q, false);
+    if (!rc) *order = &q->order;
+    return rc;
+}
+// the groups of the result a ctx holds (0: none) - what the group door checks in every member before it collects
+static uint32_t query_groups_held(const fa_ctx* c) { return c->query && c->query->tabs ? c->query->groups : 0u; }
 
 // what a query door refuses in its query (the reason in fa_last_error)
 static int query_check(fa_ctx* c, const char* fn, const fa_raw_query_t& qa) {
@@ -240,6 +253,71 @@ extern "C" int fa_raw_query_reset(fa_ctx* c) {
     return q->tabs ? tab_reset(c, *q->tabs) : FA_OK;
 }
 
+// ---- another ctx's rows into the result held ----------------------------------------------------------------------------------------
+// n rows of ONE kind in HBM: every row is checked (raw_query_rows_check_kernel, one status word, one wait) before the first is added;
+// then launches of at most the tables' chunk, room for that many keys reserved in table kind & 1 before each (the fold's rule).
+extern "C" int fa_raw_query_merge_device(fa_ctx* c, uint32_t group, const void* d_rows, size_t n) {
+    LOAD_ENTER(c);
+    static const char fn[] = "fa_raw_query_merge_device";
+    if (!d_rows && n) return fail(c, FA_ERR_ARG, std::string(fn) + ": null argument");
+    QueryState* q = c->query;
+    if (!q || !q->tabs || !q->groups) return fail(c, FA_ERR_ARG, std::string(fn) + ": the ctx holds no query result (start one with any query, such as fa_raw_query_pending over an empty range)");
+    if (!group || (group & (group - 1)) || !(q->groups & group)) return fail(c, FA_ERR_ARG, std::string(fn) + ": group is exactly one bit of the groups of the result held");
+    if ((uintptr_t)d_rows & 7) return fail(c, FA_ERR_ARG, std::string(fn) + ": the rows are 8-byte aligned");
+    if (n >= (1ull << 31)) return fail(c, FA_ERR_ARG, std::string(fn) + ": too many rows for one call (2^31)");
+    if (!n) return FA_OK;
+    QueryTabs& t = *q->tabs;
+    if (inside(q->rows, d_rows) || inside(q->top, d_rows)) return fail(c, FA_ERR_ARG, std::string(fn) + ": the rows are this ctx's own result (a result is not merged into itself)");
+    const uint32_t kind = (uint32_t)__builtin_ctz(group);
+    const int d = (int)(kind & 1u);
+    HIPCHK(c, zero_word(t.cursor.get(), c->stream));
+    hipLaunchKernelGGL(raw_query_rows_check_kernel, grid_n(n), dim3(256), 0, c->stream, (const TalkRow*)d_rows, (uint64_t)n, kind, t.cursor.get());
+    HIPCHK(c, hipGetLastError());
+    q->merge_launches++;
+    unsigned int bad = 0;
+    HIPCHK(c, read_word(t.cursor.get(), bad, c->stream));
+    if (bad)
+        return fail(c, FA_ERR_ARG, std::string(fn) + ": a row is no row of this kind (address kinds: canonical key, value 0; scalar kinds: zero key and etype; MINUTE: value % 60 == 0; TOTAL: value 0); nothing was added");
+    const size_t chunk = std::max<size_t>(1, t.chunk);
+    for (size_t i = 0; i < n;) {
+        const size_t m = std::min(n - i, chunk);
+        int rc = tab_reserve(c, t, d, m);
+        if (rc) return rc;
+        RawQueryMergeArgs a{(const TalkRow*)d_rows + i, (uint32_t)m, kind, t.tab[d].get(), t.mask(d), t.d_ctr.get()};
+        // (timed and counted with the fold launches: fa_raw_query_stats' launches and fold_ns)
+        rc = tab_fold_launch(c, t, m, [&](dim3 grid) { hipLaunchKernelGGL(raw_query_merge_kernel, grid, dim3(QueryTab::BLOCK), 0, c->stream, a); });
+        if (rc) return rc;
+        t.used_ub[d] += m;
+        i += m;
+    }
+    TalkCounters h;
+    int rc = tab_settle(c, t, h);  // (the caller's rows are not referenced after the call)
+    if (rc) return rc;
+    q->mst.merge_calls++, q->mst.rows_merged += n;
+    return FA_OK;
+}
+extern "C" int fa_raw_query_merge_rows(fa_ctx* c, uint32_t group, const fa_query_row* rows, size_t n) {
+    LOAD_ENTER(c);
+    if (!rows && n) return fail(c, FA_ERR_ARG, "fa_raw_query_merge_rows: null argument");
+    if (!n) return fa_raw_query_merge_device(c, group, nullptr, 0);  // (the refusals of the state and the group bit)
+    DevBuf<TalkRow> d;
+    if (!d.grow(n * sizeof(TalkRow))) {
+        (void)hipGetLastError();
+        return fail(c, FA_ERR_NOMEM, "fa_raw_query_merge_rows: hipMalloc failed; nothing was added");
+    }
+    HIPCHK(c, hipMemcpyAsync(d.get(), rows, n * sizeof(TalkRow), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (the caller's rows are not referenced after the call)
+    return fa_raw_query_merge_device(c, group, d.get(), n);
+}
+extern "C" int fa_raw_query_merge_stats(fa_ctx* c, fa_raw_query_merge_stats_t* out) {
+    FA_ON_DEVICE(c);
+    if (!c) return FA_ERR_ARG;
+    if (!out) return fail(c, FA_ERR_ARG, "fa_raw_query_merge_stats: null argument");
+    memset(out, 0, sizeof *out);
+    if (c->query) *out = c->query->mst;
+    return FA_OK;
+}
+
 extern "C" int fa_raw_query_stats(fa_ctx* c, fa_raw_query_stats_t* out) {
     FA_ON_DEVICE(c);
     if (!c) return FA_ERR_ARG;
@@ -249,7 +327,7 @@ extern "C" int fa_raw_query_stats(fa_ctx* c, fa_raw_query_stats_t* out) {
     if (!q) return FA_OK;
     *out = q->st;
     out->rows_matched = q->matched0, out->absorbed = q->absorbed0, out->grows = q->grows0, out->fold_ns = q->fold_ns0;
-    out->launches += q->launches0;
+    out->launches += q->launches0 + q->merge_launches;
     if (q->tabs) {
         if (c->sticky) return c->sticky;
         TalkCounters h;

@@ -6,7 +6,8 @@
 // close exchanges device buffers over RCCL and merges them without a host sort (flow-pipeline_amd/dist.py).
 
 // The RowOps<K> a row kind runs - THE statement of that mapping: both port kinds share one instantiation, both top-k kinds
-// another, both talker kinds a third.  f(std::integral_constant<int, K>{}); false for a kind that is none (7 is none).
+// another, both talker kinds a third; the two query kinds differ in their emit passes.  f(std::integral_constant<int, K>{}); false for a
+// kind that is none (7, 10 and 11 are none).
 template <class F>
 static bool with_row_kind(int kind, F&& f) {
     switch (kind) {
@@ -16,6 +17,8 @@ static bool with_row_kind(int kind, F&& f) {
     case RK_MINUTE: f(std::integral_constant<int, RK_MINUTE>{}); return true;
     case RK_TOPK_SRC: case RK_TOPK_DST: f(std::integral_constant<int, RK_TOPK_SRC>{}); return true;
     case RK_TALKERS_SRC: case RK_TALKERS_DST: f(std::integral_constant<int, RK_TALKERS_SRC>{}); return true;
+    case RK_QUERY_WEIGHT: f(std::integral_constant<int, RK_QUERY_WEIGHT>{}); return true;
+    case RK_QUERY_KEY: f(std::integral_constant<int, RK_QUERY_KEY>{}); return true;
     default: return false;
     }
 }
@@ -30,11 +33,19 @@ static_assert(sizeof(RowOps<RK_PORT_SRC>::Row) == sizeof(RowW) && sizeof(RowOps<
 static_assert(sizeof(RowOps<RK_TOPK_SRC>::Row) == sizeof(TopkRow) && sizeof(TopkRow) == 24, "row layout");
 static_assert(sizeof(RowOps<RK_TALKERS_SRC>::Row) == sizeof(TalkRow) && sizeof(TalkRow) == sizeof(fa_talker_row) && sizeof(TalkRow) == 40, "row layout");
 static_assert(RowOps<RK_TALKERS_SRC>::NK2 <= RP_MAX_WORDS, "emit words");
+static_assert(sizeof(RowOps<RK_QUERY_WEIGHT>::Row) == sizeof(fa_query_row) && sizeof(RowOps<RK_QUERY_KEY>::Row) == sizeof(fa_query_row) && sizeof(fa_query_row) == 40, "row layout");
+static_assert(RK_QUERY_WEIGHT == FA_ROWS_QUERY_WEIGHT && RK_QUERY_KEY == FA_ROWS_QUERY_KEY, "row kinds");
 // The talker kinds' emit order, and fa_top_talkers': the first `need` of n rows (device memory) by four full-width sorts, in the
 // talker state's scratch (talkers_host.inc).  The packed emit sort below returned rows out of order on sets of a million talker
 // rows (DESIGN.md 3.7); these four sorts never did.
 static int talk_order_rows(fa_ctx* c, hipStream_t stream, const TalkRow* rows, uint32_t n, size_t need, TalkRow* out);
 static int talk_order_passes(fa_ctx* c, hipStream_t stream, DevBuf<>& order, const TalkRow* rows, uint32_t n, size_t need, TalkRow* out, int passes);
+// The query kinds' emit order runs the same passes in the query state's scratch (raw_query_host.inc): the state comes into being
+// without tables on a ctx that never queried.
+static bool is_query_kind(int kind) { return kind == RK_QUERY_WEIGHT || kind == RK_QUERY_KEY; }
+static int query_order_scratch(fa_ctx* c, DevBuf<>** order);
+static const char QUERY_NOT_PRODUCIBLE[] =
+    "fa_rows_merge_device: a query row no query produces (etype 0 or 0x800; bytes 4..15 zero under 0x800; value != 0 only with a zero key and etype 0)";
 extern "C" size_t fa_row_bytes(int kind) { return row_bytes_of(kind); }
 
 static int ensure_dev(fa_ctx* c, DevBuf<>& b, size_t bytes, const char* what) {
@@ -384,7 +395,8 @@ static int rows_merge_t(fa_ctx* c, hipStream_t stream, ReadClock& clk, const voi
     const bool may_be_long = n > m && (uint64_t)n >= (uint64_t)RUN_SERIAL;  // (a run of RUN_SERIAL rows needs at least that many rows)
     // a kind without an emit order is done with the reduce: straight into the pinned host buffer when no run can be long (the
     // atomics of row_tail_kernel want device memory)
-    Row* red = (Ops::NK2 == 0 && host && m_emit == m && !may_be_long) ? (Row*)c->h_rows : (Row*)c->m_out[0];
+    constexpr bool QUERY = KIND == RK_QUERY_WEIGHT || KIND == RK_QUERY_KEY;  // (NK2 == 0, yet ordered behind the reduce)
+    Row* red = (Ops::NK2 == 0 && !QUERY && host && m_emit == m && !may_be_long) ? (Row*)c->h_rows : (Row*)c->m_out[0];
     rc = reduce_into(red);
     if (rc) return rc;
     if (may_be_long) {
@@ -399,6 +411,18 @@ static int rows_merge_t(fa_ctx* c, hipStream_t stream, ReadClock& clk, const voi
         dst = host ? (Row*)c->h_rows : (Row*)c->m_out[1];
         rc = talk_order_rows(c, stream, (const Row*)red, m, m_emit, dst);
         if (rc) return rc;
+        clk.mark("emit order", stream);
+    } else if constexpr (KIND == RK_QUERY_WEIGHT || KIND == RK_QUERY_KEY) {  // fa_raw_query_rows' order by fa_raw_query_rows' passes (merge.cuh, RowOpsQuery)
+        DevBuf<>* order = nullptr;
+        rc = query_order_scratch(c, &order);
+        if (!rc) rc = ensure_dev(c, c->m_out[1], m_emit * sizeof(Row), "ordered rows");
+        if (rc) return rc;
+        dst = (Row*)c->m_out[1];  // (never the pinned buffer: a kernel rewrites the rows behind the order)
+        hipLaunchKernelGGL(query_rows_key_kernel<true>, grid_n(m), b, 0, stream, red, m);
+        rc = talk_order_passes(c, stream, *order, (const Row*)red, m, m_emit, dst, KIND == RK_QUERY_WEIGHT ? 4 : 3);
+        if (rc) return rc;
+        hipLaunchKernelGGL(query_rows_key_kernel<false>, grid_n(m_emit), b, 0, stream, dst, (uint32_t)m_emit);
+        HIPCHK(c, hipGetLastError());
         clk.mark("emit order", stream);
     } else if constexpr (Ops::NK2 > 0) {  // emit order: a second sort over the groups
         uint32_t* cur2 = nullptr;
@@ -448,6 +472,8 @@ static int kind_enabled(fa_ctx* c, int kind) {
     case RK_TOPK_SRC: return c->ks_src ? FA_OK : fail(c, FA_ERR_ARG, "fa_topk: key set not enabled");
     case RK_TOPK_DST: return c->ks_dst ? FA_OK : fail(c, FA_ERR_ARG, "fa_topk: key set not enabled");
     case RK_TALKERS_SRC: case RK_TALKERS_DST: return c->talk ? FA_OK : fail(c, FA_ERR_UNSUPPORTED, TALK_OFF);
+    case RK_QUERY_WEIGHT: case RK_QUERY_KEY:
+        return fail(c, FA_ERR_UNSUPPORTED, "fa_rows_device: query rows come from fa_raw_query_rows_device (a row kind names no GROUP BY: the call has no place for the group bit)");
     default: return fail(c, FA_ERR_ARG, "unknown row kind");
     }
 }
@@ -463,6 +489,8 @@ static const char* row_kind_name(int kind) {
     case RK_TOPK_DST: return "top-k DstAddr";
     case RK_TALKERS_SRC: return "talkers SrcAddr";
     case RK_TALKERS_DST: return "talkers DstAddr";
+    case RK_QUERY_WEIGHT: return "query rows by weight";
+    case RK_QUERY_KEY: return "query rows by key";
     default: return "unknown";
     }
 }
@@ -995,6 +1023,15 @@ static int talker_rows_canonical(fa_ctx* c, const void* d_rows, size_t n) {
     HIPCHK(c, read_word(&c->d_ctr->rows_count, bad, c->stream));
     return bad ? fail(c, FA_ERR_ARG, TALK_NOT_CANONICAL) : FA_OK;
 }
+// query rows from elsewhere, likewise
+static int query_rows_producible(fa_ctx* c, const void* d_rows, size_t n) {
+    if (!n) return FA_OK;
+    HIPCHK(c, zero_word(&c->d_ctr->rows_count, c->stream));
+    hipLaunchKernelGGL(query_rows_check_kernel, grid_n(n), dim3(256), 0, c->stream, (const TalkRow*)d_rows, (uint64_t)n, &c->d_ctr->rows_count);
+    unsigned int bad = 0;
+    HIPCHK(c, read_word(&c->d_ctr->rows_count, bad, c->stream));
+    return bad ? fail(c, FA_ERR_ARG, QUERY_NOT_PRODUCIBLE) : FA_OK;
+}
 
 extern "C" int fa_rows_merge_device(fa_ctx* c, int kind, const void* d_rows, size_t n, size_t k, const void** d_out, size_t* n_out) {
     FA_ON_DEVICE(c);
@@ -1012,6 +1049,10 @@ extern "C" int fa_rows_merge_device(fa_ctx* c, int kind, const void* d_rows, siz
         if (rc) return rc;
         if (talk_rows_hold(c, d_rows)) return fail(c, FA_ERR_ARG, "rows to merge alias the ctx's result buffer (copy them first)");
         rc = talker_rows_canonical(c, d_rows, n);
+        if (rc) return rc;
+    }
+    if (is_query_kind(kind)) {
+        rc = query_rows_producible(c, d_rows, n);
         if (rc) return rc;
     }
     ReadClock clk(c, false);

@@ -38,6 +38,7 @@ ROW_APP_DTYPE = np.dtype([
 PORT_ROW_DTYPE = np.dtype([("port", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
 MINUTE_ROW_DTYPE = np.dtype([("minute", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
 TALKER_ROW_DTYPE = np.dtype([("key", "u1", 16), ("etype", "<u4"), ("_pad", "<u4"), ("weight", "<u8"), ("count", "<u8")])
+QUERY_ROW_DTYPE = np.dtype([("key", "u1", 16), ("etype", "<u4"), ("value", "<u4"), ("weight", "<u8"), ("count", "<u8")])
 
 
 def partitions_of(rank: int, world: int, n_partitions: int):
@@ -117,6 +118,17 @@ def merge_talkers_host(parts) -> np.ndarray:
     return rows
 
 
+def merge_query_host(parts, order=0) -> np.ndarray:
+    """Partial query row sets of ONE kind (raw_query_rows with k = 0 of several contexts) -> one row per (value, key, etype),
+    weight and count summed mod 2^64, value kept, in raw_query_rows' order: RAW_O_WEIGHT (0) weight DESC, then value, key bytes,
+    etype; RAW_O_KEY (1) value, key bytes, etype (merge.cuh RowOpsQuery restated)."""
+    if order not in (0, 1):
+        raise ValueError("order is RAW_O_WEIGHT (0) or RAW_O_KEY (1)")
+    by_key = lambda r: (r["etype"],) + _be64_halves(r["key"])[::-1] + (r["value"],)  # noqa: E731
+    emit = None if order == 1 else (lambda r: by_key(r) + (_heaviest_first(r),))
+    return _merge_host(parts, QUERY_ROW_DTYPE, by_key, ("value", "key", "etype"), ("weight", "count"), emit)
+
+
 def allgather_struct(rows: np.ndarray, dtype, group=None, device=None):
     """All ranks receive every rank's rows of `dtype` (list indexed by rank)."""
     rows = np.ascontiguousarray(rows, dtype=dtype)
@@ -163,7 +175,8 @@ def _mix64(z: np.ndarray) -> np.ndarray:
 
 def _key_words(rows: np.ndarray, kind: int):
     """The merge-order key words of a row kind, least significant first (merge.cuh, RowOps<KIND>::key)."""
-    from . import ROWS_5M, ROWS_APP, ROWS_MINUTE, ROWS_PORT_DST, ROWS_PORT_SRC, ROWS_TALKERS_DST, ROWS_TALKERS_SRC, ROWS_TOPK_DST, ROWS_TOPK_SRC
+    from . import (ROWS_5M, ROWS_APP, ROWS_MINUTE, ROWS_PORT_DST, ROWS_PORT_SRC, ROWS_QUERY_KEY, ROWS_QUERY_WEIGHT, ROWS_TALKERS_DST, ROWS_TALKERS_SRC, ROWS_TOPK_DST,
+                   ROWS_TOPK_SRC)
     u64 = np.uint64
     if kind == ROWS_5M:
         return [(rows["dst_as"].astype(u64) << u64(32)) | rows["etype"].astype(u64),
@@ -179,6 +192,8 @@ def _key_words(rows: np.ndarray, kind: int):
     words = [lo.astype(u64), hi.astype(u64)]
     if kind in (ROWS_TALKERS_SRC, ROWS_TALKERS_DST):
         return [rows["etype"].astype(u64)] + words
+    if kind in (ROWS_QUERY_WEIGHT, ROWS_QUERY_KEY):
+        return [rows["etype"].astype(u64)] + words + [rows["value"].astype(u64)]
     if kind in (ROWS_TOPK_SRC, ROWS_TOPK_DST):
         return words
     raise ValueError("unknown row kind %r" % (kind,))
@@ -436,6 +451,24 @@ def top_talkers_merged(agg, dst, k=0, group=None, t_lo=None, t_hi=None) -> np.nd
     ranged = None if t_lo is None and t_hi is None else (lambda: agg.talkers_range_rows_device(dst, t_lo, t_hi))
     sptr, m = close.merge(*close.exchange_by_owner(ALL_TIMESLOTS, ranged), k)  # this rank's share, cut at k
     return close.merge_and_fetch(*close.gather(sptr, m), k, "the merge of the shares' rows")
+
+
+def raw_query_merged(agg, group_bit, k=0, order=0, group=None) -> np.ndarray:
+    """One kind of the query results the ranks' contexts hold, merged across ranks: identical on every rank and equal, byte for
+    byte, to FlowAgg.raw_query_rows(group_bit, k, order) of one ctx whose result covers every rank's rows.  The ranks' results
+    are not changed.  The local rows are raw_query_rows_device(group_bit, k = 0, order): a rank's first k say nothing about the
+    global first k.  Address kinds travel as the top talkers do - exchange by owner, merge cut at k, all-gather of the shares'
+    k rows, merge cut at k; scalar kinds (small sets) are gathered whole and merged once.  order: RAW_O_WEIGHT (0) / RAW_O_KEY (1)."""
+    from . import ALL_TIMESLOTS, RAW_G_DST_ADDR, RAW_G_SRC_ADDR, RAW_O_KEY, RAW_O_WEIGHT, ROWS_QUERY_KEY, ROWS_QUERY_WEIGHT
+    if order not in (RAW_O_WEIGHT, RAW_O_KEY):
+        raise ValueError("order is RAW_O_WEIGHT or RAW_O_KEY")
+    close = _Close(agg, ROWS_QUERY_WEIGHT if order == RAW_O_WEIGHT else ROWS_QUERY_KEY, group)
+    rows = lambda: agg.raw_query_rows_device(group_bit, 0, order)  # noqa: E731
+    if group_bit & (RAW_G_SRC_ADDR | RAW_G_DST_ADDR):
+        sptr, m = close.merge(*close.exchange_by_owner(ALL_TIMESLOTS, rows), k)  # this rank's share, cut at k
+        return close.merge_and_fetch(*close.gather(sptr, m), k, "the merge of the shares' query rows")
+    ptr, n = close.local(rows, (0, -1))
+    return close.merge_and_fetch(*close.gather(ptr, n), k, "the merge of the gathered query rows")
 
 
 def allgather_rows(rows: np.ndarray, group=None, device=None):

@@ -295,11 +295,20 @@ int fa_merge_rows_device(fa_ctx*, const void* d_rows, size_t n);
  *   FA_ROWS_MINUTE    fa_minute_row ORDER BY minute                                         (fa_minute_series; viz-ch.json:74)
  *   FA_ROWS_TOPK_SRC / _DST  fa_topk_row   ORDER BY weight DESC, key bytes                  (fa_topk; viz-ch.json:233,479)
  *   FA_ROWS_TALKERS_SRC / _DST  fa_talker_row  ORDER BY weight DESC, key bytes, etype       (fa_top_talkers; ABI 8, addition)
- * Kind 7 is unassigned and stays unknown to every call.  The talker kinds need fa_talkers_enable on the ctx that is
+ *   FA_ROWS_QUERY_WEIGHT  fa_query_row  ORDER BY weight DESC, value, key bytes, etype          (fa_raw_query_rows, FA_RAW_O_WEIGHT; ABI 8, addition)
+ *   FA_ROWS_QUERY_KEY     fa_query_row  ORDER BY value, key bytes, etype                       (fa_raw_query_rows, FA_RAW_O_KEY; ABI 8, addition)
+ * Kinds 7, 10 and 11 are unassigned and stay unknown to every call.  The talker kinds need fa_talkers_enable on the ctx that is
  * called (FA_ERR_UNSUPPORTED otherwise, from fa_rows_device / _merge_device / _partition_device / _fetch alike); they are
  * not windowed - timeslot is ignored - and fa_rows_merge_device refuses rows that are not canonical (fa_merge_talkers' rule:
  * FA_ERR_ARG, nothing merged, the outputs untouched).  An exact top k over partitions needs every partition's WHOLE table
  * (fa_rows_device with k = 0), hash-partitioned: fa_group_top_talkers / dist.top_talkers_merged.
+ * The query kinds carry the rows of fa_raw_query_rows[_device] through fa_rows_merge_device / _partition_device / _fetch ON ANY
+ * CTX, nothing enabled.  The identity of a row is (value, key bytes, etype); weight and count are summed mod 2^64, value is kept;
+ * the partition hashes that identity.  A row carries no GROUP BY: ROWS OF DIFFERENT FA_RAW_G_* KINDS ARE NEVER MIXED IN ONE CALL -
+ * the caller's duty (SrcPort 80 and DstPort 80 would be summed).  fa_rows_merge_device refuses a row no query produces - etype
+ * outside {0, 0x800}; etype 0x800 with a non-zero byte 4..15; value != 0 together with a non-zero key or etype - with FA_ERR_ARG,
+ * nothing merged, the outputs untouched.  fa_rows_device answers FA_ERR_UNSUPPORTED for them: it has no place for the group bit;
+ * the rows come from fa_raw_query_rows_device(group, order, 0).  The topic-wide read: fa_group_raw_query_rows / dist.raw_query_merged.
  * Multi-GPU window close (one ctx per GPU / Kafka partition, inserter.go:176): every rank calls fa_rows_device,
  * the ranks all-gather the device buffers over RCCL (counts first, no padding), every rank calls
  * fa_rows_merge_device on the concatenation - sum is a commutative monoid, so the result equals the single-ctx
@@ -308,7 +317,9 @@ enum {
     FA_ROWS_5M = 0, FA_ROWS_APP = 1, FA_ROWS_PORT_SRC = 2, FA_ROWS_PORT_DST = 3, FA_ROWS_MINUTE = 4,
     FA_ROWS_TOPK_SRC = 5, FA_ROWS_TOPK_DST = 6,
     /* 7: unassigned */
-    FA_ROWS_TALKERS_SRC = 8, FA_ROWS_TALKERS_DST = 9
+    FA_ROWS_TALKERS_SRC = 8, FA_ROWS_TALKERS_DST = 9,
+    /* 10, 11: unassigned (callers and tests rely on fa_row_bytes(10) == 0) */
+    FA_ROWS_QUERY_WEIGHT = 12, FA_ROWS_QUERY_KEY = 13
 };
 size_t fa_row_bytes(int kind); /* bytes of one row of the kind; 0 for an unknown kind */
 /* This ctx's result for (kind, timeslot) exactly as the matching read call would return it - the sub-buckets of a
@@ -851,7 +862,7 @@ int fa_sketch_fold_stats(fa_ctx*, fa_sketch_fold_stats_t* out);
  * statistics, as a refused call of the whole-file doors does.
  * Memory: that of fa_raw_restore (a slot per block of the input, decoded or not) plus 152 bytes per part.
  * Additive: a ctx that never calls these functions runs the code it ran.  NOT built: copying only the needed compressed bytes
- * (the whole input is copied), a compact image (undecoded slots are allocated), a group or dist door, a consumer flag, a range
+ * (the whole input is copied), a compact image (undecoded slots are allocated), a consumer flag, a range
  * on TimeFlowStart. */
 typedef struct {
     uint32_t date, t_min, t_max, _pad; /* Date[0] (0 for a part without rows); t_min / t_max of the rows in range, 0 when none */
@@ -919,7 +930,7 @@ int fa_raw_range_stats(fa_ctx*, fa_raw_range_stats_t* out);
  * Memory, kept until fa_raw_load_reset / fa_raw_reset / fa_destroy: that of the ranged load, 10 bytes per 64 rows of the time
  * range, 8 bytes per selected row, 68 bytes per part with a row of the time range (and as many page-locked), hipcub's storage for
  * one scan, the selection.
- * (A live ctx's pending parts as input: fa_raw_select_pending, below.)  NOT built: a projection of columns, a group or dist door, a consumer flag, decoding
+ * (A live ctx's pending parts as input: fa_raw_select_pending, below.)  NOT built: a projection of columns, a consumer flag, decoding
  * the predicate's columns first and only the blocks of matching rows afterwards, OR-lists of values, pruning by TimeFlowStart. */
 #define FA_RAW_F_FLOW_START 1u
 #define FA_RAW_F_SRC_AS 2u
@@ -998,8 +1009,8 @@ int fa_raw_select_stats(fa_ctx*, fa_raw_select_stats_t* out);
  * group of the kind being read, the order's keys.
  * (Pending parts of a live ctx as input: fa_raw_query_pending, below.)  NOT built: decoding only the columns a query names;
  * columns already in HBM as input; sum(Packets),
- * compound keys such as (SrcAS, DstAS), OR-lists; a group or dist door (rows with k = 0 are mergeable by sum: a merge call can
- * follow); a consumer flag. */
+ * compound keys such as (SrcAS, DstAS), OR-lists; a consumer flag.  (The merge call and the topic-wide doors: "queries over the
+ * whole topic", below.) */
 #define FA_RAW_G_SRC_ADDR 1u   /* the talker panels' key: fa_talker_row's canonical (key, etype), talkers.cuh's rule */
 #define FA_RAW_G_DST_ADDR 2u
 #define FA_RAW_G_SRC_PORT 4u   /* the whole UInt32 column value */
@@ -1034,6 +1045,44 @@ int fa_raw_query_rows_device(fa_ctx*, uint32_t group, int order, size_t k, const
 int fa_raw_query_reset(fa_ctx*);
 /* The counters of this ctx's queries; works on any ctx (all zero before the first call). */
 int fa_raw_query_stats(fa_ctx*, fa_raw_query_stats_t* out);
+
+/* ---- ABI 8, addition: queries over the whole topic -------------------------------------- */
+/* One ctx answers for one Kafka partition; a panel asks about the topic.  Three layers, each usable alone:
+ *  1. the row kinds FA_ROWS_QUERY_WEIGHT / _KEY (above): query rows through the exchange steps of the window close;
+ *  2. fa_raw_query_merge_device / _rows: n rows of ONE kind are ADDED to the result this ctx holds.  Only another ctx's
+ *     fa_raw_query_rows[_device](group, any order, k = 0) gives mergeable rows (a cut result lacks groups).  Afterwards
+ *     fa_raw_query_rows of this ctx answers for both, and a later fa_raw_query / fa_raw_query_pending with KEEP goes on adding.
+ *     `group` is exactly one bit of the held result's groups, else FA_ERR_ARG - also when no result is held: start one with any
+ *     query, for instance fa_raw_query_pending over an empty range.  EVERY ROW IS CHECKED BEFORE ANY IS ADDED, a refused call
+ *     changes nothing (FA_ERR_ARG): an address kind needs canonical rows (fa_talker_row's rule) with value 0; a scalar kind a zero
+ *     key and etype 0; MINUTE value % 60 == 0; TOTAL value 0.  The rows are read where they lie (8-byte aligned; not this ctx's own
+ *     result buffers) and not referenced after the call; the host form copies them to HBM first.  raw_query_merge_kernel: one lane
+ *     per row, the fold's own key text, the fold's tables and capacity rule (launches of at most 2^20 rows, that many keys reserved
+ *     before each).  Counted in fa_raw_query_stats' launches and fold_ns (the add launches are timed as folds) and in
+ *     fa_raw_query_merge_stats (fa_raw_query_stats_t has no size argument and cannot grow).
+ *  3. the group doors.  fa_group_raw_query_pending runs fa_raw_query_pending(member, q) on every member, KEEP passed through; a
+ *     member without fa_raw_enable is FA_ERR_UNSUPPORTED before any member runs.  The members stay the caller's: stored files are
+ *     added member by member with fa_raw_query, then this call with KEEP.  fa_group_raw_query_reset: fa_raw_query_reset on every
+ *     member.  fa_group_raw_query_rows MERGES WHAT THE MEMBERS HOLD: before anything is collected or exchanged every member must
+ *     hold a result whose groups contain `group` (FA_ERR_ARG otherwise, as for a `group` that is not one FA_RAW_G_* bit or a bad
+ *     order).  The result equals, BYTE FOR BYTE, fa_raw_query_rows(group, order, k) of ONE ctx whose result covers every member's
+ *     rows.  The members' results are not changed and the call is repeatable.  An exact first k cannot be made of the members'
+ *     first k (a key that is tenth everywhere can lead overall): every member's whole result of the kind travels in HBM - address
+ *     kinds hash-partitioned by owner, merged and cut at k per owner, the n x k rows gathered on one root and merged with the same
+ *     cut (fa_group_top_talkers' two stages); scalar kinds, small sets, gathered whole on one root - and k rows cross PCIe.  A
+ *     group of one returns its member's first k rows.  FA_ERR_CAPACITY puts the rows needed in *n_out.  A refusal names the
+ *     member in fa_group_last_error and in every member's fa_last_error.  FA_VERBOSE prints the steps' times.
+ * NOT built: a consumer flag or query protocol in the host program; one exchange for several kinds at once (a read is one kind);
+ * sum(Packets), compound keys, OR-lists; a projection of columns. */
+typedef struct {
+    uint64_t merge_calls;                  /* fa_raw_query_merge_device / _rows calls that added their rows */
+    uint64_t rows_merged;                  /* rows they added */
+} fa_raw_query_merge_stats_t;
+/* Synchronous. */
+int fa_raw_query_merge_device(fa_ctx*, uint32_t group, const void* d_rows, size_t n);   /* fa_query_row in HBM */
+int fa_raw_query_merge_rows(fa_ctx*, uint32_t group, const fa_query_row* rows, size_t n); /* host rows */
+/* Works on any ctx (all zero before the first merge). */
+int fa_raw_query_merge_stats(fa_ctx*, fa_raw_query_merge_stats_t* out);
 
 /* ---- ABI 8, addition: the pending flows_raw parts as input ------------------------------ */
 /* "Top talkers of the last five minutes": the rows a dashboard asks about most are usually still PENDING in the ingesting ctx - built
@@ -1075,7 +1124,7 @@ int fa_raw_query_stats(fa_ctx*, fa_raw_query_stats_t* out);
  * Memory, kept until fa_raw_reset / fa_destroy: 48 bytes per searched part (and as many page-locked), plus what the select or the
  * query keeps.
  * Additive: a ctx that never calls these functions runs the code it ran.  NOT built: columns already in HBM (fa_columns) as input,
- * a group or dist door, a consumer flag, a projection of columns. */
+ * a consumer flag, a projection of columns.  (The topic-wide query: fa_group_raw_query_pending, below.) */
 typedef struct {
     uint64_t calls;                        /* probe, query and select calls whose input stood (pending_run succeeded) */
     uint64_t parts_seen;                   /* pending parts of those calls = parts_skipped + parts_whole + parts_searched */
@@ -1224,6 +1273,10 @@ int fa_group_top_talkers_range(fa_group*, int dst, uint32_t t_lo, uint32_t t_hi,
  * fa_ports_enable_buckets -> FA_ERR_UNSUPPORTED, members with different bucket_secs -> FA_ERR_ARG: both before anything is
  * exchanged, the member named in the group's and every member's last error. */
 int fa_group_top_ports_range(fa_group*, int dst, uint32_t t_lo, uint32_t t_hi, size_t k, fa_port_row* out, size_t cap, size_t* n_out);
+/* Grouped queries over the whole topic: the contract is under "queries over the whole topic" above. */
+int fa_group_raw_query_pending(fa_group*, const fa_raw_query_t* q);
+int fa_group_raw_query_rows(fa_group*, uint32_t group, int order, size_t k, fa_query_row* out, size_t cap, size_t* n_out);
+int fa_group_raw_query_reset(fa_group*);
 /* fa_stats summed over the members (kernel_ns: the slowest member's last launch). */
 int fa_group_stats(fa_group*, fa_stats_t* out);
 
