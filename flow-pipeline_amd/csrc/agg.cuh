@@ -199,7 +199,6 @@ __global__ __launch_bounds__(AGG_BLOCK) void agg_kernel(KArgs a) {
 // two-word compare, one ds_read2_b64 looks at the home slot and its successor - and the full key is only rebuilt
 // once per group, when the group is added to the device-wide table.  Open addressing without wrap-around: a key
 // lives in one of the AGG_PROBES slots from its home slot on (the table has that many slots of slack at the end).
-constexpr int AGG8_SLOTS = 4096;
 constexpr int AGG8_ALL = AGG8_SLOTS + AGG_PROBES;
 struct Agg8Table {
     unsigned long long key[AGG8_ALL], s1[AGG8_ALL], s2[AGG8_ALL];  // key = 1 << 63 | kh << 32 | lo;  sums as in AggTable

@@ -115,9 +115,7 @@ struct fa_ctx {
     DevBuf<uint4> wseg;
     DevBuf<uint32_t> wseg_counts;   // [nparts][nwg] + 4 words: the time base and bucket range of a log chunk
     static size_t wcounts_cap(const DevBuf<uint32_t>& b) { return b ? b.bytes() / sizeof(uint32_t) - 4 : 0; }  // ... where they start
-    int wide_mode = 0;         // env FA_WIDE: 0 adaptive, 1 "atomic" (every update through memory-side atomics), 2 "scatter" (always the scatter sink),
-                               // 3 "log": scatter, and the launch's tuples stay in their segments (wlog below) instead of being folded at once
-    // ---- wide log (FA_WIDE=log) ----
+    // ---- wide log (FA_WIDE=log, or chosen by the feedback below) ----
     // A (SrcAddr,DstPort,Proto) stream opens a row for nearly every record: folding a launch's tuples into the hash table is
     // two random HBM accesses per record that aggregate nothing - and the window close sorts the rows anyway.  In log mode a
     // launch's segment buffers are simply KEPT (a chunk); reads take the table's rows AND the chunks' tuples through the
@@ -135,12 +133,7 @@ struct fa_ctx {
         bool minb_known = false;
     };
     std::vector<WChunk> wlog, wlog_free;
-    bool wide_probed = false;      // the ctx has seen its first launch (ingest_device_records: a first big launch is probed with its first 2^20 records)
-    bool wide_defer = false;       // adaptive (FA_WIDE unset): log mode from the moment more than half of a million records opened new rows - for
-                                   // the rest of the ctx's life (deferred launches tell nothing about new rows; a stream that stops opening
-                                   // rows folds its chunks through wagg_kernel once more than wlog_max are pending: the scatter sink's cost)
-    uint64_t seen_wfold = 0;       // Counters::wfold_n at the last feedback look
-    size_t wlog_max = 8;
+    size_t wlog_max = 8;           // env FA_WIDE_LOG_CHUNKS
     // Upper bound of the wide table's rows at any moment (wide_rows_bound): what the newest counter snapshot the host has
     // seen counted, plus every row that whatever was queued BEHIND that snapshot could still open - ingest launches
     // (a record opens at most wide_per_record rows, through the scatter sink's fold or the atomic paths) and folds of log
@@ -150,26 +143,16 @@ struct fa_ctx {
     uint32_t wseg_budget = 0;      // env FA_WSEG_BUDGET (tests only): segment buffers the ctx may hold at a time - the next allocation "fails"
     uint32_t late_below = 0;       // time buckets below it belong to flows_5m windows that were closed: records that still arrive for them are counted (stats.records_late)
     uint64_t wlog_recorded = 0, wlog_folded = 0, wlog_replayed = 0, wlog_dropped = 0, wlog_wm_moves = 0, wlog_nomem_folds = 0;  // chunks (fa_stats, FA_VERBOSE)
-    bool wide_scatter = true;  // adaptive: the scatter sink while a good share of the records open new rows (7 atomics each
-                               // on the atomic path); a stream that mostly hits existing rows (one atomic line transaction
-                               // each) is cheaper without the detour through the segments
-    uint64_t seen_wused = 0, seen_ok_w = 0;
     bool cms_atomic = false;  // env FA_CMS=atomic (A/B, tests): every sketch update through memory-side atomics
     bool cms_scatter_ok = false;  // the sketch geometry fits the scatter sink (256 partitions of <= 2^14 counters)
     int sink_mode = 0;  // 0 auto, 1 direct, 2 scatter (env FA_SINK)
     // (what is decided for ONE launch - sink, tuple format, kernel variant, grid - is a LaunchPlan, launch_plan.h: a value that
     // ingest_device_records builds and passes on, never a member here)
-    // tuple format feedback: compact tuples while (almost) every record fits them.  A launch whose misfits (records
-    // that only a wide tuple holds - they took the direct path) exceed 1/16 of its records switches the ctx to wide
-    // tuples for the next 64 launches, then compact is tried again.  Only speed depends on this, never results.
-    int t8_mode = 0;              // env FA_TUPLE: 0 adaptive, 1 always compact ("8"), 2 always wide ("16")
-    uint64_t t8_wide_until = 0;   // batches counter value up to which wide tuples are used
-    uint64_t seen_misfit8 = 0, seen_ok = 0;  // counter values at the last look
-    uint64_t seen_retried = 0, seq_until = 0;  // launches before batch seq_until run the learnt-field-order variant (format_feedback)
-    int seq_mode = 0;                          // FA_SEQ: 1 always, 2 never
-    uint64_t seen_agg_groups = 0, seen_agg_launches = 0;
-    uint32_t agg_passes_forced = 0;  // env FA_AGG_PASSES (tests, A/B)
-    uint32_t agg_passes = 1;      // agg8_kernel passes for the next launch (1, 2, 4, 8): groups per launch / (partitions x passes) <= half the LDS table
+    // What those decisions are made FROM, launch after launch - compact or wide tuples, the learnt-field-order kernel, scatter sink,
+    // atomics or log for (SrcAddr,DstPort,Proto), the passes of agg8_kernel - is this one value (ingest_feedback.h): its knobs are
+    // set in fa_create, settle and poll_snapshots show it the counters (feedback_look), and every condition on it is one of its
+    // named answers.
+    IngestFeedback fb;
     unsigned stage_threads = 8;   // host threads of the staging copy (fa_ingest)
     uint32_t par = 0;             // parity of the next launch (Counters::exotic_count / retry_count copies)
     uint32_t seg_cap_limit = 0;   // env FA_SEG_CAP (tests only): upper bound on tuples per segment
@@ -355,7 +338,7 @@ static KArgs make_args(fa_ctx* c) {
     a.port_hist = c->port_hist;
     a.gran_recip = (1.0 / (double)c->gran) * (1.0 + 1.0 / 1099511627776.0);
     a.par = c->par;
-    a.agg_passes = c->agg_passes_forced ? c->agg_passes_forced : c->agg_passes;
+    a.agg_passes = c->fb.passes();
     a.late_below = c->late_below;
     return a;
 }
@@ -414,18 +397,20 @@ extern "C" int fa_create(const fa_config* cfg_in, fa_ctx** out) {
     if (const char* d = getenv("FA_SEG_CAP")) c->seg_cap_limit = std::max<uint32_t>(40u, (uint32_t)atoi(d) & ~7u);
     if (const char* d = getenv("FA_SINK")) c->sink_mode = !strcmp(d, "direct") ? 1 : !strcmp(d, "scatter") ? 2 : 0;
     if (const char* d = getenv("FA_CMS")) c->cms_atomic = !strcmp(d, "atomic");
-    if (const char* d = getenv("FA_WIDE")) c->wide_mode = !strcmp(d, "atomic") ? 1 : !strcmp(d, "scatter") ? 2 : !strcmp(d, "log") ? 3 : 0;
     if (const char* d = getenv("FA_WIDE_LOG_CHUNKS")) c->wlog_max = (size_t)std::max(0, atoi(d));
     if (const char* d = getenv("FA_WSEG_BUDGET")) c->wseg_budget = (uint32_t)std::max(1, atoi(d));
-    if (const char* d = getenv("FA_AGG_PASSES")) {
-        const int v = atoi(d);
-        c->agg_passes_forced = (v == 1 || v == 2 || v == 4 || v == 8) ? (uint32_t)v : 0u;
-    }
     c->cms_scatter_ok = cms_scatterable(cfg.cms_depth, cfg.cms_width_log2);
     if (const char* d = getenv("FA_STAGE_THREADS")) c->stage_threads = (unsigned)std::min(64, std::max(1, atoi(d)));
     c->stage_threads = std::min(c->stage_threads, std::max(1u, std::thread::hardware_concurrency()));
-    if (const char* d = getenv("FA_TUPLE")) c->t8_mode = !strcmp(d, "8") ? 1 : !strcmp(d, "16") ? 2 : 0;
-    if (const char* d = getenv("FA_SEQ")) c->seq_mode = !strcmp(d, "1") ? 1 : !strcmp(d, "0") ? 2 : 0;  // learnt-field-order kernel: always / never (default: by the counters)
+    {  // the knobs of the ingest feedback (ingest_feedback.h), in the order of FeedbackKnobs; the wide table comes into being further down
+        int wide = 0, tuple = 0, seq = 0, passes = 0;
+        if (const char* d = getenv("FA_WIDE")) wide = !strcmp(d, "atomic") ? 1 : !strcmp(d, "scatter") ? 2 : !strcmp(d, "log") ? 3 : 0;
+        if (const char* d = getenv("FA_TUPLE")) tuple = !strcmp(d, "8") ? 1 : !strcmp(d, "16") ? 2 : 0;
+        if (const char* d = getenv("FA_SEQ")) seq = !strcmp(d, "1") ? 1 : !strcmp(d, "0") ? 2 : 0;  // learnt-field-order kernel: always / never (default: by the counters)
+        if (const char* d = getenv("FA_AGG_PASSES")) passes = atoi(d);
+        if (passes != 1 && passes != 2 && passes != 4 && passes != 8) passes = 0;
+        c->fb.knobs = FeedbackKnobs{wide, tuple, seq, (uint32_t)passes, c->plog2, false, c->wlog_max > 0};
+    }
     auto bail = [&](const char* what, hipError_t e) {
         g_create_error = std::string("fa_create: ") + what + ": " + hipGetErrorString(e);
         fa_destroy(c);
@@ -502,6 +487,7 @@ extern "C" int fa_create(const fa_config* cfg_in, fa_ctx** out) {
         if (!c->wtab.grow(wbytes)) return bail("hipMalloc(wide table)", hipGetLastError());
         if ((e = hipMemsetAsync(c->wtab, 0, wbytes, c->stream)) != hipSuccess) return bail("memset", e);
         if (!c->wspill.grow(sizeof(WSpillEntry) * c->wspill_cap)) return bail("hipMalloc(wide spill)", hipGetLastError());
+        c->fb.knobs.wide_table = true;
         c->stats.wide_capacity = 1ull << c->wcap_log2;
     }
     if (cfg.key_sets & FA_KEYS_PORT_HIST) {
@@ -526,7 +512,7 @@ extern "C" void fa_destroy(fa_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (getenv("FA_VERBOSE") && c->d_ctr && c->h_ctr && hipMemcpy(c->h_ctr, c->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost) == hipSuccess)
         fprintf(stderr, "[flowagg] agg8: %llu groups added in %llu launches, passes now %u; direct %llu, ok %llu, wide rows %llu\n",
-                (unsigned long long)c->h_ctr->agg_groups, (unsigned long long)c->h_ctr->agg_launches, c->agg_passes,
+                (unsigned long long)c->h_ctr->agg_groups, (unsigned long long)c->h_ctr->agg_launches, c->fb.agg_passes,
                 (unsigned long long)c->h_ctr->direct, (unsigned long long)c->h_ctr->ok, (unsigned long long)(c->wused_base + c->h_ctr->wused));
     if (getenv("FA_VERBOSE") && c->wlog_recorded)
         fprintf(stderr, "[flowagg] wide log: %llu chunks recorded, %llu folded by wagg_kernel, %llu by the atomic replay, %llu dropped whole, %zu pending\n",
@@ -659,7 +645,7 @@ extern "C" int fa_stats(fa_ctx* c, fa_stats_t* out) {
     c->stats.wide_log_dropped = c->wlog_dropped;
     c->stats.wide_log_watermark_moves = c->wlog_wm_moves;
     c->stats.wide_log_nomem_folds = c->wlog_nomem_folds;
-    c->stats.wide_log_mode = (c->wide_mode == 3 || (c->wide_mode == 0 && c->wide_defer)) ? 1 : 0;
+    c->stats.wide_log_mode = c->fb.log_mode() ? 1 : 0;
     if (c->cand_state && rc == FA_OK) {
         CandState h[2];
         if (hipMemcpy(h, c->cand_state, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)

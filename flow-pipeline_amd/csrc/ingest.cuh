@@ -642,7 +642,7 @@ struct HotAddrsOpt<false> {
 };
 
 // SEQ: the variant with the learnt-field-order tier (lane_work tier 4) - a kernel of its own, launched while the counters say that
-// most records need the order-free parser (maintain_host.inc, format_feedback): in the common kernel the tier's code cost the
+// most records need the order-free parser (ingest_feedback.h, learnt_order): in the common kernel the tier's code cost the
 // streams that never use it (GoFlow shape: +1.3 % per launch, same box, through the register allocation alone).
 template <uint32_t KEYSETS, bool T8, bool SEQ = false, int CANDM = -1>
 __global__ __launch_bounds__(wtile_block<KEYSETS>(), wt_lean(KEYSETS) ? 6 : 4) void wtile_kernel(KArgs a) {

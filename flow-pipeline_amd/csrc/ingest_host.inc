@@ -424,17 +424,17 @@ static int ingest_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
     // a margin) records go ahead as a launch of their own and the host looks at the counters before the rest follows - a stream that
     // opens a row per record (BASELINE config 5) keeps the rest of that launch in the log instead of folding 16 M rows into the
     // hash table first (one extra launch and one synchronisation in a ctx's life).
-    if (c->wtab && (c->cfg.key_sets & FA_KEYS_ADDR_PORT_PROTO) && c->wide_mode == 0 && !c->wide_defer && !c->wide_probed && n >= (1u << 22)) {
-        c->wide_probed = true;
-        const size_t m = ((size_t)1 << 20) + ((size_t)1 << 17);  // (format_feedback wants 2^20 decoded records; some may be refused)
+    if (c->wtab && (c->cfg.key_sets & FA_KEYS_ADDR_PORT_PROTO) && c->fb.wants_probe() && n >= (1u << 22)) {
+        c->fb.mark_probed();
+        const size_t m = ((size_t)1 << 20) + ((size_t)1 << 17);  // (the feedback's look wants 2^20 decoded records; some may be refused)
         const size_t b0 = (size_t)((double)bytes * (double)m / (double)n);
         int rc0 = ingest_device_records(c, d_buf, len, b0, d_off, m);
         if (rc0) return rc0;
-        rc0 = settle(c);  // (the counters of those records: format_feedback decides between table, scatter sink and log)
+        rc0 = settle(c);  // (the counters of those records: the feedback's look decides between table, scatter sink and log)
         if (rc0) return rc0;
         return ingest_device_records(c, d_buf, len, bytes - b0, (const uint32_t*)d_off + m, n - m);
     }
-    c->wide_probed = true;
+    c->fb.mark_probed();
     if (c->wide_per_record) {
         // a launch may not be able to park more wide-table updates than the spill buffer holds: split it
         const size_t lim = (c->wspill_cap - (1u << 20)) / c->wide_per_record;
@@ -447,13 +447,8 @@ static int ingest_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
             return FA_OK;
         }
     }
-    LaunchPlan p;
-    p.variant = ks_variant(c->cfg.key_sets);
-    // small batches are not worth a second pass: they go straight to the device-wide table
-    p.wave_tiles = (c->cfg.key_sets & FA_KEYS_AS_PAIR) && (c->sink_mode == 2 || (c->sink_mode == 0 && n >= (1u << 15)));
-    // tuple format of this launch (table.cuh): compact 8-byte tuples on the wave-tile kernel with 256 partitions,
-    // unless recent launches showed that this stream's records do not fit them
-    p.t8 = p.wave_tiles && c->plog2 == 8 && c->t8_mode != 2 && (c->t8_mode == 1 || c->stats.batches >= c->t8_wide_until);
+    LaunchPlan p;  // (decided in three stages, launch_plan.h: here, with the grid known, and behind the preparations)
+    plan_sink(p, c->cfg.key_sets, c->sink_mode, n, c->plog2, c->fb, c->stats.batches);
     if (n > AGG_MAX_BATCH && !p.t8) {  // the packed LDS sums of the wide-tuple aggregation hold 2^24 records per launch
         const size_t h = n / 2;
         int rc1 = ingest_device_records(c, d_buf, len, bytes / 2, d_off, h);
@@ -479,9 +474,7 @@ static int ingest_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
         p.grid = with_variant(p.variant, [&](auto v) { return grid_for(c, tile_kernel<MODE_INGEST, decltype(v)::value>, a.n, p.tile_recs); });
     }
     a.tile_recs = p.tile_recs;
-    p.cms_segments = p.wave_tiles && (c->cfg.key_sets & (FA_KEYS_SRCADDR_CMS | FA_KEYS_DSTADDR_CMS)) && !c->cms_atomic && c->cms_scatter_ok;
-    p.wide_segments = p.wave_tiles && c->wtab && (c->cfg.key_sets & FA_KEYS_ADDR_PORT_PROTO) && p.grid <= WAGG_MAX_NWG &&
-                      (c->wide_mode == 2 || c->wide_mode == 3 || (c->wide_mode == 0 && c->wide_scatter));
+    plan_segments(p, c->cfg.key_sets, c->cms_atomic, c->cms_scatter_ok, c->wtab != nullptr, c->fb);
     if (p.wave_tiles) {
         rc = ensure_segments(c, n, p, a);
         if (rc) return rc;
@@ -501,17 +494,14 @@ static int ingest_device_records(fa_ctx* c, const void* d_buf, size_t len, size_
         refresh_table_args(c, a);
     }
     // (what the feedback rules say NOW: a settle inside the preparations above may have moved them)
-    p.wlog = p.wide_segments && (c->wide_mode == 3 || (c->wide_mode == 0 && c->wide_defer));
-    // most records of the last launches needed the order-free parser: the kernel that learns a field order per wave
-    p.seq_variant = p.wave_tiles && c->cfg.key_sets == FA_KEYS_AS_PAIR && c->seq_mode != 2 && (c->seq_mode == 1 || c->stats.batches < c->seq_until);
-    p.side = p.cms_segments && c->cand_stream && c->cand_state;
+    plan_followers(p, c->cfg.key_sets, c->cand_stream && c->cand_state, c->fb, c->stats.batches);
     if (c->wtab) c->wpot_total += (uint64_t)n * c->wide_per_record;  // (rows this launch may open in the wide table: wide_rows_bound)
     rc = launch_tiles<MODE_INGEST>(c, a, p, c->ev_pool.take(3));
     if (rc) return rc;
     if (p.wlog) {
         rc = wlog_record(c, a, n);
         if (rc) return rc;
-    } else if (c->wide_mode == 0 && !c->wide_defer && !c->wlog.empty()) {
+    } else if (c->fb.left_log_mode() && !c->wlog.empty()) {
         // the library left the log mode: what is pending drains - a chunk per launch while wagg_kernel can take it (1.2 ms), one
         // in eight launches when the table has grown since and it is the atomic replay (13 ms for 16.67 M tuples)
         const fa_ctx::WChunk& k = c->wlog.front();

@@ -1,11 +1,13 @@
 // launch_plan.h - what the host decides for ONE ingest or decode launch, as a value, and the functions of plain values behind
-// those decisions (no fa_ctx, no HIP call: tests/host_launch_plan.hip runs them on the host).
+// those decisions, the launch guard's verdict among them (no fa_ctx, no HIP call: tests/host_launch_plan.hip and
+// tests/host_ingest_feedback.hip run them on the host).
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
 #include <utility>
 
+#include "ingest_feedback.h"
 #include "sinks.cuh"
 
 namespace fa {
@@ -70,5 +72,53 @@ struct LaunchPlan {
     bool wlog = false;           // ... which stay where they are as a log chunk (wlog_record) instead of being folded
     bool side = false;           // candidates mode: the flows_5m aggregation runs on the side stream
 };
+
+// The plan is decided in three stages (ingest_device_records calls them in this order), each a function of plain values and
+// of the feedback (ingest_feedback.h: what the earlier launches taught the ctx).
+// Before the launch guard: the sink and the tuple format of a launch of n records, planned at batch count `batches`.
+inline void plan_sink(LaunchPlan& p, uint32_t key_sets, int sink_mode, size_t n, uint32_t plog2, const IngestFeedback& fb, uint64_t batches) {
+    p.variant = ks_variant(key_sets);
+    // small batches are not worth a second pass: they go straight to the device-wide table (sink_mode, env FA_SINK: 0 auto, 1 direct, 2 scatter)
+    p.wave_tiles = (key_sets & FA_KEYS_AS_PAIR) && (sink_mode == 2 || (sink_mode == 0 && n >= (1u << 15)));
+    // tuple format of this launch (table.cuh): compact 8-byte tuples on the wave-tile kernel with 256 partitions,
+    // unless recent launches showed that this stream's records do not fit them
+    p.t8 = p.wave_tiles && plog2 == 8 && fb.compact_tuples(batches);
+}
+// With p.grid known: which of the other sinks' updates leave as tuples too.
+inline void plan_segments(LaunchPlan& p, uint32_t key_sets, bool cms_atomic, bool cms_scatter_ok, bool wide_table, const IngestFeedback& fb) {
+    p.cms_segments = p.wave_tiles && (key_sets & (FA_KEYS_SRCADDR_CMS | FA_KEYS_DSTADDR_CMS)) && !cms_atomic && cms_scatter_ok;
+    p.wide_segments = p.wave_tiles && wide_table && (key_sets & FA_KEYS_ADDR_PORT_PROTO) && p.grid <= WAGG_MAX_NWG && fb.wide_scatter_sink();
+}
+// Behind the preparations (a settle inside them may have moved the feedback: this is what it says NOW).
+inline void plan_followers(LaunchPlan& p, uint32_t key_sets, bool candidates, const IngestFeedback& fb, uint64_t batches) {
+    p.wlog = p.wide_segments && fb.log_mode();
+    // most records of the last launches needed the order-free parser: the kernel that learns a field order per wave
+    p.seq_variant = p.wave_tiles && key_sets == FA_KEYS_AS_PAIR && fb.learnt_order(batches);
+    p.side = p.cms_segments && candidates;
+}
+
+// ---- the launch guard: never lose aggregates ----
+// What the newest counter snapshot says about a launch of n more records: a table above 50 % load or parked updates are
+// settled (grow + replay) right away; a launch is only queued while the updates that everything in flight could park still
+// fit the spill buffers - otherwise the host first waits for the newest snapshot (pre_launch_guard, maintain_host.inc).
+enum GuardVerdict { GUARD_GO = 0, GUARD_WAIT = 1, GUARD_SETTLE = 2 };
+struct GuardSnapshot {  // of the newest Counters the host has seen
+    uint32_t spill_count, wspill_count;
+    uint64_t used, wused;
+};
+struct GuardHost {
+    uint64_t used_base, wused_base;    // groups created before the current counter epoch
+    uint64_t slots, wslots;            // the two tables' sizes
+    uint32_t spill_cap, wspill_cap;
+    bool wide_table;
+    uint32_t wide_per_record;          // wide-table updates one record can cause
+    uint64_t in_flight;                // records launched behind the snapshot
+};
+inline GuardVerdict guard_verdict(const GuardSnapshot& h, const GuardHost& c, size_t n) {
+    if (h.spill_count || h.wspill_count || (c.used_base + h.used) * 2 > c.slots || (c.wide_table && (c.wused_base + h.wused) * 2 > c.wslots)) return GUARD_SETTLE;
+    const uint64_t pot = c.in_flight + n;  // records whose updates the host has not seen settle
+    if (pot + (1u << 20) > c.spill_cap || (c.wide_table && pot * c.wide_per_record + (1u << 20) > c.wspill_cap)) return GUARD_WAIT;
+    return GUARD_GO;
+}
 
 }  // namespace fa

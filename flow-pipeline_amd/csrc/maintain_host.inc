@@ -100,61 +100,9 @@ static int settle_wide(fa_ctx* c, Counters& h) {
 
 static int cms_fold(fa_ctx* c);
 
-// tuple-format feedback (what the next LaunchPlan::t8 is decided from): h = counters at least as new as the last look
-static void format_feedback(fa_ctx* c, const Counters& h) {
-    const uint64_t d_mis = h.misfit8 - c->seen_misfit8, d_ok = h.ok - c->seen_ok;
-    if (d_ok && d_mis * 16 > d_ok) c->t8_wide_until = c->stats.batches + 64;
-    // records that went through the second-chance parsers: most of them -> the kernel variant that learns the producer's field order
-    if (h.retried < c->seen_retried) c->seen_retried = h.retried;
-    if (d_ok && (h.retried - c->seen_retried) * 2 > d_ok) c->seq_until = c->stats.batches + 64;
-    c->seen_retried = h.retried;
-    c->seen_misfit8 = h.misfit8;
-    c->seen_ok = h.ok;
-    if (c->wtab && !c->wide_defer) {  // (SrcAddr,DstPort,Proto): scatter sink or atomics, by the share of records that opened a row lately
-        if (h.wused < c->seen_wused) c->seen_wused = h.wused;  // (table rebuilt: the count starts over)
-        if (h.ok < c->seen_ok_w) c->seen_ok_w = h.ok;
-        const uint64_t dw = h.wused - c->seen_wused, dn = h.ok - c->seen_ok_w;
-        if (dn >= (1u << 20)) {
-            if (dw * 5 > dn) c->wide_scatter = true;
-            else if (dw * 10 < dn) c->wide_scatter = false;
-            // ... and no table at all for a stream that opens a row for most of its records: the log (fa_ctx::wlog)
-            if (c->wide_mode == 0 && c->wide_scatter && dw * 2 > dn && c->wlog_max > 0) {
-                c->wide_defer = true;
-                c->seen_wfold = h.wfold_n;
-            }
-            c->seen_wused = h.wused;
-            c->seen_ok_w = h.ok;
-        }
-    }
-    if (c->wtab && c->wide_defer && c->wide_mode == 0) {  // log mode chosen by the library: do the chunks that ARE folded still open rows?
-        const uint64_t dn = h.wfold_n - c->seen_wfold;
-        if (h.wused < c->seen_wused || h.wfold_n < c->seen_wfold) {  // (table rebuilt / counters restarted: no verdict from this look)
-            c->seen_wused = h.wused;
-            c->seen_wfold = h.wfold_n;
-        } else if (dn >= (1u << 20)) {
-            // fewer than half of the folded tuples opened a row: this stream aggregates - back to the table (scatter sink or
-            // atomics, by the feedback above); the chunks still pending are folded one per launch (fa_ingest_device)
-            if ((h.wused - c->seen_wused) * 2 < dn) {
-                c->wide_defer = false;
-                c->seen_ok_w = h.ok;
-            }
-            c->seen_wused = h.wused;
-            c->seen_wfold = h.wfold_n;
-        }
-    }
-    // passes of agg8_kernel: the groups a launch adds to the device table, per partition and pass, against the LDS table
-    if (h.agg_launches < c->seen_agg_launches || h.agg_groups < c->seen_agg_groups) c->seen_agg_launches = c->seen_agg_groups = 0;
-    const uint64_t d_l = h.agg_launches - c->seen_agg_launches, d_g = h.agg_groups - c->seen_agg_groups;
-    if (d_l) {
-        const uint64_t per_part = d_g / d_l >> c->plog2;
-        uint32_t want = 1;
-        while (want < 8 && per_part > (uint64_t)(AGG8_SLOTS / 2) * want) want *= 2;
-        // (a launch that overflowed its table under-counts: move up one step at a time, down only when clearly below)
-        if (want > c->agg_passes) c->agg_passes = std::min(want, c->agg_passes * 2);
-        else if (want < c->agg_passes && per_part * 3 < (uint64_t)(AGG8_SLOTS / 2) * c->agg_passes) c->agg_passes = std::max(want, c->agg_passes / 2);
-        c->seen_agg_launches = h.agg_launches;
-        c->seen_agg_groups = h.agg_groups;
-    }
+// one look of the adaptive feedback (ingest_feedback.h: what the next LaunchPlans are decided from): h = counters at least as new as the last look's
+static void feedback_look(fa_ctx* c, const Counters& h) {
+    c->fb.look(FeedbackLook{h.ok, h.misfit8, h.retried, h.wused, h.wfold_n, h.agg_launches, h.agg_groups}, c->stats.batches);
 }
 
 // Waits for the stream, folds device counters into stats, replays spills after growing.
@@ -187,7 +135,7 @@ static int settle(fa_ctx* c) {
     c->stats.records_misfit_compact = h.misfit8;
     c->stats.records_late = h.late;
     c->stats.table_used = c->used_base + h.used;
-    format_feedback(c, h);
+    feedback_look(c, h);
     if (h.spill_lost) {
         c->sticky = FA_ERR_TABLE_FULL;
         return fail(c, FA_ERR_TABLE_FULL, "group-by table and spill buffer overflowed; aggregates were lost");
@@ -392,28 +340,26 @@ static void poll_snapshots(fa_ctx* c, bool wait_newest) {
             c->known_records = c->snap_records[k];
             c->known_seq = q;
             c->known_wpot = c->snap_wpot[k];
-            format_feedback(c, c->known);
+            feedback_look(c, c->known);
             return;
         }
     }
 }
 static int pre_launch_guard(fa_ctx* c, size_t n) {
-    auto verdict = [&]() -> int {  // 0 go, 1 look again after waiting, 2 settle
+    auto verdict = [&]() {  // (guard_verdict, launch_plan.h, on the newest snapshot the host has seen)
         const Counters& h = c->known;
-        if (h.spill_count || h.wspill_count || (c->used_base + h.used) * 2 > (1ull << c->cap_log2) ||
-            (c->wtab && (c->wused_base + h.wused) * 2 > (1ull << c->wcap_log2)))
-            return 2;
-        const uint64_t pot = (c->launched_records - c->known_records) + n;  // records whose updates the host has not seen settle
-        if (pot + (1u << 20) > c->spill_cap || (c->wtab && pot * c->wide_per_record + (1u << 20) > c->wspill_cap)) return 1;
-        return 0;
+        return guard_verdict(GuardSnapshot{h.spill_count, h.wspill_count, h.used, h.wused},
+                             GuardHost{c->used_base, c->wused_base, 1ull << c->cap_log2, 1ull << c->wcap_log2, c->spill_cap, c->wspill_cap, c->wtab != nullptr,
+                                       c->wide_per_record, c->launched_records - c->known_records},
+                             n);
     };
     poll_snapshots(c, false);
-    int v = verdict();
-    if (v == 1) {
+    GuardVerdict v = verdict();
+    if (v == GUARD_WAIT) {
         poll_snapshots(c, true);
-        v = verdict() ? 2 : 0;
+        v = verdict() != GUARD_GO ? GUARD_SETTLE : GUARD_GO;
     }
-    return v == 2 ? settle(c) : FA_OK;
+    return v == GUARD_SETTLE ? settle(c) : FA_OK;
 }
 static int post_launch_snapshot(fa_ctx* c, size_t n) {
     c->launched_records += n;

@@ -69,6 +69,8 @@ constexpr int AGG_BLOCK = 1024;    // agg_kernel: 16 waves share one LDS table
 #endif
 constexpr int AGG_SLOTS = FA_AGG_SLOTS;  // 32 B of LDS per slot (4096: 128 KiB)
 constexpr int AGG_PROBES = 16;
+constexpr int AGG8_SLOTS = 4096;     // agg8_kernel's LDS table (agg.cuh); the host's pass-count feedback measures against it (ingest_feedback.h)
+constexpr int WAGG_MAX_NWG = 1536;   // wagg_kernel: segments per region it can take (wagg.cuh); a launch with more workgroups keeps the atomic path (launch_plan.h)
 constexpr uint32_t AGG_MAX_BATCH = 1u << 24;  // wide tuples: count <= 2^24 per slot keeps the packed LDS sums exact (Packets < 2^15: 15 + 24 + 25 bits)
 constexpr uint32_t AGG8_MAX_BATCH = (1u << 25) - 1u;  // compact tuples (Packets < 2^9): 25 bits of count
 static_assert(TILE_STRIDE % 16 == 0, "LDS tile buffers must stay 16-byte aligned");

@@ -34,7 +34,6 @@ constexpr int WAGG_BLOCK = FA_WAGG_BLOCK;
 constexpr int WAGG_U = FA_WAGG_U;                      // tuples per thread and chunk
 constexpr int WAGG_CHUNK = WAGG_BLOCK * WAGG_U;
 constexpr int WAGG_SLOTS = 2 * WAGG_CHUNK;             // LDS table of representatives: load <= 0.5
-constexpr int WAGG_MAX_NWG = 1536;
 
 struct WAggLds {
     uint32_t prefix[WAGG_MAX_NWG + 1];

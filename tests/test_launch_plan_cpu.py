@@ -18,7 +18,7 @@ def _run():
     exe = os.path.join(out, "host_launch_plan")
     src = os.path.join(ROOT, "tests", "host_launch_plan.hip")
     csrc = os.path.join(ROOT, "flow-pipeline_amd", "csrc")
-    deps = [src, os.path.join(csrc, "launch_plan.h"), os.path.join(csrc, "sinks.cuh")]
+    deps = [src, os.path.join(csrc, "launch_plan.h"), os.path.join(csrc, "ingest_feedback.h"), os.path.join(csrc, "sinks.cuh")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-o", exe, src])
     res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
